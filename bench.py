@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """bench.py - agent-steps/s of the per-tick agent-update path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4096] [--vehicles 1000000] [--policy full]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4096] [--vehicles 1000000] [--policy full] [--full]
+                    [--dump-outputs DIR]
 
 A "step" is one CityModel.step() tick over the synthetic workload.  At N=1 the workload is the configuration
 BASELINE.json's metric is quoted on - a 4096x4096 procedurally generated city with 10^6 vehicles - under the
 reference's DEFAULT policy (`--policy full`: QUEUE_ACTUATED light groups, replanning with the GPU A*, contraflow
 overtakes / detours, malfunctions and sideswipes; config.py untouched apart from rain and spawning being off so that the
 population is closed).  The reduced policies of BASELINE configs 2 / 3-without-searches are kept as
-`--policy config2` / `--policy lights` and are reported, for the same world, as `secondary` fields of the N=1 line.
+`--policy config2` / `--policy lights` and are reported, for the same world, as `secondary` fields of the N=1 --full line.
 
 N>1: one process per GPU.  `python bench.py --gpus N` without a torchrun environment launches its own N ranks
 (torch.distributed.run, 127.0.0.1) before anything touches a GPU; under the driver's torchrun it reads
@@ -20,9 +21,13 @@ RANK / LOCAL_RANK / WORLD_SIZE.  Two bit-exact multi-GPU modes:
 
 Prints ONE JSON line on rank 0 with the contract fields plus
   "roofline":     the dominant kernel of THIS run: algorithmic bytes (for k_decide_replan SURVEY.md §8(d)'s
-                  50 B per expansion + 25 B per relaxation) / HIP-event time, against 8 TB/s HBM
+                  50 B per expansion + 25 B per relaxation) / HIP-event time, against 8 TB/s HBM.
+A plain run sets up, warms up, times the K steps and prints that line.  --full adds what takes runs of its own:
   "cpu_baseline": the CPU oracle (single-threaded C++ restatement, kind "port") on a bounded sample of the same workload,
-                  timed on this box's host cores in a child process while the GPU leg runs (rank 0, N=1 only).
+                  timed on this box's host cores in a child process while the GPU leg runs (rank 0, N=1 only);
+  "secondary":    the reduced policies on the same world (N=1, --policy full only);
+  "config.ranks_hold_identical_state": N>1 sharded mode, every rank's state compared after the run.
+--dump-outputs DIR writes what the last timed step left a caller (dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -31,6 +36,7 @@ import subprocess
 import sys
 import tempfile
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -77,8 +83,88 @@ def make_workload(size, vehicles, seed, world="synthetic", carves=False):
         tables = citygen.generate(size, size, seed=seed, carve_subblock_roads=bool(carves))
     t1 = time.time()
     lo, hi = (150, 400) if size >= 1024 else (30, 120)
-    routes = citygen.make_routes(tables, vehicles, seed=seed + 1, min_len=lo, max_len=hi)
+    routes = make_routes(tables, vehicles, seed=seed + 1, min_len=lo, max_len=hi)
     return tables, routes, (t1 - t0, time.time() - t1)
+
+
+ROUTE_BLOCK = 32    # walk steps per round of draws
+
+
+def make_routes(tables, n_vehicles, seed, min_len, max_len, keep_heading=0.85, threads=None):
+    """citygen.make_routes, the same routes bit for bit (tests/test_bench.py), with the walk spread over host threads: a walk
+    depends on no other vehicle, only on its columns of the draws, so one thread draws them in citygen's order, ROUTE_BLOCK
+    steps at a time, while the others walk their share of the live vehicles (at 4096^2 / 10^6 a serial walk is most of the
+    plain run's set-up)."""
+    from trafficsimulation_amd.citygen import DX, DY
+    rng = np.random.RandomState(seed)
+    allowed = tables["allowed_dirs_map"]
+    H, W = allowed.shape
+    aflat = allowed.ravel()
+    cand = np.flatnonzero((tables["is_road_map"].ravel() == 1) & (tables["intersection_map"].ravel() == 0) & (aflat != 0))
+    V = min(int(n_vehicles), len(cand))
+    start = rng.choice(cand, size=V, replace=False)
+    want = rng.randint(min_len, max_len + 1, size=V)
+    L = int(want.max())
+    if V * L > 2_000_000_000:
+        raise MemoryError("route buffer too large; lower max_len")
+    opts = np.zeros((16, 4), np.int64)      # for each bitmask, its set directions in turn (citygen.make_routes)
+    for b in range(1, 16):
+        ds = [k for k in range(4) if b & (1 << k)]
+        opts[b] = [ds[q % len(ds)] for q in range(4)]
+    drivable = (tables["is_road_map"].ravel() == 1) | (aflat != 0)
+    step = np.array([W, 1, -W, -1])
+    pos, heading, length = start.copy(), np.full(V, -1, np.int64), np.zeros(V, np.int64)
+    dirs = np.zeros((V, L), np.uint8)
+
+    def walk(idx, t0, picks, keeps):
+        """Steps t0.. of the block for the live vehicles idx; -> those still walking."""
+        for t in range(t0, min(t0 + ROUTE_BLOCK, L)):
+            if not len(idx):
+                break
+            p, h = pos[idx], heading[idx]
+            bits = aflat[p].astype(np.int64)
+            bits_nr = bits & ~np.where(h >= 0, 1 << ((h + 2) & 3), 0)      # never reverse
+            bits = np.where(bits_nr != 0, bits_nr, bits)
+            keep = (h >= 0) & ((bits >> np.maximum(h, 0)) & 1).astype(bool) & keeps[t - t0, idx]
+            d = np.where(keep, h, opts[bits, picks[t - t0, idx]])
+            npos = p + step[d]
+            nx, ny = p % W + DX[d], p // W + DY[d]
+            inb = (nx >= 0) & (nx < W) & (ny >= 0) & (ny < H)
+            ok = (bits != 0) & (want[idx] > t) & inb         # (a live vehicle has walked t cells)
+            ok &= drivable[np.where(inb, npos, 0)]
+            idx, d = idx[ok], d[ok]
+            dirs[idx, t] = d
+            pos[idx] = npos[ok]
+            heading[idx] = d
+            length[idx] += 1
+        return idx
+
+    def draw():
+        picks, keeps = np.empty((ROUTE_BLOCK, V), np.int8), np.empty((ROUTE_BLOCK, V), bool)
+        for i in range(ROUTE_BLOCK):
+            picks[i] = rng.randint(0, 4, size=V)
+            keeps[i] = rng.rand(V) < keep_heading
+        return picks, keeps
+
+    n = threads or min(16, len(os.sched_getaffinity(0)))
+    live = np.array_split(np.arange(V), 4 * n)
+    with ThreadPoolExecutor(n) as ex:
+        block = draw()
+        for t0 in range(0, L, ROUTE_BLOCK):
+            futs = [ex.submit(walk, idx, t0, *block) for idx in live]
+            if t0 + ROUTE_BLOCK < L:
+                block = draw()          # (numpy draws and the walks' array operations run outside the GIL)
+            live = [f.result() for f in futs]
+            if not any(len(idx) for idx in live):
+                break
+    keepv = (length > 0) & (pos != start)   # start == goal would despawn inside the decide phase
+    start, pos, length, dirs = start[keepv], pos[keepv], length[keepv], dirs[keepv]
+    path_off = np.zeros(len(start) + 1, np.int64)
+    path_off[1:] = np.cumsum(length)
+    flat = dirs[np.arange(L)[None, :] < length[:, None]]
+    start_xy = np.stack([start % W, start // W], axis=1).astype(np.int32)
+    goal_xy = np.stack([pos % W, pos // W], axis=1).astype(np.int32)
+    return start_xy, goal_xy, path_off, flat
 
 
 def setup(api, tables, routes, seed, extra=None, policy="config2"):
@@ -93,6 +179,32 @@ def setup(api, tables, routes, seed, extra=None, policy="config2"):
     s, g, off, dirs = routes
     api.add_vehicles_dirs(s, g, np.full(len(s), capi.POP["through"], np.int32), off, dirs)
     return api
+
+
+DUMP_ROWS = 1 << 17     # --dump-outputs: vehicle / light-group rows kept (a seeded sample above that)
+DUMP_CELLS = 1 << 20    # --dump-outputs: cells kept per map (a seeded sample above that); at most ~40 MB in all
+
+
+def _sample(n, k, seed):
+    return np.arange(n) if n <= k else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(api, out_dir):
+    """What the engine hands a caller after the last step, as out_dir/<name>.npy: the vehicle and light-group tables (float64,
+    exact for their int32 fields), the occupancy / stop / stuck maps (float32, flattened) and the counter block (float64, in
+    TsCounters' field order).  Above DUMP_ROWS rows / DUMP_CELLS cells a fixed seeded sample, in order."""
+    from trafficsimulation_amd import _capi as capi
+    os.makedirs(out_dir, exist_ok=True)
+    veh, grp = api.vehicles(), api.groups()
+    out = {"vehicles": veh[_sample(len(veh), DUMP_ROWS, 1)].astype(np.float64),
+           "groups": grp[_sample(len(grp), DUMP_ROWS, 2)].astype(np.float64)}
+    cells = _sample(api.H * api.W, DUMP_CELLS, 3)
+    for name, which in (("occupancy", capi.MAP_OCCUPANCY), ("stop", capi.MAP_STOP), ("stuck", capi.MAP_STUCK)):
+        out[name] = api.map(which).ravel()[cells].astype(np.float32)
+    c = api.counters()
+    out["counters"] = np.array([getattr(c, f) for f, _ in c._fields_], np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_leg(args):
@@ -174,8 +286,12 @@ def main():
                          "rehearsing the N>1 path with several ranks on one GPU (local rank r uses device r %% visible devices)")
     ap.add_argument("--exchange", choices=["device", "host"], default="device",
                     help="sharded mode: records exchanged between device buffers (default) or staged through host memory")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the reduced-policy legs of the N=1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the reduced-policy legs and the ranks' state comparison (off: only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the reduced-policy legs of the N=1 line")
     ap.add_argument("--cpu-seconds", type=float, default=25.0)
     ap.add_argument("--cpu-max-ticks", type=int, default=1000)
     ap.add_argument("--cpu-only", action="store_true", help=argparse.SUPPRESS)
@@ -183,6 +299,8 @@ def main():
     args = ap.parse_args()
     if args.cpu_only:
         return cpu_leg(args)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if args.gpus > 1 and env_world == 0:
@@ -196,7 +314,7 @@ def main():
 
     # the CPU leg runs beside the GPU leg on otherwise idle host cores (N=1 only)
     cpu_proc, cpu_out = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_out = tempfile.NamedTemporaryFile("w", suffix=".jsonl", delete=False).name
         cpu_proc = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--cpu-only", "--cpu-out", cpu_out,
                                      "--size", str(args.size), "--vehicles", str(args.vehicles), "--seed", str(args.seed),
@@ -278,12 +396,14 @@ def main():
     live_end = api.num_vehicles()
     # sharded mode: every rank must hold the same world after the run (both RNG streams, the counters the searches feed)
     same_state = None
-    if world > 1 and mode == "sharded":
+    if args.full and world > 1 and mode == "sharded":
         mine = [list(api.rng_fingerprint(capi_mod.RNG_GLOBAL)), list(api.rng_fingerprint(capi_mod.RNG_SCHEDULER)), int(c1.agent_steps),
                 int(c1.astar_calls), int(c1.stuck), int(c1.count_completed_through), int(live_end)]
         every = [None] * world
         dist.all_gather_object(every, mine)
         same_state = all(x == every[0] for x in every)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(api, args.dump_outputs)
     api.close()
 
     out = None
@@ -391,7 +511,7 @@ def main():
             out["config"]["exchange"] = {"calls": sharder.calls, "bytes_sent_by_rank0": sharder.bytes_sent}
 
     # the reduced policies on the same world (N=1 only): the car-following / movement / light kernels without the searches
-    if rank == 0 and world == 1 and not args.no_secondary and args.policy == "full":
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.policy == "full":
         sec = {}
         for pol in ("config2", "lights"):
             e2 = new_engine()

@@ -6,7 +6,7 @@ set -e -o pipefail
 R=$(pwd)
 OUT=$R/gpurun_out
 mkdir -p $OUT
-ARGS="--gpus 1 --steps 20 --warmup 5"
+ARGS="--gpus 1 --steps 20 --warmup 5 --full"
 python bench.py $ARGS > $OUT/fin_bench.json 2> $OUT/fin_bench.err
 echo "bench done"
 cd /tmp && export TMPDIR=/tmp

@@ -7,9 +7,9 @@ under profiles/:
                                                                           per kernel: launches, avg / max KB per launch
 
 Collected with (separate runs, as MI355X_MICROARCH.md prescribes; `cd /tmp && export TMPDIR=/tmp` first):
-  rocprofv3 --kernel-trace --stats -d <dir> -o bench -- python3 bench.py --steps 50 --warmup 5
-  rocprofv3 --pmc FETCH_SIZE -d <dir> -o pmc -- python3 bench.py --steps 12 --warmup 3
-  rocprofv3 --pmc WRITE_SIZE -d <dir> -o pmc -- python3 bench.py --steps 12 --warmup 3
+  rocprofv3 --kernel-trace --stats -d <dir> -o bench -- python3 bench.py --steps 50 --warmup 5 --full
+  rocprofv3 --pmc FETCH_SIZE -d <dir> -o pmc -- python3 bench.py --steps 12 --warmup 3 --full
+  rocprofv3 --pmc WRITE_SIZE -d <dir> -o pmc -- python3 bench.py --steps 12 --warmup 3 --full
 """
 import collections, csv, json, re, sqlite3, sys
 
@@ -83,7 +83,7 @@ def main():
                       write_kb_avg=sum(wv) / max(len(wv), 1), write_kb_max=max(wv) if wv else 0.0)
     if len(sys.argv) > 5:      # bench.py reads `kernels` when `command_config` = [size, vehicles, policy, steps, warmup] matches its run
         size, vehicles, policy, steps, warmup = sys.argv[5].split(",")
-        out = {"command": f"python3 bench.py --steps {steps} --warmup {warmup} --no-cpu-baseline (full-policy leg + the config2 / lights secondary legs, one process)",
+        out = {"command": f"python3 bench.py --steps {steps} --warmup {warmup} --full --no-cpu-baseline (full-policy leg + the config2 / lights secondary legs, one process)",
                "command_config": [int(size), int(vehicles), policy, int(steps), int(warmup)],
                "note": "KB per launch as rocprofv3 reports them; bench.py doubles FETCH_SIZE (gfx950: 128-B requests tallied at 64 B)",
                "kernels": out}

@@ -42,7 +42,8 @@ for name in %(traces)r:
     res[name] = dict(ticks=n, astar_calls=int(c.astar_calls), want_calls=int(tr["astar_calls_spawn"]) + int(tr["astar_per_tick"].sum()),
                      exchanges=sr.calls, bytes=sr.bytes_sent, fp=list(api.rng_fingerprint(capi.RNG_GLOBAL)))
     api.close()
-print(json.dumps(dict(rank=rank, res=res)), flush=True)
+with open(os.path.join(%(outdir)r, "rank%%d.json" %% rank), "w") as f:      # (one file per rank: lines printed to the
+    json.dump(dict(rank=rank, res=res), f)                                  # shared stdout of the ranks can interleave)
 d.destroy_process_group()
 '''
 
@@ -63,15 +64,15 @@ def test_ranks_sharded_replans_match_the_reference(world, device_direct, tight_p
         env["TS_QUAD"], env["TS_QUAD_MIN"] = "1", "1"
     if tight_pool:      # (almost no room reserved in the path pool: planners find it full, the pool is garbage-collected / grown INSIDE the
         env["TS_DEBUG_POOL_PER_ENTRY"] = "2"      # sharded tick, and the export must not rely on the pool's growth to size its buffer)
-    with tempfile.NamedTemporaryFile("w", suffix=".py", delete=False) as f:
-        f.write(WORKER % dict(root=ROOT, traces=traces, device_direct=device_direct))
-        path = f.name
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", port, path]
-    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
-    os.unlink(path)
-    assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
-    rows = [json.loads(line) for line in out.stdout.splitlines() if line.startswith('{"rank"')]
+    with tempfile.TemporaryDirectory() as outdir:
+        path = os.path.join(outdir, "worker.py")
+        with open(path, "w") as f:
+            f.write(WORKER % dict(root=ROOT, traces=traces, device_direct=device_direct, outdir=outdir))
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
+               "--master-addr", "127.0.0.1", "--master-port", port, path]
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+        rows = [json.load(open(os.path.join(outdir, n))) for n in sorted(os.listdir(outdir)) if n.startswith("rank")]
     assert sorted(r["rank"] for r in rows) == list(range(world))
     rows = sorted(rows, key=lambda r: r["rank"])
     r0 = rows[0]
@@ -138,7 +139,7 @@ def test_bench_two_ranks_over_gloo_smoke():
     reports the process group's size and that both ranks ended in the same state."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "512", "--vehicles", "12000",
-           "--steps", "4", "--warmup", "4", "--no-cpu-baseline", "--no-secondary"]
+           "--steps", "4", "--warmup", "4", "--full", "--no-cpu-baseline", "--no-secondary"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     row = json.loads([line for line in out.stdout.splitlines() if line.startswith("{")][-1])
