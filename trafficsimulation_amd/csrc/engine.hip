@@ -45,31 +45,177 @@
 
 namespace {
 
-// The replanning work queue (k_replan): replan_n[0..3] = class list lengths as k_decide_main left them (e->hint[8..]),
+// a host step that returns a TS_* code: a failure is passed on
+#define TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)
+
+// grow a device buffer to `nc` elements (its contents are not kept) when its capacity `cap` is below `need`
+template <typename T, typename C>
+int grow(E* e, T** p, C& cap, size_t need, size_t nc) {
+  if (need <= (size_t)cap) return TS_OK;
+  TRY(regrow(e, p, 0, nc));
+  cap = (C)nc;
+  return TS_OK;
+}
+// copy `bytes` from the device and wait for them (and for everything queued before)
+int read_back(E* e, void* dst, const void* src, size_t bytes) {
+  HIPOK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPOK(hipStreamSynchronize(e->stream));
+  return TS_OK;
+}
+
+// The replanning work queue (k_replan): replan_n[0..3] = class list lengths as k_decide_main left them (e->hm->replan_n),
 // lists 0..3 = the classes, list 4 = entries that found the path pool full.
 inline int replan_pending(const int* n8) { return n8[0] + n8[1] + n8[2] + n8[3]; }
 
 constexpr int SEG_VEHICLES = 1 << 20;   // vehicles per decide pass (bounds one pass' look-ahead into the MT19937 word ring)
 
-int run_replans(E* e) {   // e->hint[8..15] = replan_n as k_decide_main left it
+inline RLists replan_lists(const E* e) {
+  RLists rl;
+  for (int q = 0; q < 6; q++) rl.l[q] = e->replan_list[q];
+  return rl;
+}
+
+// Order class list h (n entries) by its sort key.  Sharded, the order must be total and the same on every rank: 64-bit keys
+// that end in the entry itself; otherwise key/value pairs.
+int sort_replan_list(E* e, int h, int n, bool sharded) {
+  Dev& d = e->d;
+  hipStream_t st = e->stream;
+  int32_t* list = e->replan_list[h];
+  if ((size_t)n > e->cap_sortbuf) {
+    const size_t nc = (size_t)n * 2;
+    TRY(regrow(e, &e->sort_keys, 0, nc * 2));          // (room for 64-bit keys)
+    TRY(regrow(e, &e->sort_keys_alt, 0, nc * 2));
+    TRY(regrow(e, &e->sort_vals_alt, 0, nc));
+    e->cap_sortbuf = nc;
+  }
+  unsigned long long* k0 = (unsigned long long*)e->sort_keys;
+  unsigned long long* k1 = (unsigned long long*)e->sort_keys_alt;
+  auto sort = [&](void* tmp, size_t& tmp_bytes) {
+    return sharded ? hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, k0, k1, n, 0, 32 + REPLAN_KEY_BITS, st)
+                   : hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, e->sort_keys, e->sort_keys_alt, list, e->sort_vals_alt, n, 0,
+                                                        REPLAN_KEY_BITS, st);
+  };
+  if (sharded) hipLaunchKernelGGL(k_replan_keys64, dim3(nblk(n)), dim3(BLK), 0, st, d, list, n, k0);
+  else hipLaunchKernelGGL(k_replan_keys, dim3(nblk(n)), dim3(BLK), 0, st, d, list, n, e->sort_keys);
+  size_t tmp_bytes = 0;
+  HIPOK(sort(nullptr, tmp_bytes));
+  TRY(grow(e, &e->sort_tmp, e->cap_sorttmp, tmp_bytes, tmp_bytes * 2));
+  HIPOK(sort(e->sort_tmp, tmp_bytes));
+  if (sharded) hipLaunchKernelGGL(k_replan_unkey64, dim3(nblk(n)), dim3(BLK), 0, st, k1, n, list);
+  else HIPOK(hipMemcpyAsync(list, e->sort_vals_alt, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+  return TS_OK;
+}
+
+// What is left of a replanning pass becomes the whole queue, in list 0: `left` entries of `handed_back` (the quads' hand-backs
+// k_replan did not get to), then the `retry` entries that found the path pool full, once there is room for them.  replan_n[6]
+// (the entries this rank planned) is kept.
+int requeue_in_list0(E* e, const int32_t* handed_back, int left, int retry) {
+  Dev& d = e->d;
+  hipStream_t st = e->stream;
+  if (retry > 0) {
+    d.pool_cap_words = e->pool_cap;
+    TRY(pool_make_room(e, (size_t)retry * 1024 + (1u << 20)));
+  }
+  if (left > 0) HIPOK(hipMemcpyAsync(e->replan_list[0], handed_back, (size_t)left * 4, hipMemcpyDeviceToDevice, st));
+  if (retry > 0) HIPOK(hipMemcpyAsync(e->replan_list[0] + left, e->replan_list[4], (size_t)retry * 4, hipMemcpyDeviceToDevice, st));
+  int* rn = e->hm->replan_n;
+  const int keep_owned = rn[6];
+  for (int q = 0; q < 8; q++) rn[q] = 0;
+  rn[0] = left + retry; rn[6] = keep_owned;
+  HIPOK(hipMemcpyAsync(d.cnt->replan_n, rn, sizeof(int) * 8, hipMemcpyHostToDevice, st));
+  return TS_OK;
+}
+
+// The quad pass of a big queue (see run_replans): the classes in TS_QUAD_CLASSES go to k_replan_quad while k_replan serves the
+// others and the quads' hand-backs beside it.  What neither got to is queued again in list 0.
+int run_quad_pass(E* e, const RLists& rl) {
   Dev& d = e->d;
   const TsParams& P = e->P;
   hipStream_t st = e->stream;
-  RLists rl;
-  for (int q = 0; q < 6; q++) rl.l[q] = e->replan_list[q];
-  int rc = ensure_slots(e);
-  if (rc) return rc;
-  if (!e->density_valid) { rc = ensure_density(e, d.occ_snap); if (rc) return rc; e->density_valid = true; }
-  rc = ensure_amap(e);
-  if (rc) return rc;
+  HostMirror& hm = *e->hm;
+  const int quad_mask = getenv("TS_QUAD_CLASSES") ? atoi(getenv("TS_QUAD_CLASSES")) & 15 : 7;
+  int nq = 0, nw = 0;
+  for (int c = 0; c < 4; c++) { if ((quad_mask >> c) & 1) nq += hm.replan_n[c]; else nw += hm.replan_n[c]; }
+  const double tl = now_ms();
+  TRY(arena_to_quads(e));
+  HIPOK(hipMemsetAsync(d.cnt->quad_n, 0, sizeof(int) * 4, st));
+  int tok = prof_begin(e, PK_REPLAN, nq + nw);
+  int qgrid = 0;
+  if (nq > 0) {
+    HIPOK(hipMemsetAsync(e->replan_list[5], 0xFF, (size_t)nq * 4, st));     // (hand-back entries: -1 = not written yet)
+    HIPOK(hipEventRecord(e->quad_ev0, st));
+    HIPOK(hipStreamWaitEvent(e->quad_stream, e->quad_ev0, 0));
+    qgrid = std::min((nq + 15) / 16, e->qslots.n_slots / 16);
+    if (g_trace_launches) { fprintf(stderr, "[launch] k_replan_quad items=%d grid=%d\n", nq, qgrid); fflush(stderr); }
+    hipLaunchKernelGGL(k_replan_quad, dim3(qgrid), dim3(64), 0, e->quad_stream, d, P, e->qslots, rl, quad_mask, e->replan_list[4],
+                       e->replan_list[5], e->dist_rank, e->dist_world, e->dist_world > 1 ? e->owned_list : nullptr);
+    HIPOK(hipEventRecord(e->quad_ev1, e->quad_stream));
+  }
+  // (k_replan never holds anything the quads wait for: were the two launches ever serialised, it would simply find the
+  // hand-back list complete)
+  // k_replan's waves beside the quads serve the most expensive class and the quads' hand-backs: 512 of them for a wave that hands back
+  // thousands, 384 once the previous wave handed back few (they take issue slots from the quads: measured on the bench workload's four
+  // waves, 5 678 / 2 895 / 1 379 / 2 514 hand-backs: 4.18 / 3.65 / 3.22 / 2.69 s with 512, 4.56 / 3.33 / 2.88 / 2.44 s with 384)
+  const int side_waves = getenv("TS_QUAD_SIDE_WAVES") ? atoi(getenv("TS_QUAD_SIDE_WAVES"))
+                                                      : (e->quad_last_fb < 0 || e->quad_last_fb > 4096 ? 512 : 384);
+  const int wgrid = std::min(e->side_slots, std::max(std::min(nw, e->side_slots), nq > 0 ? side_waves : 1));
+  if (nw > 0 || nq > 0)
+    hipLaunchKernelGGL(k_replan, dim3(wgrid), dim3(64), 0, st, d, P, e->slots, rl, e->replan_list[4], e->dist_rank,
+                       e->dist_world, e->dist_world > 1 ? e->owned_list : nullptr, 15 & ~quad_mask, e->replan_list[5], qgrid, nq);
+  if (nq > 0) HIPOK(hipStreamWaitEvent(st, e->quad_ev1, 0));
+  prof_end(e, tok);
+  int qn[4] = {0, 0, 0, 0};
+  HIPOK(hipMemcpyAsync(hm.replan_n, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
+  HIPOK(hipMemcpyAsync(&hm.error, &d.cnt->error, sizeof(int), hipMemcpyDeviceToHost, st));
+  TRY(read_back(e, qn, d.cnt->quad_n, sizeof(int) * 4));
+  if (g_trace_launches) { fprintf(stderr, "[done] replanning pass with the quads\n"); fflush(stderr); }
+  if (hm.error == TS_E_CAPACITY) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
+  const int fb = qn[0], retry = hm.replan_n[4];
+  e->quad_jobs += nq; e->quad_fallbacks += fb;
+  e->quad_last_fb = fb;
+#ifdef TS_QUAD_PROF
+  {
+    long long pf[8];
+    HIPOK(hipMemcpy(pf, d.cnt->prof, sizeof(pf), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[quadprof] wave cycles %lld, in the lockstep loop %lld, wave turns %lld, quad turns %lld: %.0f cycles per turn, %.1f quads per turn\n",
+            pf[0], pf[1], pf[2], pf[3], pf[2] ? (double)pf[1] / (double)pf[2] : 0.0, pf[2] ? (double)pf[3] / (double)pf[2] : 0.0);
+    HIPOK(hipMemset(d.cnt->prof, 0, sizeof(pf)));
+    long long qp[8];
+    HIPOK(hipMemcpy(qp, d.cnt->qprof, sizeof(qp), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[quadprof] per wave turn: pop+loads %.0f, sift LDS %.0f, sift deep %.0f, goal/stale %.0f, eval %.0f, pushes(+skipped) %.0f, tail %.0f, between turns %.0f\n",
+            (double)qp[0] / pf[2], (double)qp[1] / pf[2], (double)qp[2] / pf[2], (double)qp[3] / pf[2], (double)qp[4] / pf[2], (double)qp[5] / pf[2], (double)qp[6] / pf[2], (double)qp[7] / pf[2]);
+    HIPOK(hipMemset(d.cnt->qprof, 0, sizeof(qp)));
+  }
+#endif
+  if (getenv("TS_DEBUG_REPLAN")) {
+    int dbg[8];
+    HIPOK(hipMemcpy(dbg, d.cnt->dbg, sizeof(dbg), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[replan] hand-backs so far by reason: window / g %d, heap %d, expansion budget %d, path buffer %d, policy (step-limited / contraflow search) %d, other %d\n", dbg[1], dbg[2], dbg[3], dbg[4], dbg[5], dbg[6]);
+    fprintf(stderr, "[replan] tick %lld: %d entries to the quads (%d waves of %d), %d to k_replan (%d waves); handed over %d, pool-full %d, %.2f ms\n",
+            (long long)e->C.step_count, nq, qgrid, e->qslots.n_slots / 16, nw, wgrid, fb, retry, now_ms() - tl);
+  }
+  // what k_replan did not get to serve of the hand-backs (it only gives up on them when the two kernels were not run side
+  // by side) and what found the path pool full is queued again
+  const int served = std::min(qn[2], fb);
+  return requeue_in_list0(e, e->replan_list[5] + served, fb - served, retry);
+}
+
+int run_replans(E* e) {   // e->hm->replan_n = the queue as k_decide_main left it
+  Dev& d = e->d;
+  const TsParams& P = e->P;
+  hipStream_t st = e->stream;
+  HostMirror& hm = *e->hm;
+  const RLists rl = replan_lists(e);
+  TRY(ensure_slots(e));
+  if (!e->density_valid) { TRY(ensure_density(e, d.occ_snap)); e->density_valid = true; }
+  TRY(ensure_amap(e));
   // room in the path pool for what these replans will write (a planner that finds the pool full throws its searches
   // away and is run again): 128 words = 2048 path cells per entry, garbage-collecting / growing the pool if need be
   // (TS_DEBUG_POOL_PER_ENTRY shrinks the reservation so that tests can walk the pool-full retry path)
   const char* dbg_per = getenv("TS_DEBUG_POOL_PER_ENTRY");
   const size_t per_entry = dbg_per ? (size_t)atoi(dbg_per) : 128;
-  rc = pool_make_room(e, (size_t)replan_pending(e->hint + 8) * per_entry + (dbg_per ? 64u : (1u << 20)));
-  if (rc) return rc;
-  if (dbg_per) d.pool_cap_words = std::min(e->pool_cap, e->pool_used + (size_t)replan_pending(e->hint + 8) * per_entry + 64u);
+  TRY(pool_make_room(e, (size_t)replan_pending(hm.replan_n) * per_entry + (dbg_per ? 64u : (1u << 20))));
+  if (dbg_per) d.pool_cap_words = std::min(e->pool_cap, e->pool_used + (size_t)replan_pending(hm.replan_n) * per_entry + 64u);
   if (dbg_per && getenv("TS_DEBUG_REPLAN")) fprintf(stderr, "[replan] pool used %zu cap %zu -> logical cap %llu\n", e->pool_used, e->pool_cap, d.pool_cap_words);
   // Order every class list by expected cost (largest first: the longest search of a tick bounds it) and, among equals, in
   // space (Morton order of 32 x 32-cell blocks of the vehicles' positions): the searches that run at the same time then
@@ -77,40 +223,8 @@ int run_replans(E* e) {   // e->hint[8..15] = replan_n as k_decide_main left it
   // private tables for the MALL.  The order of the queue does not touch any result.
   static const bool spatial = !getenv("TS_NO_SPATIAL_QUEUE");
   const bool sharded = e->dist_world > 1;      // (then the order must be total and the same on every rank: 64-bit keys, every list)
-  for (int h = 0; h < 4 && (spatial || sharded); h++) {
-    const int n = e->hint[8 + h];
-    if (n < (sharded ? 2 : 256)) continue;
-    if ((size_t)n > e->cap_sortbuf) {
-      const size_t nc = (size_t)n * 2;
-      rc = regrow(e, &e->sort_keys, 0, nc * 2); if (rc) return rc;          // (room for 64-bit keys)
-      rc = regrow(e, &e->sort_keys_alt, 0, nc * 2); if (rc) return rc;
-      rc = regrow(e, &e->sort_vals_alt, 0, nc); if (rc) return rc;
-      e->cap_sortbuf = nc;
-    }
-    if (sharded) {
-      unsigned long long* k0 = (unsigned long long*)e->sort_keys;
-      unsigned long long* k1 = (unsigned long long*)e->sort_keys_alt;
-      hipLaunchKernelGGL(k_replan_keys64, dim3(nblk(n)), dim3(BLK), 0, st, d, e->replan_list[h], n, k0);
-      size_t tmp_bytes = 0;
-      HIPOK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, k0, k1, n, 0, 32 + REPLAN_KEY_BITS, st));
-      if (tmp_bytes > e->cap_sorttmp) {
-        rc = regrow(e, &e->sort_tmp, 0, tmp_bytes * 2); if (rc) return rc;
-        e->cap_sorttmp = tmp_bytes * 2;
-      }
-      HIPOK(hipcub::DeviceRadixSort::SortKeys(e->sort_tmp, tmp_bytes, k0, k1, n, 0, 32 + REPLAN_KEY_BITS, st));
-      hipLaunchKernelGGL(k_replan_unkey64, dim3(nblk(n)), dim3(BLK), 0, st, k1, n, e->replan_list[h]);
-      continue;
-    }
-    hipLaunchKernelGGL(k_replan_keys, dim3(nblk(n)), dim3(BLK), 0, st, d, e->replan_list[h], n, e->sort_keys);
-    size_t tmp_bytes = 0;
-    HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, e->sort_keys, e->sort_keys_alt, e->replan_list[h], e->sort_vals_alt, n, 0, REPLAN_KEY_BITS, st));
-    if (tmp_bytes > e->cap_sorttmp) {
-      rc = regrow(e, &e->sort_tmp, 0, tmp_bytes * 2); if (rc) return rc;
-      e->cap_sorttmp = tmp_bytes * 2;
-    }
-    HIPOK(hipcub::DeviceRadixSort::SortPairs(e->sort_tmp, tmp_bytes, e->sort_keys, e->sort_keys_alt, e->replan_list[h], e->sort_vals_alt, n, 0, REPLAN_KEY_BITS, st));
-    HIPOK(hipMemcpyAsync(e->replan_list[h], e->sort_vals_alt, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-  }
+  for (int h = 0; h < 4 && (spatial || sharded); h++)
+    if (hm.replan_n[h] >= (sharded ? 2 : 256)) TRY(sort_replan_list(e, h, hm.replan_n[h], sharded));
   // The quad searcher (astar_quad.h; TS_QUAD=0 switches it off): a big
   // queue (a replanning wave of TS_QUAD_MIN entries or more) sends the classes in TS_QUAD_CLASSES to k_replan_quad (sixteen
   // searches per wave, on its own stream) while k_replan runs beside it on the most expensive class and on every vehicle
@@ -122,95 +236,18 @@ int run_replans(E* e) {   // e->hint[8..15] = replan_n as k_decide_main left it
                                              : (int)std::min<long long>(262144, std::max<long long>(16384, 46ll * e->slots.n_slots));
   bool split_done = false;      // (the queue is split between the ranks once; what is queued again - pool-full entries, hand-backs - is this rank's own)
   // (in the sharded multi-GPU mode the threshold applies to this rank's share: every world-th entry of the queue)
-  const bool quad_queue = replan_pending(e->hint + 8) / std::max(e->dist_world, 1) >= std::max(quad_min, 1);
+  const bool quad_queue = replan_pending(hm.replan_n) / std::max(e->dist_world, 1) >= std::max(quad_min, 1);
   // (set up with the first replans of a population that will fill such a queue - its first replanning wave - rather than inside that wave)
   const bool quad_soon = e->n_active / std::max(e->dist_world, 1) >= std::max(quad_min, 1);
-  if (e->quad_on && (quad_queue || quad_soon)) { rc = ensure_qslots(e); if (rc) return rc; }
+  if (e->quad_on && (quad_queue || quad_soon)) TRY(ensure_qslots(e));
   if (e->quad_on && e->qslots_ready && quad_queue) {
-    const int quad_mask = getenv("TS_QUAD_CLASSES") ? atoi(getenv("TS_QUAD_CLASSES")) & 15 : 7;
-    int nq = 0, nw = 0;
-    for (int c = 0; c < 4; c++) { if ((quad_mask >> c) & 1) nq += e->hint[8 + c]; else nw += e->hint[8 + c]; }
-    const double tl = now_ms();
+    TRY(run_quad_pass(e, rl));
     split_done = true;
-    rc = arena_to_quads(e);
-    if (rc) return rc;
-    HIPOK(hipMemsetAsync(d.cnt->quad_n, 0, sizeof(int) * 4, st));
-    int tok = prof_begin(e, PK_REPLAN, nq + nw);
-    int qgrid = 0;
-    if (nq > 0) {
-      HIPOK(hipMemsetAsync(e->replan_list[5], 0xFF, (size_t)nq * 4, st));     // (hand-back entries: -1 = not written yet)
-      HIPOK(hipEventRecord(e->quad_ev0, st));
-      HIPOK(hipStreamWaitEvent(e->quad_stream, e->quad_ev0, 0));
-      qgrid = std::min((nq + 15) / 16, e->qslots.n_slots / 16);
-      if (g_trace_launches) { fprintf(stderr, "[launch] k_replan_quad items=%d grid=%d\n", nq, qgrid); fflush(stderr); }
-      hipLaunchKernelGGL(k_replan_quad, dim3(qgrid), dim3(64), 0, e->quad_stream, d, P, e->qslots, rl, quad_mask, e->replan_list[4],
-                         e->replan_list[5], e->dist_rank, e->dist_world, e->dist_world > 1 ? e->owned_list : nullptr);
-      HIPOK(hipEventRecord(e->quad_ev1, e->quad_stream));
-    }
-    // (k_replan never holds anything the quads wait for: were the two launches ever serialised, it would simply find the
-    // hand-back list complete)
-    // k_replan's waves beside the quads serve the most expensive class and the quads' hand-backs: 512 of them for a wave that hands back
-    // thousands, 384 once the previous wave handed back few (they take issue slots from the quads: measured on the bench workload's four
-    // waves, 5 678 / 2 895 / 1 379 / 2 514 hand-backs: 4.18 / 3.65 / 3.22 / 2.69 s with 512, 4.56 / 3.33 / 2.88 / 2.44 s with 384)
-    const int side_waves = getenv("TS_QUAD_SIDE_WAVES") ? atoi(getenv("TS_QUAD_SIDE_WAVES"))
-                                                        : (e->quad_last_fb < 0 || e->quad_last_fb > 4096 ? 512 : 384);
-    const int wgrid = std::min(e->side_slots, std::max(std::min(nw, e->side_slots), nq > 0 ? side_waves : 1));
-    if (nw > 0 || nq > 0)
-      hipLaunchKernelGGL(k_replan, dim3(wgrid), dim3(64), 0, st, d, P, e->slots, rl, e->replan_list[4], e->dist_rank,
-                         e->dist_world, e->dist_world > 1 ? e->owned_list : nullptr, 15 & ~quad_mask, e->replan_list[5], qgrid, nq);
-    if (nq > 0) HIPOK(hipStreamWaitEvent(st, e->quad_ev1, 0));
-    prof_end(e, tok);
-    int qn[4] = {0, 0, 0, 0};
-    HIPOK(hipMemcpyAsync(e->hint + 8, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
-    HIPOK(hipMemcpyAsync(e->hint + 3, &d.cnt->error, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPOK(hipMemcpyAsync(qn, d.cnt->quad_n, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    if (g_trace_launches) { fprintf(stderr, "[done] replanning pass with the quads\n"); fflush(stderr); }
-    if (e->hint[3] == TS_E_CAPACITY) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
-    const int fb = qn[0], retry = e->hint[8 + 4];
-    e->quad_jobs += nq; e->quad_fallbacks += fb;
-    e->quad_last_fb = fb;
-#ifdef TS_QUAD_PROF
-    {
-      long long pf[8];
-      HIPOK(hipMemcpy(pf, d.cnt->prof, sizeof(pf), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[quadprof] wave cycles %lld, in the lockstep loop %lld, wave turns %lld, quad turns %lld: %.0f cycles per turn, %.1f quads per turn\n",
-              pf[0], pf[1], pf[2], pf[3], pf[2] ? (double)pf[1] / (double)pf[2] : 0.0, pf[2] ? (double)pf[3] / (double)pf[2] : 0.0);
-      HIPOK(hipMemset(d.cnt->prof, 0, sizeof(pf)));
-      long long qp[8];
-      HIPOK(hipMemcpy(qp, d.cnt->qprof, sizeof(qp), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[quadprof] per wave turn: pop+loads %.0f, sift LDS %.0f, sift deep %.0f, goal/stale %.0f, eval %.0f, pushes(+skipped) %.0f, tail %.0f, between turns %.0f\n",
-              (double)qp[0] / pf[2], (double)qp[1] / pf[2], (double)qp[2] / pf[2], (double)qp[3] / pf[2], (double)qp[4] / pf[2], (double)qp[5] / pf[2], (double)qp[6] / pf[2], (double)qp[7] / pf[2]);
-      HIPOK(hipMemset(d.cnt->qprof, 0, sizeof(qp)));
-    }
-#endif
-    if (getenv("TS_DEBUG_REPLAN")) {
-      int dbg[8];
-      HIPOK(hipMemcpy(dbg, d.cnt->dbg, sizeof(dbg), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[replan] hand-backs so far by reason: window / g %d, heap %d, expansion budget %d, path buffer %d, policy (step-limited / contraflow search) %d, other %d\n", dbg[1], dbg[2], dbg[3], dbg[4], dbg[5], dbg[6]);
-    }
-    if (getenv("TS_DEBUG_REPLAN"))
-      fprintf(stderr, "[replan] tick %lld: %d entries to the quads (%d waves of %d), %d to k_replan (%d waves); handed over %d, pool-full %d, %.2f ms\n",
-              (long long)e->C.step_count, nq, qgrid, e->qslots.n_slots / 16, nw, wgrid, fb, retry, now_ms() - tl);
-    // what k_replan did not get to serve of the hand-backs (it only gives up on them when the two kernels were not run side
-    // by side) and what found the path pool full is queued again below
-    const int served = std::min(qn[2], fb), left = fb - served;
-    if (retry > 0) {
-      d.pool_cap_words = e->pool_cap;
-      rc = pool_make_room(e, (size_t)retry * 1024 + (1u << 20));
-      if (rc) return rc;
-    }
-    if (left > 0) HIPOK(hipMemcpyAsync(e->replan_list[0], e->replan_list[5] + served, (size_t)left * 4, hipMemcpyDeviceToDevice, st));
-    if (retry > 0) HIPOK(hipMemcpyAsync(e->replan_list[0] + left, e->replan_list[4], (size_t)retry * 4, hipMemcpyDeviceToDevice, st));
-    const int keep_owned = e->hint[8 + 6];
-    for (int q = 0; q < 8; q++) e->hint[8 + q] = 0;
-    e->hint[8] = left + retry; e->hint[8 + 6] = keep_owned;
-    HIPOK(hipMemcpyAsync(d.cnt->replan_n, e->hint + 8, sizeof(int) * 8, hipMemcpyHostToDevice, st));
   }
-  while (replan_pending(e->hint + 8) > 0) {
-    const int n = replan_pending(e->hint + 8);
+  while (replan_pending(hm.replan_n) > 0) {
+    const int n = replan_pending(hm.replan_n);
     const int grid = std::min(n, e->slots.n_slots);
-    if (grid > e->side_slots && e->quad_on) { rc = arena_to_waves(e); if (rc) return rc; }
+    if (grid > e->side_slots && e->quad_on) TRY(arena_to_waves(e));
     const int w_rank = split_done ? 0 : e->dist_rank, w_world = split_done ? 1 : e->dist_world;
     split_done = true;
 #ifdef TS_TRACE_REPLAN
@@ -226,9 +263,8 @@ int run_replans(E* e) {   // e->hint[8..15] = replan_n as k_decide_main left it
     LAUNCH(e, PK_REPLAN, n, k_replan, dim3(grid), dim3(64), d, P, e->slots, rl, e->replan_list[4], w_rank, w_world,
            e->dist_world > 1 ? e->owned_list : nullptr, 15, (int32_t*)nullptr, 0, 0);
     const double tl = now_ms();
-    HIPOK(hipMemcpyAsync(e->hint + 8, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
-    HIPOK(hipMemcpyAsync(e->hint + 3, &d.cnt->error, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
+    HIPOK(hipMemcpyAsync(hm.replan_n, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
+    TRY(read_back(e, &hm.error, &d.cnt->error, sizeof(int)));
 #ifdef TS_TRACE_REPLAN
     if (n >= 1000) {
       std::vector<int4> h((size_t)std::min(n, tr_cap));
@@ -245,60 +281,47 @@ int run_replans(E* e) {   // e->hint[8..15] = replan_n as k_decide_main left it
       fprintf(stderr, "[replan] deepest heap so far %d, longest search so far %d expansions, %lld expansions so far with part of the heap in HBM\n",
               dbg[4], dbg[5], (long long)(((unsigned long long)(unsigned)dbg[7] << 32) | (unsigned)dbg[6]));
     }
-    if (e->hint[3] == TS_E_CAPACITY) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
-    const int retry = e->hint[8 + 4];
+    if (hm.error == TS_E_CAPACITY) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
+    const int retry = hm.replan_n[4];
     if (getenv("TS_DEBUG_REPLAN"))
       fprintf(stderr, "[replan] tick %lld: %d entries (classes %d/%d/%d/%d) on %d searchers, retry=%d, %.2f ms\n", (long long)e->C.step_count,
-              n, e->hint[8], e->hint[9], e->hint[10], e->hint[11], grid, retry, now_ms() - tl);
+              n, hm.replan_n[0], hm.replan_n[1], hm.replan_n[2], hm.replan_n[3], grid, retry, now_ms() - tl);
     if (retry == 0) break;
     // the path pool filled up: make room (GC, then growth) and run the entries that could not commit again
-    d.pool_cap_words = e->pool_cap;
-    rc = pool_make_room(e, (size_t)retry * 1024 + (1u << 20));
-    if (rc) return rc;
-    HIPOK(hipMemcpyAsync(e->replan_list[0], e->replan_list[4], (size_t)retry * 4, hipMemcpyDeviceToDevice, st));
-    const int keep_owned = e->hint[8 + 6];
-    for (int q = 0; q < 8; q++) e->hint[8 + q] = 0;
-    e->hint[8] = retry; e->hint[8 + 6] = keep_owned;
-    HIPOK(hipMemcpyAsync(d.cnt->replan_n, e->hint + 8, sizeof(int) * 8, hipMemcpyHostToDevice, st));
+    TRY(requeue_in_list0(e, nullptr, 0, retry));
   }
   d.pool_cap_words = e->pool_cap;
   return TS_OK;
 }
 
 // Replicated-state multi-GPU mode: after this rank's share of the replans, trade results with the other ranks.
-// `before` = the device counters as they were when the replanning phase began.
-struct XHeader { int64_t n_recs, n_words, n_arr, error; int64_t delta[16]; double ddelta[2]; };
-// `local_rc` != 0: this rank failed on the host side before the exchange (capacity, a device error): it still joins the
-// collective, with a header that says so, and every rank fails the tick together instead of waiting in the all-gather
-// until the process group times out.
-int exchange_replans(E* e, const DevCnt& before, int local_rc) {
+// The counters a rank's replans move, traded as deltas since the replanning phase began (XHeader::delta / ddelta, in this order)
+constexpr long long DevCnt::*X_LONG[] = {&DevCnt::stuck, &DevCnt::collisions, &DevCnt::malfunctions, &DevCnt::overtaking,
+                                         &DevCnt::in_stuck_detour, &DevCnt::parked, &DevCnt::completed_internal,
+                                         &DevCnt::completed_through, &DevCnt::dist_internal, &DevCnt::dist_through,
+                                         &DevCnt::astar_calls, &DevCnt::astar_exp, &DevCnt::astar_relax};
+constexpr double DevCnt::*X_DOUBLE[] = {&DevCnt::dur_internal, &DevCnt::dur_through};
+// A rank's payload: this header | n_recs records | n_words path words | n_arr service records (12 bytes each)
+struct XHeader {
+  int64_t n_recs, n_words, n_arr, error;   // error: the rank's sticky device error (DevCnt::error)
+  int64_t delta[std::size(X_LONG)];
+  int64_t dec_arrived;                      // DevCnt::dec_arrived after the rank's replans (the ranks keep the largest)
+  int64_t rank_error;                       // != 0: the rank failed before the exchange, with this code, and sent the header alone
+  int64_t unused_;
+  double ddelta[std::size(X_DOUBLE)];
+};
+static_assert(sizeof(XHeader) == 176, "the header's size is part of every payload (exchange_bytes)");
+inline size_t payload_bytes(const XHeader& h) {
+  return sizeof(XHeader) + (size_t)h.n_recs * sizeof(ReplanRec) + (size_t)h.n_words * 4 + (size_t)std::max<int64_t>(h.n_arr, 0) * 12;
+}
+
+// This rank's share of the replans as exchange records and path words (d_recs, d_xwords), and the header that describes them;
+// `after` = the device counters once they were planned
+int export_replans(E* e, const DevCnt& before, XHeader& hd, DevCnt& after) {
   Dev& d = e->d;
   hipStream_t st = e->stream;
-  const double t0 = now_ms();
-  if (local_rc) {
-    XHeader hd;
-    memset(&hd, 0, sizeof(hd));
-    hd.delta[14] = local_rc;
-    e->send_buf.resize(sizeof(hd));
-    memcpy(e->send_buf.data(), &hd, sizeof(hd));
-    void* recv = nullptr;
-    int64_t* sizes = nullptr;
-    int64_t stride = 0;
-    const void* sendp = e->send_buf.data();
-    if (e->dist_dev) {
-      if (e->cap_send < sizeof(hd) && regrow(e, &e->d_send, 0, (size_t)4096) == TS_OK) e->cap_send = 4096;
-      if (e->cap_send >= sizeof(hd) && hipMemcpy(e->d_send, &hd, sizeof(hd), hipMemcpyHostToDevice) == hipSuccess) sendp = e->d_send;
-      else return local_rc;     // (no device memory left even for a header: the other ranks run into their collective's time-out)
-    }
-    (void)e->dist_fn(e->dist_user, sendp, (int64_t)sizeof(hd), &recv, &sizes, &stride);
-    return local_rc;
-  }
-  const int n_owned = e->hint[8 + 6];
-  if ((size_t)std::max(n_owned, 1) > e->cap_recs) {
-    const size_t nc = (size_t)n_owned * 2 + 1024;
-    int rc = regrow(e, &e->d_recs, 0, nc); if (rc) return rc;
-    e->cap_recs = nc;
-  }
+  const int n_owned = e->hm->replan_n[6];
+  TRY(grow(e, &e->d_recs, e->cap_recs, (size_t)std::max(n_owned, 1), (size_t)n_owned * 2 + 1024));
   if (!e->d_xwords_n) HIPOK(dalloc(e, &e->d_xwords_n, 1));
   // the words this rank's replans rewrote, counted first (the pool's growth over the phase is no bound: pool_make_room may
   // have garbage-collected inside it), then exported into a buffer that holds them
@@ -307,166 +330,124 @@ int exchange_replans(E* e, const DevCnt& before, int local_rc) {
   if (n_owned > 0)
     hipLaunchKernelGGL(k_replan_export, dim3(nblk(n_owned)), dim3(BLK), 0, st, d, e->owned_list, n_owned, e->d_recs, e->d_xwords, e->d_xwords_n, 1);
   unsigned long long need_words = 0;
-  HIPOK(hipMemcpyAsync(&need_words, e->d_xwords_n, sizeof(need_words), hipMemcpyDeviceToHost, st));
-  HIPOK(hipStreamSynchronize(st));
-  const DevCnt after = *e->hcnt;
-  if ((size_t)need_words + 16 > e->cap_xwords) {
-    const size_t nc = (size_t)need_words * 2 + 4096;
-    int rc = regrow(e, &e->d_xwords, 0, nc); if (rc) return rc;
-    e->cap_xwords = nc;
-  }
+  TRY(read_back(e, &need_words, e->d_xwords_n, sizeof(need_words)));
+  after = *e->hcnt;
+  TRY(grow(e, &e->d_xwords, e->cap_xwords, (size_t)need_words + 16, (size_t)need_words * 2 + 4096));
   HIPOK(hipMemsetAsync(e->d_xwords_n, 0, sizeof(unsigned long long), st));
   if (n_owned > 0)
     hipLaunchKernelGGL(k_replan_export, dim3(nblk(n_owned)), dim3(BLK), 0, st, d, e->owned_list, n_owned, e->d_recs, e->d_xwords, e->d_xwords_n, 0);
   unsigned long long n_words = 0;
-  HIPOK(hipMemcpyAsync(&n_words, e->d_xwords_n, sizeof(n_words), hipMemcpyDeviceToHost, st));
-  HIPOK(hipStreamSynchronize(st));
+  TRY(read_back(e, &n_words, e->d_xwords_n, sizeof(n_words)));
   if (n_words != need_words) return fail(e, TS_E_DEVICE, "replan export wrote a different number of words than it counted (internal error)");
-  const int n_arr = after.arr_n - before.arr_n;
+  hd.n_recs = n_owned; hd.n_words = (int64_t)n_words; hd.n_arr = after.arr_n - before.arr_n; hd.error = after.error;
+  for (size_t q = 0; q < std::size(X_LONG); q++) hd.delta[q] = after.*X_LONG[q] - before.*X_LONG[q];
+  for (size_t q = 0; q < std::size(X_DOUBLE); q++) hd.ddelta[q] = after.*X_DOUBLE[q] - before.*X_DOUBLE[q];
+  hd.dec_arrived = after.dec_arrived;
+  return TS_OK;
+}
+
+// Pack a payload where the exchange callback reads it: into the device send buffer (device-direct: gathered between device
+// buffers) or into send_buf (host-staged).  The service records are d.arr[arr_from, arr_from + n_arr).
+int stage_payload(E* e, const XHeader& hd, int arr_from, const void** sendp) {
+  const bool dev = e->dist_dev;
+  const size_t bytes = payload_bytes(hd), rec_b = (size_t)hd.n_recs * sizeof(ReplanRec), word_b = (size_t)hd.n_words * 4;
+  if (dev) TRY(grow(e, &e->d_send, e->cap_send, bytes, bytes * 2 + 4096));
+  if (!dev) e->send_buf.resize(bytes);
+  uint8_t* p = dev ? e->d_send : e->send_buf.data();
+  *sendp = p;
+  if (dev) HIPOK(hipMemcpyAsync(p, &hd, sizeof(hd), hipMemcpyHostToDevice, e->stream));
+  else memcpy(p, &hd, sizeof(hd));
+  p += sizeof(hd);
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (rec_b > 0) HIPOK(hipMemcpyAsync(p, e->d_recs, rec_b, kind, e->stream));
+  if (word_b > 0) HIPOK(hipMemcpyAsync(p + rec_b, e->d_xwords, word_b, kind, e->stream));
+  if (hd.n_arr > 0) HIPOK(hipMemcpyAsync(p + rec_b + word_b, e->d.arr + 3 * (size_t)arr_from, (size_t)hd.n_arr * 12, kind, e->stream));
+  if (dev || bytes > sizeof(hd)) HIPOK(hipStreamSynchronize(e->stream));
+  return TS_OK;
+}
+
+// `before` = the device counters as they were when the replanning phase began.  `local_rc` != 0: this rank failed on the host
+// side before the exchange (capacity, a device error).  It still joins the collective, with a header that says so, and every
+// rank fails the tick together instead of waiting in the all-gather until the process group times out; so does every failure
+// here before the collective.  A failure after the gather (pool_make_room for the others' words, an import) leaves this rank
+// part-way through the others' results and out of step with them: it is fatal for the whole group.
+int exchange_replans(E* e, const DevCnt& before, int local_rc) {
+  Dev& d = e->d;
+  hipStream_t st = e->stream;
+  const double t0 = now_ms();
   XHeader hd;
   memset(&hd, 0, sizeof(hd));
-  hd.n_recs = n_owned; hd.n_words = (int64_t)n_words; hd.n_arr = n_arr; hd.error = after.error;
-  const long long dl[] = {after.stuck - before.stuck, after.collisions - before.collisions, after.malfunctions - before.malfunctions,
-                          after.overtaking - before.overtaking, after.in_stuck_detour - before.in_stuck_detour, after.parked - before.parked,
-                          after.completed_internal - before.completed_internal, after.completed_through - before.completed_through,
-                          after.dist_internal - before.dist_internal, after.dist_through - before.dist_through,
-                          after.astar_calls - before.astar_calls, after.astar_exp - before.astar_exp, after.astar_relax - before.astar_relax};
-  for (size_t q = 0; q < sizeof(dl) / sizeof(dl[0]); q++) hd.delta[q] = dl[q];
-  hd.delta[13] = after.dec_arrived;
-  hd.ddelta[0] = after.dur_internal - before.dur_internal; hd.ddelta[1] = after.dur_through - before.dur_through;
-  const size_t bytes = sizeof(XHeader) + (size_t)n_owned * sizeof(ReplanRec) + (size_t)n_words * 4 + (size_t)std::max(n_arr, 0) * 12;
-  if (e->dist_dev) {
-    // ---- device-direct exchange: header | records | words | service records packed in device memory, gathered by the
-    // callback between device buffers, imported straight out of the gathered slots
-    if (bytes > e->cap_send) {
-      const size_t nc = bytes * 2 + 4096;
-      int rc = regrow(e, &e->d_send, 0, nc); if (rc) return rc;
-      e->cap_send = nc;
-    }
-    uint8_t* p = e->d_send;
-    HIPOK(hipMemcpyAsync(p, &hd, sizeof(hd), hipMemcpyHostToDevice, st)); p += sizeof(hd);
-    if (n_owned > 0) HIPOK(hipMemcpyAsync(p, e->d_recs, (size_t)n_owned * sizeof(ReplanRec), hipMemcpyDeviceToDevice, st));
-    p += (size_t)n_owned * sizeof(ReplanRec);
-    if (n_words > 0) HIPOK(hipMemcpyAsync(p, e->d_xwords, (size_t)n_words * 4, hipMemcpyDeviceToDevice, st));
-    p += (size_t)n_words * 4;
-    if (n_arr > 0) HIPOK(hipMemcpyAsync(p, d.arr + 3 * (size_t)before.arr_n, (size_t)n_arr * 12, hipMemcpyDeviceToDevice, st));
-    HIPOK(hipStreamSynchronize(st));
-    void* recv = nullptr;
-    int64_t* sizes = nullptr;
-    int64_t stride = 0;
-    const int xrc = e->dist_fn(e->dist_user, e->d_send, (int64_t)bytes, &recv, &sizes, &stride);
-    if (xrc != 0 || !recv || !sizes) return fail(e, TS_E_DEVICE, "the replan exchange callback failed");
-    std::vector<XHeader> hs((size_t)e->dist_world);
-    for (int r = 0; r < e->dist_world; r++) {
-      if (r == e->dist_rank) continue;
-      if ((size_t)sizes[r] < sizeof(XHeader)) return fail(e, TS_E_DEVICE, "short replan exchange buffer");
-      HIPOK(hipMemcpyAsync(&hs[r], (const uint8_t*)recv + (size_t)r * (size_t)stride, sizeof(XHeader), hipMemcpyDeviceToHost, st));
-    }
-    HIPOK(hipStreamSynchronize(st));
-    DevCnt merged = after;
-    long long in_words = 0, in_arr = 0;
-    for (int r = 0; r < e->dist_world; r++) {
-      if (r == e->dist_rank) continue;
-      const XHeader& h2 = hs[r];
-      if (h2.delta[14]) return fail(e, (int)h2.delta[14], "rank " + std::to_string(r) + " failed in its share of the replans (error " + std::to_string((long long)h2.delta[14]) + ")");
-      in_words += h2.n_words; in_arr += h2.n_arr;
-      if ((size_t)sizes[r] != sizeof(XHeader) + (size_t)h2.n_recs * sizeof(ReplanRec) + (size_t)h2.n_words * 4 + (size_t)h2.n_arr * 12)
-        return fail(e, TS_E_DEVICE, "replan exchange buffer size mismatch");
-    }
-    if (in_words > 0) { int rc = pool_make_room(e, (size_t)in_words + 64); if (rc) return rc; }
-    if (in_arr > 0 && (long long)after.arr_n + in_arr > d.arr_cap) return fail(e, TS_E_CAPACITY, "more service records in one tick than the record buffer holds");
-    e->exchange_bytes += (long long)bytes;
-    int arr_at = after.arr_n;
-    for (int r = 0; r < e->dist_world; r++) {
-      if (r == e->dist_rank) continue;
-      const XHeader& h2 = hs[r];
-      const uint8_t* q = (const uint8_t*)recv + (size_t)r * (size_t)stride + sizeof(XHeader);
-      merged.stuck += h2.delta[0]; merged.collisions += h2.delta[1]; merged.malfunctions += h2.delta[2]; merged.overtaking += h2.delta[3];
-      merged.in_stuck_detour += h2.delta[4]; merged.parked += h2.delta[5]; merged.completed_internal += h2.delta[6];
-      merged.completed_through += h2.delta[7]; merged.dist_internal += h2.delta[8]; merged.dist_through += h2.delta[9];
-      merged.astar_calls += h2.delta[10]; merged.astar_exp += h2.delta[11]; merged.astar_relax += h2.delta[12];
-      merged.dur_internal += h2.ddelta[0]; merged.dur_through += h2.ddelta[1];
-      if (h2.error && !merged.error) merged.error = (int)h2.error;
-      if ((int)h2.delta[13] > merged.dec_arrived) merged.dec_arrived = (int)h2.delta[13];
-      if (h2.n_recs > 0)
-        hipLaunchKernelGGL(k_replan_import, dim3(nblk((long long)h2.n_recs)), dim3(BLK), 0, st, d, (const ReplanRec*)q, (int)h2.n_recs,
-                           (const uint32_t*)(q + (size_t)h2.n_recs * sizeof(ReplanRec)));
-      if (h2.n_arr > 0) {
-        HIPOK(hipMemcpyAsync(d.arr + 3 * (size_t)arr_at, q + (size_t)h2.n_recs * sizeof(ReplanRec) + (size_t)h2.n_words * 4, (size_t)h2.n_arr * 12, hipMemcpyDeviceToDevice, st));
-        arr_at += (int)h2.n_arr;
-      }
-    }
-    unsigned long long pool_now = 0;
-    HIPOK(hipMemcpyAsync(&pool_now, &d.cnt->pool_used, sizeof(pool_now), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));     // (the gathered slots are the callee's again after this tick's imports)
-    merged.pool_used = pool_now; merged.arr_n = arr_at;
-    *e->hcnt = merged;
-    HIPOK(hipMemcpyAsync(d.cnt, e->hcnt, sizeof(DevCnt), hipMemcpyHostToDevice, st));
-    HIPOK(hipStreamSynchronize(st));
-    e->exchange_ms += now_ms() - t0;
-    return TS_OK;
+  DevCnt after = before;
+  const void* sendp = nullptr;
+  if (!local_rc) local_rc = export_replans(e, before, hd, after);
+  if (!local_rc) local_rc = stage_payload(e, hd, before.arr_n, &sendp);
+  if (local_rc) {
+    memset(&hd, 0, sizeof(hd));
+    hd.rank_error = local_rc;
+    const std::string why = e->err;
+    const int staged = stage_payload(e, hd, 0, &sendp);
+    e->err = why;
+    if (staged != TS_OK) return local_rc;   // (no device memory left even for a header: the other ranks run into their collective's time-out)
   }
-  e->send_buf.resize(bytes);
-  uint8_t* p = e->send_buf.data();
-  memcpy(p, &hd, sizeof(hd)); p += sizeof(hd);
-  if (n_owned > 0) HIPOK(hipMemcpyAsync(p, e->d_recs, (size_t)n_owned * sizeof(ReplanRec), hipMemcpyDeviceToHost, st));
-  p += (size_t)n_owned * sizeof(ReplanRec);
-  if (n_words > 0) HIPOK(hipMemcpyAsync(p, e->d_xwords, (size_t)n_words * 4, hipMemcpyDeviceToHost, st));
-  p += (size_t)n_words * 4;
-  if (n_arr > 0) HIPOK(hipMemcpyAsync(p, d.arr + 3 * (size_t)before.arr_n, (size_t)n_arr * 12, hipMemcpyDeviceToHost, st));
-  HIPOK(hipStreamSynchronize(st));
+  const int64_t bytes = (int64_t)payload_bytes(hd);
   void* recv = nullptr;
   int64_t* sizes = nullptr;
   int64_t stride = 0;
-  const int xrc = e->dist_fn(e->dist_user, e->send_buf.data(), (int64_t)bytes, &recv, &sizes, &stride);
+  const int xrc = e->dist_fn(e->dist_user, sendp, bytes, &recv, &sizes, &stride);
+  if (local_rc) return local_rc;
   if (xrc != 0 || !recv || !sizes) return fail(e, TS_E_DEVICE, "the replan exchange callback failed");
-  // apply the other ranks' results; counters through the host copy
+  // the other ranks' headers (in the gathered device slots, or the gathered host buffer), checked, and their counters merged
+  // into this rank's: the device copy moves on only in pool_used (imports), everything else is after + the others' deltas
+  auto slot = [&](int r) { return (const uint8_t*)recv + (size_t)r * (size_t)stride; };
+  std::vector<XHeader> hs((size_t)e->dist_world);
+  for (int r = 0; r < e->dist_world; r++) {
+    if (r == e->dist_rank) continue;
+    if ((size_t)sizes[r] < sizeof(XHeader)) return fail(e, TS_E_DEVICE, "short replan exchange buffer");
+    if (e->dist_dev) HIPOK(hipMemcpyAsync(&hs[r], slot(r), sizeof(XHeader), hipMemcpyDeviceToHost, st));
+    else memcpy(&hs[r], slot(r), sizeof(XHeader));
+  }
+  if (e->dist_dev) HIPOK(hipStreamSynchronize(st));
   DevCnt merged = after;
   long long in_words = 0, in_arr = 0;
   for (int r = 0; r < e->dist_world; r++) {
     if (r == e->dist_rank) continue;
-    const uint8_t* q = (const uint8_t*)recv + (size_t)r * (size_t)stride;
-    if ((size_t)sizes[r] < sizeof(XHeader)) return fail(e, TS_E_DEVICE, "short replan exchange buffer");
-    XHeader h2;
-    memcpy(&h2, q, sizeof(h2));
-    if (h2.delta[14]) return fail(e, (int)h2.delta[14], "rank " + std::to_string(r) + " failed in its share of the replans (error " + std::to_string((long long)h2.delta[14]) + ")");
-    in_words += h2.n_words; in_arr += h2.n_arr;
-    if ((size_t)sizes[r] != sizeof(XHeader) + (size_t)h2.n_recs * sizeof(ReplanRec) + (size_t)h2.n_words * 4 + (size_t)h2.n_arr * 12)
-      return fail(e, TS_E_DEVICE, "replan exchange buffer size mismatch");
+    const XHeader& h = hs[r];
+    if (h.rank_error) return fail(e, (int)h.rank_error, "rank " + std::to_string(r) + " failed in its share of the replans (error " + std::to_string((long long)h.rank_error) + ")");
+    if ((size_t)sizes[r] != payload_bytes(h)) return fail(e, TS_E_DEVICE, "replan exchange buffer size mismatch");
+    in_words += h.n_words; in_arr += h.n_arr;
+    for (size_t q = 0; q < std::size(X_LONG); q++) merged.*X_LONG[q] += h.delta[q];
+    for (size_t q = 0; q < std::size(X_DOUBLE); q++) merged.*X_DOUBLE[q] += h.ddelta[q];
+    if (h.error && !merged.error) merged.error = (int)h.error;
+    if ((int)h.dec_arrived > merged.dec_arrived) merged.dec_arrived = (int)h.dec_arrived;
   }
-  if (in_words > 0) { int rc = pool_make_room(e, (size_t)in_words + 64); if (rc) return rc; }
+  if (in_words > 0) TRY(pool_make_room(e, (size_t)in_words + 64));
   if (in_arr > 0 && (long long)after.arr_n + in_arr > d.arr_cap) return fail(e, TS_E_CAPACITY, "more service records in one tick than the record buffer holds");
-  e->exchange_bytes += (long long)bytes;
+  e->exchange_bytes += bytes;
   int arr_at = after.arr_n;
   for (int r = 0; r < e->dist_world; r++) {
     if (r == e->dist_rank) continue;
-    const uint8_t* q = (const uint8_t*)recv + (size_t)r * (size_t)stride;
-    XHeader h2;
-    memcpy(&h2, q, sizeof(h2)); q += sizeof(h2);
-    merged.stuck += h2.delta[0]; merged.collisions += h2.delta[1]; merged.malfunctions += h2.delta[2]; merged.overtaking += h2.delta[3];
-    merged.in_stuck_detour += h2.delta[4]; merged.parked += h2.delta[5]; merged.completed_internal += h2.delta[6];
-    merged.completed_through += h2.delta[7]; merged.dist_internal += h2.delta[8]; merged.dist_through += h2.delta[9];
-    merged.astar_calls += h2.delta[10]; merged.astar_exp += h2.delta[11]; merged.astar_relax += h2.delta[12];
-    merged.dur_internal += h2.ddelta[0]; merged.dur_through += h2.ddelta[1];
-    if (h2.error && !merged.error) merged.error = (int)h2.error;
-    if ((int)h2.delta[13] > merged.dec_arrived) merged.dec_arrived = (int)h2.delta[13];
-    if (h2.n_recs > 0) {
-      if ((size_t)h2.n_recs > e->cap_recs) { const size_t nc = (size_t)h2.n_recs * 2; int rc = regrow(e, &e->d_recs, 0, nc); if (rc) return rc; e->cap_recs = nc; }
-      if ((size_t)h2.n_words + 16 > e->cap_xwords) { const size_t nc = (size_t)h2.n_words * 2 + 4096; int rc = regrow(e, &e->d_xwords, 0, nc); if (rc) return rc; e->cap_xwords = nc; }
-      HIPOK(hipMemcpyAsync(e->d_recs, q, (size_t)h2.n_recs * sizeof(ReplanRec), hipMemcpyHostToDevice, st));
-      if (h2.n_words > 0) HIPOK(hipMemcpyAsync(e->d_xwords, q + (size_t)h2.n_recs * sizeof(ReplanRec), (size_t)h2.n_words * 4, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_replan_import, dim3(nblk((long long)h2.n_recs)), dim3(BLK), 0, st, d, e->d_recs, (int)h2.n_recs, e->d_xwords);
+    const XHeader& h = hs[r];
+    const uint8_t* recs = slot(r) + sizeof(XHeader);
+    const uint8_t* words = recs + (size_t)h.n_recs * sizeof(ReplanRec);
+    if (h.n_recs > 0 && e->dist_dev) {   // imported straight out of the gathered slot
+      hipLaunchKernelGGL(k_replan_import, dim3(nblk((long long)h.n_recs)), dim3(BLK), 0, st, d, (const ReplanRec*)recs, (int)h.n_recs,
+                         (const uint32_t*)words);
+    } else if (h.n_recs > 0) {           // staged through d_recs / d_xwords
+      TRY(grow(e, &e->d_recs, e->cap_recs, (size_t)h.n_recs, (size_t)h.n_recs * 2));
+      TRY(grow(e, &e->d_xwords, e->cap_xwords, (size_t)h.n_words + 16, (size_t)h.n_words * 2 + 4096));
+      HIPOK(hipMemcpyAsync(e->d_recs, recs, (size_t)h.n_recs * sizeof(ReplanRec), hipMemcpyHostToDevice, st));
+      if (h.n_words > 0) HIPOK(hipMemcpyAsync(e->d_xwords, words, (size_t)h.n_words * 4, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_replan_import, dim3(nblk((long long)h.n_recs)), dim3(BLK), 0, st, d, e->d_recs, (int)h.n_recs, e->d_xwords);
       HIPOK(hipStreamSynchronize(st));   // (the staging buffers are reused for the next rank)
     }
-    if (h2.n_arr > 0) {
-      HIPOK(hipMemcpyAsync(d.arr + 3 * (size_t)arr_at, q + (size_t)h2.n_recs * sizeof(ReplanRec) + (size_t)h2.n_words * 4, (size_t)h2.n_arr * 12, hipMemcpyHostToDevice, st));
-      arr_at += (int)h2.n_arr;
+    if (h.n_arr > 0) {
+      HIPOK(hipMemcpyAsync(d.arr + 3 * (size_t)arr_at, words + (size_t)h.n_words * 4, (size_t)h.n_arr * 12,
+                           e->dist_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+      arr_at += (int)h.n_arr;
     }
   }
-  // counters: the device copy moved on only in pool_used (imports); everything else is after + the others' deltas
   unsigned long long pool_now = 0;
-  HIPOK(hipMemcpyAsync(&pool_now, &d.cnt->pool_used, sizeof(pool_now), hipMemcpyDeviceToHost, st));
-  HIPOK(hipStreamSynchronize(st));
+  TRY(read_back(e, &pool_now, &d.cnt->pool_used, sizeof(pool_now)));     // (device-direct: the gathered slots are the callee's again after this tick's imports)
   merged.pool_used = pool_now; merged.arr_n = arr_at;
   *e->hcnt = merged;
   HIPOK(hipMemcpyAsync(d.cnt, e->hcnt, sizeof(DevCnt), hipMemcpyHostToDevice, st));
@@ -497,40 +478,628 @@ int words_upload(E* e, uint64_t upto) {
   return TS_OK;
 }
 
+// random() < c  <=>  the 53-bit integer (a << 26 | b) < ceil(c * 2^53)   (exact: power-of-two scaling)
+inline unsigned long long thr53(double c) {
+  if (!(c > 0.0)) return 0;
+  if (c >= 1.0) return 1ull << 53;
+  return (unsigned long long)std::ceil(std::ldexp(c, 53));
+}
+// the speed roll: getrandbits(span.bit_length()) = a word >> rshift, until it is below span
+struct Roll { uint32_t span; int rshift; };
+inline Roll roll_of(const TsParams& P) {
+  const uint32_t span = (uint32_t)(P.vehicle_max_speed - P.vehicle_min_speed + 1);
+  return Roll{span, __builtin_clz(span)};
+}
+
+// Pass 1 (device) of the vehicles [start, start + n): fixed-word prefix sums, roll ranks, roll start offsets
+int rng_pass1(E* e, int start, int n) {
+  Dev& d = e->d;
+  hipStream_t st = e->stream;
+  const int nb = nblk(n, BLK * RS_ITEMS);
+  HIPOK(hipMemsetAsync(&d.cnt->rng_event, 0xFF, sizeof(unsigned int), st));
+  int tok = prof_begin(e, PK_RNG, n);
+  hipLaunchKernelGGL(k_rng_blocksum, dim3(nb), dim3(BLK), 0, st, d.F, start, n, e->rng_blocks);
+  hipLaunchKernelGGL(k_rng_scanblocks, dim3(1), dim3(1024), 0, st, e->rng_blocks, nb, d.cnt->rng_tot);
+  hipLaunchKernelGGL(k_rng_final, dim3(nb), dim3(BLK), 0, st, d, start, n, e->rng_blocks);
+  prof_end(e, tok);
+  return TS_OK;
+}
+
+// The take table for the stretch of the stream a pass that starts at `base` will most likely walk: the one built ahead of
+// time covers [take_base, take_base + take_n) (`*toff` = where this pass starts in it); otherwise one is built now, from the
+// estimate of the last pass (positions beyond it fall back to the accept bitmask on the host), valid once the stream syncs
+int take_table(E* e, Roll rl, uint64_t base, size_t* n_take, size_t* toff) {
+  hipStream_t st = e->stream;
+  if (e->take_n > 0 && base >= e->take_base && base - e->take_base + 4096 < e->take_n) {
+    *toff = (size_t)(base - e->take_base);
+    *n_take = e->take_n - *toff;
+    HIPOK(hipEventSynchronize(e->take_ev));
+    return TS_OK;
+  }
+  size_t nt = (size_t)std::min<uint64_t>(e->cap_take, e->take_guess);
+  if (e->words_uploaded < base + nt + 64) nt = e->words_uploaded > base + 64 ? (size_t)(e->words_uploaded - base - 64) : 0;
+  if (nt > 0) {
+    HIPOK(hipStreamWaitEvent(st, e->words_ev, 0));
+    if (e->take_ev_recorded) HIPOK(hipEventSynchronize(e->take_ev));   // the table built ahead still owns d_take / h_take
+    hipLaunchKernelGGL(k_rng_take, dim3(nblk((long long)nt)), dim3(BLK), 0, st, e->d.words, (unsigned long long)base,
+                       (int)nt, rl.span, rl.rshift, e->d_take);
+    HIPOK(hipMemcpyAsync(e->h_take, e->d_take, nt, hipMemcpyDeviceToHost, st));
+  }
+  e->take_base = base; e->take_n = nt;
+  *toff = 0; *n_take = nt;
+  return TS_OK;
+}
+
+// Pass 2 (host): pass 1's totals and roll start offsets read back, then the serial chain over the speed rolls.  Roll k starts
+// at base + rollD[k] + (words taken by the rolls before it); the producer thread tabulated how many words a roll takes from any
+// position.  Fills h_Tcum[0..*cnt]; *taken = the words the pass takes (fixed words and rolls).
+int roll_chain(E* e, Roll rl, uint64_t base, const uint8_t* take_tab, size_t n_take, int n, int* cnt_out, uint64_t* taken) {
+  Dev& d = e->d;
+  const int guess = std::min(n, e->roll_guess);
+  HIPOK(hipMemcpyAsync(e->hm->rng_tot, d.cnt->rng_tot, sizeof(unsigned int) * 2, hipMemcpyDeviceToHost, e->stream));
+  if (guess > 0) HIPOK(hipMemcpyAsync(e->h_rollD, d.rollD, (size_t)guess * 4, hipMemcpyDeviceToHost, e->stream));
+  const double t_w1 = now_ms();
+  HIPOK(hipStreamSynchronize(e->stream));
+  host_prof(e, PH_WAIT1, now_ms() - t_w1, n);
+  const uint32_t Ctot = e->hm->rng_tot[0];
+  const int cnt = (int)e->hm->rng_tot[1];
+  if (cnt > guess) TRY(read_back(e, e->h_rollD + guess, d.rollD + guess, (size_t)(cnt - guess) * 4));
+  e->roll_guess = cnt + cnt / 8 + 1024;
+  const double t_scan0 = now_ms();
+  MTPipe& r = e->rng_global;
+  const uint32_t span = rl.span;
+  const int rshift = rl.rshift;
+  uint32_t* Tcum = e->h_Tcum;
+  const uint32_t* rollD = e->h_rollD;
+  Tcum[0] = 0;
+  uint64_t T = 0, ensured = 0;
+  int k0 = 0;
+  {
+    // fast path while the walk stays inside the device-built table: nothing but the dependent chain
+    // T -> address -> byte load -> T (32-bit arithmetic, four rolls per trip)
+    uint32_t T32 = 0;
+    const uint32_t lim = (uint32_t)std::min<size_t>(n_take, 0x7FFFFFFFu);
+    int k = 0;
+    for (; k + 4 <= cnt; k += 4) {
+      const uint32_t r0 = rollD[k], r1 = rollD[k + 1], r2 = rollD[k + 2], r3 = rollD[k + 3];
+      if ((uint64_t)r3 + T32 + 256 >= lim) break;
+      const uint32_t t0 = take_tab[r0 + T32]; const uint32_t a0 = T32 + t0;
+      const uint32_t t1 = take_tab[r1 + a0]; const uint32_t a1 = a0 + t1;
+      const uint32_t t2 = take_tab[r2 + a1]; const uint32_t a2 = a1 + t2;
+      const uint32_t t3 = take_tab[r3 + a2]; const uint32_t a3 = a2 + t3;
+      if (__builtin_expect((t0 == 0) | (t1 == 0) | (t2 == 0) | (t3 == 0), 0)) break;   // a run the table does not record
+      Tcum[k + 1] = a0; Tcum[k + 2] = a1; Tcum[k + 3] = a2; Tcum[k + 4] = a3;
+      T32 = a3;
+    }
+    k0 = k; T = T32;
+  }
+  for (int k = k0; k < cnt; k++) {
+    const uint64_t pos = base + rollD[k] + T;
+    if (__builtin_expect(pos + 8 >= ensured, 0)) {
+      const uint64_t want = (pos - r.pos()) + (1u << 18);
+      r.need(want + 1248);
+      ensured = pos + (1u << 18) - 64;
+    }
+    const uint64_t rel = pos - base;
+    uint32_t t = rel < n_take ? take_tab[rel] : r.take(pos);
+    if (__builtin_expect(t == 0, 0)) {  // run longer than the table records: count it here
+      uint64_t q = pos;
+      for (;;) {
+        r.need((q - r.pos()) + 8);
+        if ((r.at(q++) >> rshift) < span) break;
+      }
+      t = (uint32_t)(q - pos);
+    }
+    T += t;
+    Tcum[k + 1] = (uint32_t)T;
+  }
+  host_prof(e, PH_SCAN, now_ms() - t_scan0, n);
+  *cnt_out = cnt;
+  *taken = Ctot + T;
+  return TS_OK;
+}
+
+// Rare: a malfunction / sideswipe fired at the vehicle `evk` names (index * 2 + is_collision).  Everything before it stands;
+// apply the event, move the stream to just behind its draws and re-derive the draw bytes of the suffix, which the next pass
+// starts at (*start)
+int draw_event(E* e, unsigned int evk, uint64_t base, int hi, int* start) {
+  Dev& d = e->d;
+  const TsParams& P = e->P;
+  hipStream_t st = e->stream;
+  HostMirror& hm = *e->hm;
+  e->C.rng_fixups++;
+  const int ev_at = (int)(evk >> 1), ev_coll = (int)(evk & 1u);
+  uint32_t cx = 0, rr = 0;
+  uint8_t fbyte = 0;
+  HIPOK(hipMemcpyAsync(&hm.ev_vid, d.active + ev_at, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPOK(hipMemcpyAsync(&hm.ev_partner, d.cand + ev_at, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPOK(hipMemcpyAsync(&cx, d.Cx + ev_at, 4, hipMemcpyDeviceToHost, st));
+  HIPOK(hipMemcpyAsync(&rr, d.rollrank + ev_at, 4, hipMemcpyDeviceToHost, st));
+  TRY(read_back(e, &fbyte, d.F + ev_at, 1));
+  const uint64_t after = base + cx + e->h_Tcum[rr] + (ev_coll ? ((fbyte & F_DRAW_MALF) ? 4u : 2u) : 2u);
+  e->rng_global.advance_to(after);
+  LAUNCH(e, PK_EVENT, 1, k_apply_event, dim3(1), dim3(64), d, P, hm.ev_vid, ev_coll, hm.ev_partner, ev_at);
+  *start = ev_at + 1;
+  if (*start < hi) LAUNCH(e, PK_DECIDE_PRE, hi - *start, k_decide_pre, dim3(nblk(hi - *start)), dim3(BLK), d, P, *start, hi);
+  return TS_OK;
+}
+
+// Prefetch the part of the stream the next tick will most likely read (at most one pass' worth - the ring holds
+// MAX_AHEAD_BLOCKS blocks; populations above SEG vehicles decide in passes) ...
+int prefetch_next_tick(E* e, Roll rl, int nA) {
+  MTPipe& r = e->rng_global;
+  { const double t_wu = now_ms();
+    const uint64_t ahead = std::min<uint64_t>((uint64_t)std::min(nA, SEG_VEHICLES) * 4 + (1u << 16), MTPipe::MAX_AHEAD_BLOCKS * 600ull - (1u << 16));
+    TRY(words_upload(e, r.pos() + ahead));
+    host_prof(e, PH_WORDS, now_ms() - t_wu, nA); }
+  // ... and build the next tick's take table behind that upload, on the copy stream: kernel and download
+  // overlap the move phase instead of sitting in front of the next host chain
+  const uint64_t nb = r.pos();
+  size_t nt = (size_t)std::min<uint64_t>(e->cap_take, e->take_guess);
+  if (e->words_uploaded < nb + nt + 64) nt = e->words_uploaded > nb + 64 ? (size_t)(e->words_uploaded - nb - 64) : 0;
+  e->take_n = 0;
+  static const bool ahead = !getenv("TS_NO_TAKE_AHEAD");
+  if (nt > 0 && ahead) {
+    hipLaunchKernelGGL(k_rng_take, dim3(nblk((long long)nt)), dim3(BLK), 0, e->copy_stream, e->d.words, (unsigned long long)nb,
+                       (int)nt, rl.span, rl.rshift, e->d_take);
+    HIPOK(hipMemcpyAsync(e->h_take, e->d_take, nt, hipMemcpyDeviceToHost, e->copy_stream));
+    HIPOK(hipEventRecord(e->take_ev, e->copy_stream));
+    e->take_ev_recorded = true;
+    e->take_base = nb; e->take_n = nt;
+  }
+  return TS_OK;
+}
+
+// The searches the decide phase queued: sharded, this rank's share and the exchange; all of them otherwise
+int dispatch_replans(E* e) {
+  const int n_all = replan_pending(e->hm->replan_n);
+  if (e->dist_world <= 1) return n_all > 0 ? run_replans(e) : TS_OK;
+  // every rank sees the same work lists (as sets): plan this rank's share, then trade results - also when this
+  // rank has nothing to plan, the exchange is collective
+  TRY(read_back(e, e->hcnt, e->d.cnt, sizeof(DevCnt)));
+  const DevCnt before = *e->hcnt;
+  int rc_local = grow(e, &e->owned_list, e->cap_owned, (size_t)n_all, (size_t)n_all * 2 + 1024);
+  if (!rc_local && n_all > 0) rc_local = run_replans(e);
+  return exchange_replans(e, before, rc_local);
+}
+
+// One stretch [lo, hi) of the decide order, start to finish: draws, step_decide, the searches it asks for.  A tick
+// is one stretch unless a vehicle may despawn inside the decide phase (decide_stretches) or vehicles decide one at a time
+// (decide_point).  nA = the tick's decide population: the stretch that ends it prefetches the next tick's words.
+int decide_range(E* e, const int lo, const int hi, const int nA) {
+  Dev& d = e->d;
+  const TsParams& P = e->P;
+  hipStream_t st = e->stream;
+  HIPOK(hipMemsetAsync(d.cnt->replan_n, 0, sizeof(int) * 8, st));
+  const Roll rl = roll_of(P);
+  MTPipe& r = e->rng_global;
+  const RLists rlists = replan_lists(e);
+  // vehicles per pass (bounds the look-ahead into the word ring); TS_DEBUG_SEG shrinks it so that tests can walk
+  // the multi-pass path on small worlds
+  static const int SEG = getenv("TS_DEBUG_SEG") ? std::max(64, atoi(getenv("TS_DEBUG_SEG"))) : SEG_VEHICLES;
+  int start = lo;
+  bool main_done = false;
+  LAUNCH(e, PK_DECIDE_PRE, hi - lo, k_decide_pre, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi);
+  while (start < hi) {
+    const int seg_end = std::min(hi, start + SEG), n = seg_end - start;
+    TRY(rng_pass1(e, start, n));
+    const uint64_t base = r.pos();
+    size_t n_take = 0, toff = 0;
+    TRY(take_table(e, rl, base, &n_take, &toff));
+    int cnt = 0;
+    uint64_t taken = 0;
+    TRY(roll_chain(e, rl, base, e->h_take + toff, n_take, n, &cnt, &taken));
+    const uint64_t final_pos = base + taken;
+    e->take_guess = taken + taken / 8 + (1u << 16);
+    // the words this pass reads must be on the device (usually prefetched during the previous tick)
+    const double t_wu = now_ms();
+    TRY(words_upload(e, final_pos + 8));
+    host_prof(e, PH_WORDS, now_ms() - t_wu, n);
+    HIPOK(hipStreamWaitEvent(st, e->words_ev, 0));
+    HIPOK(hipMemcpyAsync(d.Tcum, e->h_Tcum, ((size_t)cnt + 1) * 4, hipMemcpyHostToDevice, st));
+    // pass 3 (device): every vehicle reads its words: malfunction / sideswipe tests, rolled speeds
+    {
+      int tok = prof_begin(e, PK_RNG, n);
+      hipLaunchKernelGGL(k_rng_apply, dim3(nblk(n)), dim3(BLK), 0, st, d, start, n, (unsigned long long)base,
+                         thr53(P.malfunction_chance), thr53(P.sideswipe_chance), rl.span, rl.rshift, P.vehicle_min_speed);
+      prof_end(e, tok);
+    }
+    if (seg_end == hi) {  // k_decide_main returns at once if a draw fired (the fix-up below re-runs it)
+      LAUNCH(e, PK_DECIDE_MAIN, hi - lo, k_decide_main, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi, rlists);
+      HIPOK(hipMemcpyAsync(e->hm->replan_n, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIPOK(hipMemcpyAsync(&e->hm->rng_event, &d.cnt->rng_event, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    const double t_w3 = now_ms();
+    HIPOK(hipStreamSynchronize(st));
+    host_prof(e, PH_WAIT3, now_ms() - t_w3, n);
+    const unsigned int evk = e->hm->rng_event;
+    if (evk == 0xFFFFFFFFu) {
+      r.advance_to(final_pos);
+      start = seg_end;
+      main_done = seg_end == hi;
+      continue;
+    }
+    TRY(draw_event(e, evk, base, hi, &start));
+  }
+  if (!main_done) {  // the last pass ended with an event at the very last vehicle (or there was no pass left)
+    HIPOK(hipMemsetAsync(&d.cnt->rng_event, 0xFF, sizeof(unsigned int), st));
+    LAUNCH(e, PK_DECIDE_MAIN, hi - lo, k_decide_main, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi, rlists);
+    TRY(read_back(e, e->hm->replan_n, d.cnt->replan_n, sizeof(int) * 8));
+  }
+  if (hi == nA) TRY(prefetch_next_tick(e, rl, nA));
+  return dispatch_replans(e);
+}
+
+// What the phases of one tick share on the host
+struct HostEv { uint32_t rank; int hid; int slot; };            // a host agent's step: rain manager (hid 0) or cloud
+struct Point { uint32_t rank; int kind; int ref; int slot; };   // the device's rounds stop in front of it: kind 0 = the clock agent,
+                                                                // 1 = finishing service vehicle, 2 = a vehicle's own step_decide
+struct HostStep { uint32_t rank; int kind; int ref; };          // kind 0 rain (ref: index into host_events), 1 CityBlock,
+                                                                // 2 service start, 3 service despawn
+struct TickState {
+  bool seq = false, svc_on = false;
+  int nA = 0, nS = 0;
+  int arr_read = 0;                    // service records of this tick consumed so far
+  std::vector<int32_t> recs;           // the records fetch_records read last
+  std::vector<HostEv> host_events;
+  std::vector<HostStep> static_events;   // kinds 0 and 1, known before the rounds
+  size_t se_cur = 0;                   // static events handled so far
+  std::vector<Point> points;
+  RainDiscs discs{-1, {}, {}, {}};     // discs.n = -1: the manager has not stepped in this tick
+  int host_deaths = 0;
+  uint32_t rank_clock = 0;
+  double elapsed0 = 0;
+  int done = 0;                        // agents stepped so far in the move phase
+  int dev_deaths = 0, dev_arr = 0, dev_error = 0;   // the device's deaths / arr_n / error as the last rounds left them
+};
+
+// fetch service records [arr_read, upto) from the device
+int fetch_records(E* e, TickState& ts, int upto) {
+  ts.recs.clear();
+  if (upto > e->d.arr_cap) return fail(e, TS_E_CAPACITY, "more service records in one tick than the record buffer holds");
+  if (upto <= ts.arr_read) return TS_OK;
+  ts.recs.resize((size_t)(upto - ts.arr_read) * 3);
+  TRY(read_back(e, ts.recs.data(), e->d.arr + 3 * (size_t)ts.arr_read, ts.recs.size() * 4));
+  ts.arr_read = upto;
+  return TS_OK;
+}
+
+// Vehicles that stand on their target (a trip that ends where it starts) despawn inside the decide phase
+// (vehicle_base.py:657-661) - and leave the schedule before it is shuffled.  `standing` = their decide indices.
+int find_standing(E* e, int nA, std::vector<int32_t>& standing) {
+  if (!e->d_standing) HIPOK(dalloc(e, &e->d_standing, (size_t)E::STANDING_CAP + 1));
+  HIPOK(hipMemsetAsync(e->d_standing, 0, sizeof(int32_t), e->stream));
+  hipLaunchKernelGGL(k_find_standing, dim3(nblk(nA)), dim3(BLK), 0, e->stream, e->d, nA, e->d_standing, (int)E::STANDING_CAP);
+  int32_t n_st = 0;
+  TRY(read_back(e, &n_st, e->d_standing, sizeof(int32_t)));
+  if (n_st > E::STANDING_CAP) return fail(e, TS_E_CAPACITY, "more than 4096 vehicles stand on their own target");
+  standing.resize((size_t)n_st);
+  if (n_st > 0) HIPOK(hipMemcpy(standing.data(), e->d_standing + 1, (size_t)n_st * 4, hipMemcpyDeviceToHost));
+  std::sort(standing.begin(), standing.end());
+  if (n_st == 0) e->standing_possible = false;
+  return TS_OK;
+}
+
+// Stretch by stretch, each ending at a vehicle that may despawn: everybody up to and including it decides (draws,
+// searches and all), then it leaves the maps and the vehicle behind it loses its turn (k_decide_despawn) - the
+// later stretches see exactly what the reference's sequential loop would show them.
+int decide_stretches(E* e, TickState& ts, const std::vector<int32_t>& standing) {
+  Dev& d = e->d;
+  const int nA = ts.nA;
+  int lo = 0, removed = 0;
+  size_t ci = 0;
+  while (lo < nA) {
+    while (ci < standing.size() && standing[ci] < lo) ci++;   // (it was the one that lost its turn)
+    const bool at_candidate = ci < standing.size();
+    const int hi = at_candidate ? standing[ci] + 1 : nA;
+    d.dec_expect = at_candidate ? hi : 0;
+    if (at_candidate) HIPOK(hipMemsetAsync(&d.cnt->dec_arrived, 0, sizeof(int), e->stream));
+    int rc = decide_range(e, lo, hi, nA);
+    d.dec_expect = 0;
+    if (rc) return rc;
+    lo = hi;
+    if (at_candidate) {
+      int arrived = 0;
+      TRY(read_back(e, &arrived, &d.cnt->dec_arrived, sizeof(int)));
+      if (arrived == hi) {
+        hipLaunchKernelGGL(k_decide_despawn, dim3(1), dim3(64), 0, e->stream, d, e->P, hi - 1, hi < nA ? hi : -1);
+        e->amap_valid = false;
+        removed++;
+        lo = hi + 1;
+      }
+      ci++;
+    }
+  }
+  if (removed > 0) {   // the schedule is shuffled without them (RandomActivation.step takes the live keys)
+    TRY(compact_lists(e, removed));
+    ts.nA = e->n_active; ts.nS = e->n_sched;
+  }
+  return TS_OK;
+}
+
+// on_target_reached inside step_decide for vehicles that stay on the grid (vehicle_base.py:657-661): apply the
+// flag changes now that no decider can see them half-way, then the host part in decide order
+int decide_arrivals(E* e, TickState& ts) {
+  TRY(read_back(e, &e->hm->arr_n, &e->d.cnt->arr_n, sizeof(int)));
+  const int n_rec = e->hm->arr_n;
+  if (n_rec <= 0) return TS_OK;
+  TRY(fetch_records(e, ts, n_rec));
+  hipLaunchKernelGGL(k_decide_arrive, dim3(nblk(n_rec)), dim3(BLK), 0, e->stream, e->d, 0, n_rec);
+  std::vector<std::pair<int, int>> order;   // (decide index, vehicle)
+  for (int k = 0; k < n_rec; k++) if (ts.recs[3 * k + 2] == AR_DECIDE) order.push_back({ts.recs[3 * k], ts.recs[3 * k + 1]});
+  std::sort(order.begin(), order.end());
+  for (auto& o : order) { int k = svc_find(e, o.second); if (k >= 0) svc_start(e, e->svc[k]); }
+  return TS_OK;
+}
+
+// The host's part of the move phase, in rank order.  Host-side agents (rain manager, rain clouds) step at their ranks: they only
+// touch host state and the global stream, so they need no device synchronisation of their own (clouds created during this tick
+// do not step).  CityBlocks step on the host at their ranks too.  The device's rounds stop in front of the points: the traffic
+// generator's own step (`split`: spawns plan on the maps as they are at that point), service vehicles whose load timer runs out
+// in this tick (_finish_service plans a path there too) and, without pathfinding batching, every vehicle's step_decide.
+int collect_host_work(E* e, TickState& ts, bool split) {
+  Dev& d = e->d;
+  hipStream_t st = e->stream;
+  if (e->rain_manager) {
+    const int nh = e->n_host_agents;
+    std::vector<int32_t> slots(nh);
+    TRY(read_back(e, slots.data(), d.hslot, (size_t)nh * 4));
+    std::vector<uint32_t> ranks(nh);
+    for (int hdx = 0; hdx < nh; hdx++) {
+      if (hdx > 0 && !e->rains_all[(size_t)hdx - 1].alive) continue;
+      HIPOK(hipMemcpyAsync(&ranks[hdx], d.rank + slots[hdx], 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPOK(hipStreamSynchronize(st));
+    for (int hdx = 0; hdx < nh; hdx++) {
+      if (hdx > 0 && !e->rains_all[(size_t)hdx - 1].alive) continue;
+      ts.host_events.push_back(HostEv{ranks[hdx], hdx, slots[hdx]});
+    }
+    std::sort(ts.host_events.begin(), ts.host_events.end(), [](const HostEv& a, const HostEv& b) { return a.rank < b.rank; });
+  }
+  for (size_t k = 0; k < ts.host_events.size(); k++) ts.static_events.push_back(HostStep{ts.host_events[k].rank, 0, (int)k});
+  if (split) ts.points.push_back(Point{ts.rank_clock, 0, 0, e->clock_slot});
+  std::vector<int32_t> ids;
+  const int nb = std::min((int)e->blocks.size(), e->blocks_scheduled);
+  for (int b = 0; b < nb; b++) ids.push_back(b);
+  std::vector<int> fin;   // indices into e->svc
+  for (size_t k = 0; k < e->svc.size(); k++) {
+    auto& v = e->svc[k];
+    if (v.phase != 1) continue;
+    if (v.ticks <= 1) { fin.push_back((int)k); ids.push_back(v.vid); }   // service_ticks -= 1; <= 0 -> _finish_service
+    else v.ticks -= 1;
+  }
+  if (!ids.empty()) {
+    if ((int)ids.size() > e->cap_ids) {
+      const int nc = (int)ids.size() * 2 + 64;
+      TRY(regrow(e, &e->d_ids, 0, (size_t)nc));
+      TRY(regrow(e, &e->d_sr, 0, (size_t)nc * 2));
+      e->cap_ids = nc;
+    }
+    std::vector<int32_t> sr(ids.size() * 2);
+    HIPOK(hipMemcpyAsync(e->d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
+    if (nb > 0) hipLaunchKernelGGL(k_gather_ranks, dim3(nblk(nb)), dim3(BLK), 0, st, d, e->d_ids, nb, 0, e->d_sr);
+    if (!fin.empty())
+      hipLaunchKernelGGL(k_gather_ranks, dim3(nblk((long long)fin.size())), dim3(BLK), 0, st, d, e->d_ids + nb, (int)fin.size(), 1,
+                         e->d_sr + 2 * nb);
+    TRY(read_back(e, sr.data(), e->d_sr, sr.size() * 4));
+    for (int b = 0; b < nb; b++) ts.static_events.push_back(HostStep{(uint32_t)sr[2 * b + 1], 1, b});
+    for (size_t q = 0; q < fin.size(); q++)
+      ts.points.push_back(Point{(uint32_t)sr[2 * (nb + q) + 1], 1, e->svc[fin[q]].vid, sr[2 * (nb + q)]});
+  }
+  if (ts.seq && ts.nA > 0) {
+    // kind 2 = a vehicle about to step: its step_decide runs first (ServiceVehicleAgent.step returns before it while servicing,
+    // vehicle_service.py:43-49).  ref = its index in the decide order.
+    const int nS = ts.nS;
+    std::vector<uint32_t> rk((size_t)nS);
+    std::vector<int8_t> kinds((size_t)nS);
+    std::vector<int32_t> refs((size_t)nS), aidx((size_t)e->n_vehicles_total);
+    std::vector<uint16_t> fl((size_t)e->n_vehicles_total);
+    HIPOK(hipMemcpyAsync(rk.data(), d.rank, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
+    HIPOK(hipMemcpyAsync(kinds.data(), d.sched_kind, (size_t)nS, hipMemcpyDeviceToHost, st));
+    HIPOK(hipMemcpyAsync(refs.data(), d.sched_ref, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
+    HIPOK(hipMemcpyAsync(aidx.data(), d.active_idx, (size_t)e->n_vehicles_total * 4, hipMemcpyDeviceToHost, st));
+    TRY(read_back(e, fl.data(), d.flags, (size_t)e->n_vehicles_total * 2));
+    for (int q = 0; q < nS; q++) {
+      if (kinds[q] != K_VEHICLE) continue;
+      const int vid = refs[q];
+      if (fl[vid] & VF_SERVICING) continue;
+      ts.points.push_back(Point{rk[q], 2, aidx[vid], q});
+    }
+  }
+  std::sort(ts.static_events.begin(), ts.static_events.end(), [](const HostStep& a, const HostStep& b) { return a.rank < b.rank; });
+  std::sort(ts.points.begin(), ts.points.end(), [](const Point& a, const Point& b) { return a.rank < b.rank; });
+  return TS_OK;
+}
+
+// host-side work of every agent ranked below `hi`, in rank order: rain, CityBlocks, and what the device reported
+// about service vehicles (arrivals -> _start_service, despawns)
+int run_window(E* e, TickState& ts, uint32_t hi) {
+  Dev& d = e->d;
+  hipStream_t st = e->stream;
+  std::vector<HostStep> evs;
+  while (ts.se_cur < ts.static_events.size() && ts.static_events[ts.se_cur].rank < hi) evs.push_back(ts.static_events[ts.se_cur++]);
+  if (ts.svc_on) {
+    TRY(fetch_records(e, ts, ts.dev_arr));
+    for (size_t k = 0; k + 2 < ts.recs.size(); k += 3) {
+      if (ts.recs[k + 2] == AR_START) evs.push_back(HostStep{(uint32_t)ts.recs[k], 2, ts.recs[k + 1]});
+      else if (ts.recs[k + 2] == AR_DESPAWN) evs.push_back(HostStep{(uint32_t)ts.recs[k], 3, ts.recs[k + 1]});
+    }
+  }
+  std::stable_sort(evs.begin(), evs.end(), [](const HostStep& a, const HostStep& b) { return a.rank < b.rank; });
+  if (getenv("TS_DEBUG_EVENTS"))
+    for (const HostStep& ev : evs)
+      fprintf(stderr, "[events] tick %lld rank %u kind %d ref %d%s\n", (long long)e->C.step_count, ev.rank, ev.kind, ev.ref,
+              ev.kind == 0 ? (ts.host_events[ev.ref].hid == 0 ? " (rain manager)" : " (cloud)") : "");
+  for (const HostStep& ev : evs) {
+    if (ev.kind == 0) {
+      const HostEv& h = ts.host_events[ev.ref];
+      if (h.hid == 0) {
+        TRY(rain_manager_step(e, ts.discs));
+        if (ts.seq && ts.discs.n >= 0) {   // the vehicles that decide after the manager in this tick read the new rain_map (vehicle_base.py:104)
+          hipLaunchKernelGGL(k_rain_map, dim3(nblk((long long)e->N)), dim3(BLK), 0, st, d.rain, e->W, e->H, e->prev_discs, ts.discs);
+          e->prev_discs = ts.discs;
+          ts.discs.n = -1;
+        }
+      }
+      else if (rain_agent_step(e, h.hid)) {
+        const int8_t dead = K_DEAD;   // schedule.remove(self)
+        HIPOK(hipMemcpyAsync(d.sched_kind + h.slot, &dead, 1, hipMemcpyHostToDevice, st));
+        HIPOK(hipStreamSynchronize(st));
+        ts.host_deaths++;
+      }
+    } else if (ev.kind == 1) {
+      block_step(e, ev.ref);
+    } else {
+      const int k = svc_find(e, ev.ref);
+      if (k < 0) continue;
+      if (ev.kind == 2) svc_start(e, e->svc[k]);
+      else {
+        auto& v = e->svc[k];
+        if (v.id >= 0) e->sv_live[(size_t)(v.type == TS_TRIP_SERVICE_FOOD ? 0 : e->gen.T.total_service_vehicles_food) + v.id] = 0;
+        if (v.type == TS_TRIP_SERVICE_FOOD) e->C.live_service_food--; else e->C.live_service_waste--;
+        e->svc.erase(e->svc.begin() + k);
+      }
+    }
+  }
+  return TS_OK;
+}
+
+// Rounds of claims and resolves until `target` agents have stepped (nobody ranked at or beyond `rank_limit` moves).  Round 1
+// covers every slot; later rounds only the slots that were still blocked (ping-pong lists).
+int run_rounds(E* e, TickState& ts, int target, uint32_t rank_limit) {
+  Dev& d = e->d;
+  const TsParams& P = e->P;
+  hipStream_t st = e->stream;
+  const int nS = ts.nS;
+  int round_no = 0, pending_bound = nS;
+  HIPOK(hipMemsetAsync(d.cnt->pend_n, 0, sizeof(int) * 2, st));
+  while (ts.done < target) {
+    const int chunk = round_no == 0 ? 1 : 4;
+    e->amap_valid = false;   // the rounds below move vehicles and switch lights
+    for (int rr = 0; rr < chunk; rr++, round_no++) {
+      if ((e->epoch % EPOCHS) == 0) {  // epoch prefix wrapped: stale keys would win again -> clear once
+        size_t n = (size_t)e->N;
+        hipLaunchKernelGGL(k_claims_reset, dim3(nblk((long long)n)), dim3(BLK), 0, st, d.cell, (int)n);
+        HIPOK(hipMemsetAsync(d.gclaim_r, 0xFF, (size_t)std::max(d.G, 1) * 4, st));
+      }
+      const uint32_t prefix = (EPOCHS - 1) - (e->epoch % EPOCHS);
+      e->epoch++;
+      const int in = round_no & 1, out = in ^ 1;   // round r reads list[r & 1] (none in round 0), writes the other
+      const int32_t* in_list = round_no == 0 ? nullptr : e->pend_list[in];
+      const int grid_items = round_no == 0 ? nS : pending_bound;
+      HIPOK(hipMemsetAsync(&d.cnt->pend_n[out], 0, sizeof(int), st));
+      const int flat = round_no == 0 && d.gc_n > 0 && e->groups_scheduled == d.G && P.light_algorithm != TS_LIGHTS_DISABLED;
+      LAUNCH(e, PK_MOVE_CLAIM, grid_items, k_move_claim, dim3(nblk(grid_items)), dim3(BLK), d, P, nS, prefix, in_list,
+             &d.cnt->pend_n[in], rank_limit, flat);
+      if (flat) LAUNCH(e, PK_MOVE_CLAIM, d.gc_n, k_move_claim_groups, dim3(nblk(d.gc_n)), dim3(BLK), d, prefix, rank_limit);
+      LAUNCH(e, PK_MOVE_RESOLVE, grid_items, k_move_resolve, dim3(nblk(grid_items)), dim3(BLK), d, P, nS, prefix,
+             ts.rank_clock, ts.elapsed0, in_list, &d.cnt->pend_n[in], e->pend_list[out], &d.cnt->pend_n[out], rank_limit);
+      e->C.move_rounds++;
+    }
+    HostMirror& hm = *e->hm;
+    TRY(read_back(e, &hm.resolved, &d.cnt->resolved, sizeof(int) * 4));   // resolved .. error
+    if (hm.resolved == ts.done && hm.resolved < target) return fail(e, TS_E_DEVICE, "move phase made no progress (internal error)");
+    ts.done = hm.resolved;
+    ts.dev_deaths = hm.deaths; ts.dev_arr = hm.arr_n; ts.dev_error = hm.error;
+    pending_bound = std::max(1, target - ts.done);
+  }
+  return TS_OK;
+}
+
+// step_decide of the vehicle whose turn it is (decide index i, vehicle_base.py:669-670), alone: draws from the stream where it
+// stands, searches on the maps as they are, flags / parking / despawn applied before anybody else looks
+int decide_point(E* e, TickState& ts, int i) {
+  Dev& d = e->d;
+  hipStream_t st = e->stream;
+  d.elapsed = e->C.elapsed;
+  e->amap_valid = false;
+  d.dec_expect = i + 1;
+  HIPOK(hipMemsetAsync(&d.cnt->dec_arrived, 0, sizeof(int), st));
+  int rc = decide_range(e, i, i + 1, ts.nA);
+  d.dec_expect = 0;
+  if (rc) return rc;
+  int after[2] = {0, 0};
+  HIPOK(hipMemcpyAsync(&after[0], &d.cnt->dec_arrived, sizeof(int), hipMemcpyDeviceToHost, st));
+  TRY(read_back(e, &after[1], &d.cnt->arr_n, sizeof(int)));
+  if (after[0] == i + 1) hipLaunchKernelGGL(k_decide_despawn, dim3(1), dim3(64), 0, st, d, e->P, i, -1);
+  if (ts.svc_on && after[1] > ts.arr_read) {
+    const int first = ts.arr_read;
+    TRY(fetch_records(e, ts, after[1]));
+    hipLaunchKernelGGL(k_decide_arrive, dim3(nblk(after[1] - first)), dim3(BLK), 0, st, d, first, after[1]);
+    for (size_t k = 0; k + 2 < ts.recs.size(); k += 3)
+      if (ts.recs[k + 2] == AR_DECIDE) { int q = svc_find(e, ts.recs[k + 1]); if (q >= 0) svc_start(e, e->svc[q]); }
+  }
+  e->amap_valid = false;
+  return TS_OK;
+}
+
+// schedule.step: the device's rounds up to every point, the host's work in rank order between them
+int move_phase(E* e, TickState& ts) {
+  Dev& d = e->d;
+  hipStream_t st = e->stream;
+  ts.rank_clock = e->rank_clock_host;
+  ts.elapsed0 = e->C.elapsed;
+  const int sched_vehicles_at_shuffle = e->n_sched_vehicles;
+  if (e->sh_err) return fail(e, TS_E_DEVICE, "the shuffle thread could not send the permutation to the device");
+  HIPOK(hipStreamWaitEvent(st, e->perm_ev, 0));   // the permutation went up on its own stream while the decide phase ran
+  hipLaunchKernelGGL(k_rank_invert, dim3(nblk(ts.nS)), dim3(BLK), 0, st, e->d_perm, d.rank, ts.nS);
+  HIPOK(hipMemsetAsync(d.resolved, 0, (size_t)ts.nS, st));
+  HIPOK(hipMemsetAsync(&d.cnt->resolved, 0, sizeof(int) * 2, st));  // resolved, deaths
+  // With an armed traffic generator the phase runs in two parts: first every agent ranked before it, then the
+  // generator's own step on the host (spawns plan on the maps as they are at that point), then the rest.
+  const bool split = e->gen.armed && e->clock_slot >= 0;
+  TRY(collect_host_work(e, ts, split));
+  ts.dev_arr = ts.arr_read;
+  for (size_t pi = 0; pi <= ts.points.size(); pi++) {
+    const bool last = pi == ts.points.size();
+    const uint32_t rank_limit = last ? NO_RANK : ts.points[pi].rank;
+    TRY(run_rounds(e, ts, last ? ts.nS : (int)rank_limit, rank_limit));
+    TRY(run_window(e, ts, rank_limit));
+    if (last) break;
+    const Point& pt = ts.points[pi];
+    if (pt.kind == 2) {
+      TRY(decide_point(e, ts, pt.ref));
+      continue;      // (its movement belongs to the rounds in front of the next point)
+    }
+    if (pt.kind == 0) TRY(generator_step(e));   // the generator's turn: DynamicTrafficAgent.step on the host
+    else { const int k = svc_find(e, pt.ref); if (k >= 0) TRY(svc_finish(e, e->svc[k])); }
+    // mark the agent's slot as stepped
+    const uint8_t one = 1;
+    HIPOK(hipMemcpyAsync(d.resolved + pt.slot, &one, 1, hipMemcpyHostToDevice, st));
+    ts.done += 1;
+    HIPOK(hipMemcpyAsync(&d.cnt->resolved, &ts.done, sizeof(int), hipMemcpyHostToDevice, st));
+    HIPOK(hipStreamSynchronize(st));
+  }
+  if (ts.dev_error) return fail(e, ts.dev_error, "device-side error: a vehicle despawned inside the decide phase without the host expecting it (internal error)");
+  if (ts.discs.n >= 0) {   // RainManager.step ran: rain_map is exactly the union of the discs it saw
+    hipLaunchKernelGGL(k_rain_map, dim3(nblk((long long)e->N)), dim3(BLK), 0, st, d.rain, e->W, e->H, e->prev_discs, ts.discs);
+    e->prev_discs = ts.discs;
+  }
+  e->C.agent_steps += sched_vehicles_at_shuffle;
+  if (ts.dev_deaths + ts.host_deaths > 0) return compact_lists(e, ts.dev_deaths);   // spawns of this tick are part of the lists by now
+  return TS_OK;
+}
 
 int tick(E* e) {
   Dev& d = e->d;
   const TsParams& P = e->P;
   hipStream_t st = e->stream;
-  int nA = e->n_active, nS = e->n_sched;
+  TickState ts;
+  ts.nA = e->n_active; ts.nS = e->n_sched;
   // PATHFINDING_BATCHING=False (vehicle_base.py:669-670): no decide phase - every vehicle runs step_decide at the top of its own
   // step(), in the shuffled order.  Here: the move phase below stops in front of every vehicle (a "point", like the traffic
   // generator's), runs the decide machinery for that one vehicle on the maps and the stream as they are, and goes on.  One
   // vehicle at a time is the reference's own speed limit for this switch; nothing about it is parallel.
-  const bool seq = !P.pathfinding_batching;
-  d.seq = seq ? 1 : 0;
-  if (seq && e->dist_world > 1) return fail(e, TS_E_UNSUPPORTED, "PATHFINDING_BATCHING=False has no sharded form (its decisions are sequential)");
-  // Vehicles that stand on their target (a trip that ends where it starts) despawn inside the decide phase
-  // (vehicle_base.py:657-661) - and leave the schedule before it is shuffled.  `standing` = their decide indices.
+  ts.seq = !P.pathfinding_batching;
+  d.seq = ts.seq ? 1 : 0;
+  if (ts.seq && e->dist_world > 1) return fail(e, TS_E_UNSUPPORTED, "PATHFINDING_BATCHING=False has no sharded form (its decisions are sequential)");
   std::vector<int32_t> standing;
-  if (e->standing_possible && nA > 0 && !seq) {
-    if (!e->d_standing) HIPOK(dalloc(e, &e->d_standing, (size_t)E::STANDING_CAP + 1));
-    HIPOK(hipMemsetAsync(e->d_standing, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_find_standing, dim3(nblk(nA)), dim3(BLK), 0, st, d, nA, e->d_standing, (int)E::STANDING_CAP);
-    int32_t n_st = 0;
-    HIPOK(hipMemcpyAsync(&n_st, e->d_standing, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    if (n_st > E::STANDING_CAP) return fail(e, TS_E_CAPACITY, "more than 4096 vehicles stand on their own target");
-    standing.resize((size_t)n_st);
-    if (n_st > 0) HIPOK(hipMemcpy(standing.data(), e->d_standing + 1, (size_t)n_st * 4, hipMemcpyDeviceToHost));
-    std::sort(standing.begin(), standing.end());
-    if (n_st == 0) e->standing_possible = false;
-  }
+  if (e->standing_possible && ts.nA > 0 && !ts.seq) TRY(find_standing(e, ts.nA, standing));
   const bool careful = !standing.empty();
   // the scheduler stream is independent of everything the decide phase does: shuffle on a host thread (unless the decide
   // phase may still change the schedule)
   struct Joiner { E* e; bool done = false; ~Joiner() { if (!done) shuffle_wait(e); } } joiner{e};
-  if (!careful) shuffle_start(e, nS); else joiner.done = true;
+  if (!careful) shuffle_start(e, ts.nS); else joiner.done = true;
   const double t_tick0 = now_ms();
 
   // density_map is a function of the occupancy at this point (city_model.py:1853)
@@ -538,580 +1107,25 @@ int tick(E* e) {
   e->density_valid = false;
   e->amap_valid = false;   // the A* snapshot is rebuilt from the cell records when the first search of the tick needs it
   d.elapsed = e->C.elapsed;
-  const bool svc_on = !e->svc.empty();
-  int arr_read = 0;   // service records of this tick consumed so far
-  if (svc_on) HIPOK(hipMemsetAsync(&d.cnt->arr_n, 0, sizeof(int), st));
-  // fetch records [arr_read, upto) from the device
-  std::vector<int32_t> recs;
-  auto fetch_records = [&](int upto) -> int {
-    recs.clear();
-    if (upto > d.arr_cap) return fail(e, TS_E_CAPACITY, "more service records in one tick than the record buffer holds");
-    if (upto <= arr_read) return TS_OK;
-    recs.resize((size_t)(upto - arr_read) * 3);
-    HIPOK(hipMemcpyAsync(recs.data(), d.arr + 3 * (size_t)arr_read, recs.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    arr_read = upto;
-    return TS_OK;
-  };
+  ts.svc_on = !e->svc.empty();
+  if (ts.svc_on) HIPOK(hipMemsetAsync(&d.cnt->arr_n, 0, sizeof(int), st));
   // ---------------- decide ----------------
-    // One stretch [lo, hi) of the decide order, start to finish: draws, step_decide, the searches it asks for.  A tick
-    // is one stretch unless a vehicle may despawn inside the decide phase (see below).
-    auto decide_range = [&](const int lo, const int hi) -> int {
-    HIPOK(hipMemsetAsync(d.cnt->replan_n, 0, sizeof(int) * 8, st));
-    // random() < c  <=>  the 53-bit integer (a << 26 | b) < ceil(c * 2^53)   (exact: power-of-two scaling)
-    auto thr53 = [](double c) -> unsigned long long {
-      if (!(c > 0.0)) return 0;
-      if (c >= 1.0) return 1ull << 53;
-      return (unsigned long long)std::ceil(std::ldexp(c, 53));
-    };
-    const unsigned long long T_malf = thr53(P.malfunction_chance), T_swipe = thr53(P.sideswipe_chance);
-    const uint32_t span = (uint32_t)(P.vehicle_max_speed - P.vehicle_min_speed + 1);
-    const int rshift = __builtin_clz(span);  // getrandbits(span.bit_length())
-    MTPipe& r = e->rng_global;
-    RLists rlists;
-    for (int q = 0; q < 6; q++) rlists.l[q] = e->replan_list[q];
-    // vehicles per pass (bounds the look-ahead into the word ring); TS_DEBUG_SEG shrinks it so that tests can walk
-    // the multi-pass path on small worlds
-    static const int SEG = getenv("TS_DEBUG_SEG") ? std::max(64, atoi(getenv("TS_DEBUG_SEG"))) : SEG_VEHICLES;
-    int start = lo;
-    bool main_done = false;
-    LAUNCH(e, PK_DECIDE_PRE, hi - lo, k_decide_pre, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi);
-    while (start < hi) {
-      const int seg_end = std::min(hi, start + SEG), n = seg_end - start;
-      const int nb = nblk(n, BLK * RS_ITEMS);
-      // pass 1 (device): fixed-word prefix sums, roll ranks, roll start offsets
-      HIPOK(hipMemsetAsync(&d.cnt->rng_event, 0xFF, sizeof(unsigned int), st));
-      {
-        int tok = prof_begin(e, PK_RNG, n);
-        hipLaunchKernelGGL(k_rng_blocksum, dim3(nb), dim3(BLK), 0, st, d.F, start, n, e->rng_blocks);
-        hipLaunchKernelGGL(k_rng_scanblocks, dim3(1), dim3(1024), 0, st, e->rng_blocks, nb, d.cnt->rng_tot);
-        hipLaunchKernelGGL(k_rng_final, dim3(nb), dim3(BLK), 0, st, d, start, n, e->rng_blocks);
-        prof_end(e, tok);
-      }
-      // take table for the stretch of the stream this pass will most likely walk (estimate from the last pass;
-      // positions beyond it fall back to the accept bitmask on the host)
-      const uint64_t base = r.pos();
-      // the table built ahead of time covers [take_base, take_base + take_n); `toff` = where this pass starts in it
-      size_t n_take = 0, toff = 0;
-      if (e->take_n > 0 && base >= e->take_base && base - e->take_base + 4096 < e->take_n) {
-        toff = (size_t)(base - e->take_base);
-        n_take = e->take_n - toff;
-        HIPOK(hipEventSynchronize(e->take_ev));
-      } else {
-        n_take = (size_t)std::min<uint64_t>(e->cap_take, e->take_guess);
-        if (n_take > 0) {
-          if (e->words_uploaded < base + n_take + 64) n_take = e->words_uploaded > base + 64 ? (size_t)(e->words_uploaded - base - 64) : 0;
-        }
-        if (n_take > 0) {
-          HIPOK(hipStreamWaitEvent(st, e->words_ev, 0));
-          if (e->take_ev_recorded) HIPOK(hipEventSynchronize(e->take_ev));   // the table built ahead still owns d_take / h_take
-          hipLaunchKernelGGL(k_rng_take, dim3(nblk((long long)n_take)), dim3(BLK), 0, st, d.words, (unsigned long long)base,
-                             (int)n_take, span, rshift, e->d_take);
-          HIPOK(hipMemcpyAsync(e->h_take, e->d_take, n_take, hipMemcpyDeviceToHost, st));
-        }
-        e->take_base = base; e->take_n = n_take;   // (valid once the sync below has passed)
-      }
-      const int guess = std::min(n, e->roll_guess);
-      HIPOK(hipMemcpyAsync(e->hint + 4, d.cnt->rng_tot, sizeof(unsigned int) * 2, hipMemcpyDeviceToHost, st));
-      if (guess > 0) HIPOK(hipMemcpyAsync(e->h_rollD, d.rollD, (size_t)guess * 4, hipMemcpyDeviceToHost, st));
-      const double t_w1 = now_ms();
-      HIPOK(hipStreamSynchronize(st));
-      host_prof(e, PH_WAIT1, now_ms() - t_w1, n);
-      const uint32_t Ctot = (uint32_t)e->hint[4];
-      const int cnt = e->hint[5];
-      if (cnt > guess) {
-        HIPOK(hipMemcpyAsync(e->h_rollD + guess, d.rollD + guess, (size_t)(cnt - guess) * 4, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-      }
-      e->roll_guess = cnt + cnt / 8 + 1024;
-      // pass 2 (host): the serial chain over the speed rolls.  Roll k starts at base + rollD[k] + (words taken by
-      // the rolls before it); the producer thread tabulated how many words a roll takes from any position.
-      const double t_scan0 = now_ms();
-      uint32_t* Tcum = e->h_Tcum;
-      const uint8_t* take_tab = e->h_take + toff;
-      const uint32_t* rollD = e->h_rollD;
-      Tcum[0] = 0;
-      {
-        uint64_t T = 0, ensured = 0;
-        int k0 = 0;
-        {
-          // fast path while the walk stays inside the device-built table: nothing but the dependent chain
-          // T -> address -> byte load -> T (32-bit arithmetic, four rolls per trip)
-          uint32_t T32 = 0;
-          const uint32_t lim = (uint32_t)std::min<size_t>(n_take, 0x7FFFFFFFu);
-          int k = 0;
-          for (; k + 4 <= cnt; k += 4) {
-            const uint32_t r0 = rollD[k], r1 = rollD[k + 1], r2 = rollD[k + 2], r3 = rollD[k + 3];
-            if ((uint64_t)r3 + T32 + 256 >= lim) break;
-            const uint32_t t0 = take_tab[r0 + T32]; const uint32_t a0 = T32 + t0;
-            const uint32_t t1 = take_tab[r1 + a0]; const uint32_t a1 = a0 + t1;
-            const uint32_t t2 = take_tab[r2 + a1]; const uint32_t a2 = a1 + t2;
-            const uint32_t t3 = take_tab[r3 + a2]; const uint32_t a3 = a2 + t3;
-            if (__builtin_expect((t0 == 0) | (t1 == 0) | (t2 == 0) | (t3 == 0), 0)) break;   // a run the table does not record
-            Tcum[k + 1] = a0; Tcum[k + 2] = a1; Tcum[k + 3] = a2; Tcum[k + 4] = a3;
-            T32 = a3;
-          }
-          k0 = k; T = T32;
-        }
-        for (int k = k0; k < cnt; k++) {
-          const uint64_t pos = base + rollD[k] + T;
-          if (__builtin_expect(pos + 8 >= ensured, 0)) {
-            const uint64_t want = (pos - r.pos()) + (1u << 18);
-            r.need(want + 1248);
-            ensured = pos + (1u << 18) - 64;
-          }
-          const uint64_t rel = pos - base;
-          uint32_t t = rel < n_take ? take_tab[rel] : r.take(pos);
-          if (__builtin_expect(t == 0, 0)) {  // run longer than the table records: count it here
-            uint64_t q = pos;
-            for (;;) {
-              r.need((q - r.pos()) + 8);
-              if ((r.at(q++) >> rshift) < span) break;
-            }
-            t = (uint32_t)(q - pos);
-          }
-          T += t;
-          Tcum[k + 1] = (uint32_t)T;
-        }
-        host_prof(e, PH_SCAN, now_ms() - t_scan0, n);
-        const uint64_t final_pos = base + Ctot + T;
-        e->take_guess = (Ctot + T) + (Ctot + T) / 8 + (1u << 16);
-        // the words this pass reads must be on the device (usually prefetched during the previous tick)
-        const double t_wu = now_ms();
-        int rc = words_upload(e, final_pos + 8);
-        if (rc) return rc;
-        host_prof(e, PH_WORDS, now_ms() - t_wu, n);
-        HIPOK(hipStreamWaitEvent(st, e->words_ev, 0));
-        HIPOK(hipMemcpyAsync(d.Tcum, Tcum, ((size_t)cnt + 1) * 4, hipMemcpyHostToDevice, st));
-        // pass 3 (device): every vehicle reads its words: malfunction / sideswipe tests, rolled speeds
-        {
-          int tok = prof_begin(e, PK_RNG, n);
-          hipLaunchKernelGGL(k_rng_apply, dim3(nblk(n)), dim3(BLK), 0, st, d, start, n, (unsigned long long)base, T_malf,
-                             T_swipe, span, rshift, P.vehicle_min_speed);
-          prof_end(e, tok);
-        }
-        if (seg_end == hi) {  // k_decide_main returns at once if a draw fired (the fix-up below re-runs it)
-          LAUNCH(e, PK_DECIDE_MAIN, hi - lo, k_decide_main, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi, rlists);
-          HIPOK(hipMemcpyAsync(e->hint + 8, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
-        }
-        HIPOK(hipMemcpyAsync(e->hint + 6, &d.cnt->rng_event, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        const double t_w3 = now_ms();
-        HIPOK(hipStreamSynchronize(st));
-        host_prof(e, PH_WAIT3, now_ms() - t_w3, n);
-        const unsigned int evk = (unsigned int)e->hint[6];
-        if (evk == 0xFFFFFFFFu) {
-          r.advance_to(final_pos);
-          start = seg_end;
-          main_done = seg_end == hi;
-          continue;
-        }
-        // rare: a malfunction / sideswipe fired at vehicle ev_at.  Everything before it stands; apply the event,
-        // move the stream to just behind its draws and re-derive the draw bytes of the suffix.
-        e->C.rng_fixups++;
-        const int ev_at = (int)(evk >> 1), ev_coll = (int)(evk & 1u);
-        uint32_t cx = 0, rr = 0;
-        uint8_t fbyte = 0;
-        HIPOK(hipMemcpyAsync(&e->hint[0], d.active + ev_at, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(&e->hint[1], d.cand + ev_at, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(&cx, d.Cx + ev_at, 4, hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(&rr, d.rollrank + ev_at, 4, hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(&fbyte, d.F + ev_at, 1, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        const uint64_t after = base + cx + Tcum[rr] + (ev_coll ? ((fbyte & F_DRAW_MALF) ? 4u : 2u) : 2u);
-        r.advance_to(after);
-        LAUNCH(e, PK_EVENT, 1, k_apply_event, dim3(1), dim3(64), d, P, e->hint[0], ev_coll, e->hint[1], ev_at);
-        start = ev_at + 1;
-        if (start < hi) LAUNCH(e, PK_DECIDE_PRE, hi - start, k_decide_pre, dim3(nblk(hi - start)), dim3(BLK), d, P, start, hi);
-      }
-    }
-    if (!main_done) {  // the last pass ended with an event at the very last vehicle (or there was no pass left)
-      HIPOK(hipMemsetAsync(&d.cnt->rng_event, 0xFF, sizeof(unsigned int), st));
-      LAUNCH(e, PK_DECIDE_MAIN, hi - lo, k_decide_main, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi, rlists);
-      HIPOK(hipMemcpyAsync(e->hint + 8, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
-      HIPOK(hipStreamSynchronize(st));
-    }
-    if (hi == nA) {
-    // prefetch the part of the stream the next tick will most likely read
-    // (at most one pass' worth - the ring holds MAX_AHEAD_BLOCKS blocks; populations above SEG vehicles decide in passes)
-    { const double t_wu = now_ms();
-      const uint64_t ahead = std::min<uint64_t>((uint64_t)std::min(nA, SEG_VEHICLES) * 4 + (1u << 16), MTPipe::MAX_AHEAD_BLOCKS * 600ull - (1u << 16));
-      int rc = words_upload(e, r.pos() + ahead); if (rc) return rc;
-      host_prof(e, PH_WORDS, now_ms() - t_wu, nA); }
-    {
-      // ... and build the next tick's take table behind that upload, on the copy stream: kernel and download
-      // overlap the move phase instead of sitting in front of the next host chain
-      const uint64_t nb = r.pos();
-      size_t nt = (size_t)std::min<uint64_t>(e->cap_take, e->take_guess);
-      if (e->words_uploaded < nb + nt + 64) nt = e->words_uploaded > nb + 64 ? (size_t)(e->words_uploaded - nb - 64) : 0;
-      e->take_n = 0;
-      static const bool ahead = !getenv("TS_NO_TAKE_AHEAD");
-      if (nt > 0 && ahead) {
-        hipLaunchKernelGGL(k_rng_take, dim3(nblk((long long)nt)), dim3(BLK), 0, e->copy_stream, d.words, (unsigned long long)nb,
-                           (int)nt, span, rshift, e->d_take);
-        HIPOK(hipMemcpyAsync(e->h_take, e->d_take, nt, hipMemcpyDeviceToHost, e->copy_stream));
-        HIPOK(hipEventRecord(e->take_ev, e->copy_stream));
-        e->take_ev_recorded = true;
-        e->take_base = nb; e->take_n = nt;
-      }
-    }
-    }
-    if (e->dist_world > 1) {
-      // every rank sees the same work lists (as sets): plan this rank's share, then trade results - also when this
-      // rank has nothing to plan, the exchange is collective
-      HIPOK(hipMemcpyAsync(e->hcnt, d.cnt, sizeof(DevCnt), hipMemcpyDeviceToHost, st));
-      HIPOK(hipStreamSynchronize(st));
-      const DevCnt before = *e->hcnt;
-      const int n_all = replan_pending(e->hint + 8);
-      int rc_local = TS_OK;
-      if (n_all > e->cap_owned) { const int nc = n_all * 2 + 1024; rc_local = regrow(e, &e->owned_list, 0, (size_t)nc); if (!rc_local) e->cap_owned = nc; }
-      if (!rc_local && n_all > 0) rc_local = run_replans(e);
-      int rc = exchange_replans(e, before, rc_local);
-      if (rc) return rc;
-    } else if (replan_pending(e->hint + 8) > 0) { int rc = run_replans(e); if (rc) return rc; }
-    return TS_OK;
-    };
-  if (nA > 0 && seq) HIPOK(hipMemsetAsync(d.ev, 0, (size_t)e->n_vehicles_total, st));
-  if (nA > 0 && !seq) {
-    HIPOK(hipMemsetAsync(d.ev, 0, (size_t)e->n_vehicles_total, st));
-    if (!careful) {
-      int rc = decide_range(0, nA);
-      if (rc) return rc;
-    } else {
-      // Stretch by stretch, each ending at a vehicle that may despawn: everybody up to and including it decides (draws,
-      // searches and all), then it leaves the maps and the vehicle behind it loses its turn (k_decide_despawn) - the
-      // later stretches see exactly what the reference's sequential loop would show them.
-      int lo = 0, removed = 0;
-      size_t ci = 0;
-      while (lo < nA) {
-        while (ci < standing.size() && standing[ci] < lo) ci++;   // (it was the one that lost its turn)
-        const bool at_candidate = ci < standing.size();
-        const int hi = at_candidate ? standing[ci] + 1 : nA;
-        d.dec_expect = at_candidate ? hi : 0;
-        if (at_candidate) HIPOK(hipMemsetAsync(&d.cnt->dec_arrived, 0, sizeof(int), st));
-        int rc = decide_range(lo, hi);
-        d.dec_expect = 0;
-        if (rc) return rc;
-        lo = hi;
-        if (at_candidate) {
-          int arrived = 0;
-          HIPOK(hipMemcpyAsync(&arrived, &d.cnt->dec_arrived, sizeof(int), hipMemcpyDeviceToHost, st));
-          HIPOK(hipStreamSynchronize(st));
-          if (arrived == hi) {
-            hipLaunchKernelGGL(k_decide_despawn, dim3(1), dim3(64), 0, st, d, P, hi - 1, hi < nA ? hi : -1);
-            e->amap_valid = false;
-            removed++;
-            lo = hi + 1;
-          }
-          ci++;
-        }
-      }
-      if (removed > 0) {   // the schedule is shuffled without them (RandomActivation.step takes the live keys)
-        int na = 0, ns = 0;
-        int rc = compact(e, 0, e->n_active, &na); if (rc) return rc;
-        rc = compact(e, 1, e->n_sched, &ns); if (rc) return rc;
-        e->n_active = na; e->n_sched = ns; e->n_sched_vehicles -= removed;
-        nA = na; nS = ns;
-        if (e->clock_slot >= 0 && e->mixed_order) {
-          std::vector<int8_t> kinds(ns);
-          HIPOK(hipMemcpy(kinds.data(), d.sched_kind, ns, hipMemcpyDeviceToHost));
-          e->clock_slot = -1;
-          for (int q = 0; q < ns; q++) if (kinds[q] == TS_AGENT_CLOCK) { e->clock_slot = q; break; }
-        }
-      }
-    }
-    if (svc_on) {
-      // on_target_reached inside step_decide for vehicles that stay on the grid (vehicle_base.py:657-661): apply the
-      // flag changes now that no decider can see them half-way, then the host part in decide order
-      HIPOK(hipMemcpyAsync(e->hint + 2, &d.cnt->arr_n, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPOK(hipStreamSynchronize(st));
-      const int n_rec = e->hint[2];
-      if (n_rec > 0) {
-        int rc = fetch_records(n_rec);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_decide_arrive, dim3(nblk(n_rec)), dim3(BLK), 0, st, d, 0, n_rec);
-        std::vector<std::pair<int, int>> order;   // (decide index, vehicle)
-        for (int k = 0; k < n_rec; k++) if (recs[3 * k + 2] == AR_DECIDE) order.push_back({recs[3 * k], recs[3 * k + 1]});
-        std::sort(order.begin(), order.end());
-        for (auto& o : order) { int k = svc_find(e, o.second); if (k >= 0) svc_start(e, e->svc[k]); }
-      }
-    }
+  if (ts.nA > 0) HIPOK(hipMemsetAsync(d.ev, 0, (size_t)e->n_vehicles_total, st));
+  if (ts.nA > 0 && !ts.seq) {
+    TRY(careful ? decide_stretches(e, ts, standing) : decide_range(e, 0, ts.nA, ts.nA));
+    if (ts.svc_on) TRY(decide_arrivals(e, ts));
   }
-
-  if (careful) { shuffle_start(e, nS); joiner.done = false; }
+  if (careful) { shuffle_start(e, ts.nS); joiner.done = false; }
   // ---------------- move (schedule.step) ----------------
   const double t_dec1 = now_ms();
-  host_prof(e, PH_DECIDE_WALL, t_dec1 - t_tick0, nA);
+  host_prof(e, PH_DECIDE_WALL, t_dec1 - t_tick0, ts.nA);
   shuffle_wait(e);
   joiner.done = true;
-  host_prof(e, PH_SHUFFLE_WAIT, now_ms() - t_dec1, nS);
-  host_prof(e, PH_SHUFFLE, e->shuffle_ms, nS);
+  host_prof(e, PH_SHUFFLE_WAIT, now_ms() - t_dec1, ts.nS);
+  host_prof(e, PH_SHUFFLE, e->shuffle_ms, ts.nS);
   const double t_move0 = now_ms();
-  const uint32_t rank_clock = e->rank_clock_host;
-  const int sched_vehicles_at_shuffle = e->n_sched_vehicles;
-  const double elapsed0 = e->C.elapsed;
-  if (nS > 0) {
-    if (e->sh_err) return fail(e, TS_E_DEVICE, "the shuffle thread could not send the permutation to the device");
-    HIPOK(hipStreamWaitEvent(st, e->perm_ev, 0));   // the permutation went up on its own stream while the decide phase ran
-    hipLaunchKernelGGL(k_rank_invert, dim3(nblk(nS)), dim3(BLK), 0, st, e->d_perm, d.rank, nS);
-    HIPOK(hipMemsetAsync(d.resolved, 0, (size_t)nS, st));
-    HIPOK(hipMemsetAsync(&d.cnt->resolved, 0, sizeof(int) * 2, st));  // resolved, deaths
-    // Round 1 covers every slot; later rounds only the slots that were still blocked (ping-pong lists).
-    // With an armed traffic generator the phase runs in two parts: first every agent ranked before it, then the
-    // generator's own step on the host (spawns plan on the maps as they are at that point), then the rest.
-    const bool split = e->gen.armed && e->clock_slot >= 0;
-    // Host-side agents (rain manager, rain clouds) step at their ranks too.  They only touch host state and the
-    // global stream, so they need no device synchronisation of their own: the ones ranked before the traffic
-    // generator run now, the others after its step.  Clouds created during this tick do not step.
-    struct HostEv { uint32_t rank; int hid; int slot; };
-    std::vector<HostEv> host_events;
-    RainDiscs discs; discs.n = -1;   // -1: the manager has not stepped in this tick
-    int host_deaths = 0;
-    if (e->rain_manager) {
-      const int nh = e->n_host_agents;
-      std::vector<int32_t> slots(nh);
-      HIPOK(hipMemcpyAsync(slots.data(), d.hslot, (size_t)nh * 4, hipMemcpyDeviceToHost, st));
-      HIPOK(hipStreamSynchronize(st));
-      std::vector<uint32_t> ranks(nh);
-      for (int hdx = 0; hdx < nh; hdx++) {
-        if (hdx > 0 && !e->rains_all[(size_t)hdx - 1].alive) continue;
-        HIPOK(hipMemcpyAsync(&ranks[hdx], d.rank + slots[hdx], 4, hipMemcpyDeviceToHost, st));
-      }
-      HIPOK(hipStreamSynchronize(st));
-      for (int hdx = 0; hdx < nh; hdx++) {
-        if (hdx > 0 && !e->rains_all[(size_t)hdx - 1].alive) continue;
-        host_events.push_back(HostEv{ranks[hdx], hdx, slots[hdx]});
-      }
-      std::sort(host_events.begin(), host_events.end(), [](const HostEv& a, const HostEv& b) { return a.rank < b.rank; });
-    }
-    // CityBlocks step on the host at their ranks; service vehicles whose load timer runs out in this tick do
-    // _finish_service there too (it plans a path on the maps as they are at that point, like the generator's spawns)
-    struct Point { uint32_t rank; int kind; int ref; int slot; };   // kind 0 = the clock agent, 1 = finishing service vehicle
-    std::vector<Point> points;
-    struct StaticEv { uint32_t rank; int kind; int ref; };          // kind 0 = rain event (index), 1 = CityBlock
-    std::vector<StaticEv> static_events;
-    for (size_t k = 0; k < host_events.size(); k++) static_events.push_back(StaticEv{host_events[k].rank, 0, (int)k});
-    if (split) points.push_back(Point{rank_clock, 0, 0, e->clock_slot});
-    {
-      std::vector<int32_t> ids;
-      const int nb = std::min((int)e->blocks.size(), e->blocks_scheduled);
-      for (int b = 0; b < nb; b++) ids.push_back(b);
-      std::vector<int> fin;   // indices into e->svc
-      for (size_t k = 0; k < e->svc.size(); k++) {
-        auto& v = e->svc[k];
-        if (v.phase != 1) continue;
-        if (v.ticks <= 1) { fin.push_back((int)k); ids.push_back(v.vid); }   // service_ticks -= 1; <= 0 -> _finish_service
-        else v.ticks -= 1;
-      }
-      if (!ids.empty()) {
-        if ((int)ids.size() > e->cap_ids) {
-          const int nc = (int)ids.size() * 2 + 64;
-          int rc = regrow(e, &e->d_ids, 0, (size_t)nc); if (rc) return rc;
-          rc = regrow(e, &e->d_sr, 0, (size_t)nc * 2); if (rc) return rc;
-          e->cap_ids = nc;
-        }
-        std::vector<int32_t> sr(ids.size() * 2);
-        HIPOK(hipMemcpyAsync(e->d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
-        if (nb > 0) hipLaunchKernelGGL(k_gather_ranks, dim3(nblk(nb)), dim3(BLK), 0, st, d, e->d_ids, nb, 0, e->d_sr);
-        if (!fin.empty())
-          hipLaunchKernelGGL(k_gather_ranks, dim3(nblk((long long)fin.size())), dim3(BLK), 0, st, d, e->d_ids + nb, (int)fin.size(), 1,
-                             e->d_sr + 2 * nb);
-        HIPOK(hipMemcpyAsync(sr.data(), e->d_sr, sr.size() * 4, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        for (int b = 0; b < nb; b++) static_events.push_back(StaticEv{(uint32_t)sr[2 * b + 1], 1, b});
-        for (size_t q = 0; q < fin.size(); q++)
-          points.push_back(Point{(uint32_t)sr[2 * (nb + q) + 1], 1, e->svc[fin[q]].vid, sr[2 * (nb + q)]});
-      }
-    }
-    if (seq && nA > 0) {
-      // kind 2 = a vehicle about to step: its step_decide runs first (ServiceVehicleAgent.step returns before it while servicing,
-      // vehicle_service.py:43-49).  ref = its index in the decide order.
-      std::vector<uint32_t> rk((size_t)nS);
-      std::vector<int8_t> kinds((size_t)nS);
-      std::vector<int32_t> refs((size_t)nS), aidx((size_t)e->n_vehicles_total);
-      std::vector<uint16_t> fl((size_t)e->n_vehicles_total);
-      HIPOK(hipMemcpyAsync(rk.data(), d.rank, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
-      HIPOK(hipMemcpyAsync(kinds.data(), d.sched_kind, (size_t)nS, hipMemcpyDeviceToHost, st));
-      HIPOK(hipMemcpyAsync(refs.data(), d.sched_ref, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
-      HIPOK(hipMemcpyAsync(aidx.data(), d.active_idx, (size_t)e->n_vehicles_total * 4, hipMemcpyDeviceToHost, st));
-      HIPOK(hipMemcpyAsync(fl.data(), d.flags, (size_t)e->n_vehicles_total * 2, hipMemcpyDeviceToHost, st));
-      HIPOK(hipStreamSynchronize(st));
-      for (int q = 0; q < nS; q++) {
-        if (kinds[q] != K_VEHICLE) continue;
-        const int vid = refs[q];
-        if (fl[vid] & VF_SERVICING) continue;
-        points.push_back(Point{rk[q], 2, aidx[vid], q});
-      }
-    }
-    std::sort(static_events.begin(), static_events.end(), [](const StaticEv& a, const StaticEv& b) { return a.rank < b.rank; });
-    std::sort(points.begin(), points.end(), [](const Point& a, const Point& b) { return a.rank < b.rank; });
-    size_t se_cur = 0;
-    // host-side work of every agent ranked below `hi`, in rank order: rain, CityBlocks, and what the device reported
-    // about service vehicles (arrivals -> _start_service, despawns)
-    auto run_window = [&](uint32_t hi) -> int {
-      struct Ev { uint32_t rank; int kind; int ref; };   // kind 0 rain, 1 block, 2 service start, 3 service despawn
-      std::vector<Ev> evs;
-      while (se_cur < static_events.size() && static_events[se_cur].rank < hi) {
-        evs.push_back(Ev{static_events[se_cur].rank, static_events[se_cur].kind, static_events[se_cur].ref});
-        se_cur++;
-      }
-      if (svc_on) {
-        const int upto = e->hint[2];
-        int rc = fetch_records(upto);
-        if (rc) return rc;
-        for (size_t k = 0; k + 2 < recs.size(); k += 3) {
-          if (recs[k + 2] == AR_START) evs.push_back(Ev{(uint32_t)recs[k], 2, recs[k + 1]});
-          else if (recs[k + 2] == AR_DESPAWN) evs.push_back(Ev{(uint32_t)recs[k], 3, recs[k + 1]});
-        }
-      }
-      std::stable_sort(evs.begin(), evs.end(), [](const Ev& a, const Ev& b) { return a.rank < b.rank; });
-      if (getenv("TS_DEBUG_EVENTS"))
-        for (const Ev& ev : evs)
-          fprintf(stderr, "[events] tick %lld rank %u kind %d ref %d%s\n", (long long)e->C.step_count, ev.rank, ev.kind, ev.ref,
-                  ev.kind == 0 ? (host_events[ev.ref].hid == 0 ? " (rain manager)" : " (cloud)") : "");
-      for (const Ev& ev : evs) {
-        if (ev.kind == 0) {
-          const HostEv& h = host_events[ev.ref];
-          if (h.hid == 0) {
-            int rc = rain_manager_step(e, discs); if (rc) return rc;
-            if (seq && discs.n >= 0) {   // the vehicles that decide after the manager in this tick read the new rain_map (vehicle_base.py:104)
-              hipLaunchKernelGGL(k_rain_map, dim3(nblk((long long)e->N)), dim3(BLK), 0, st, d.rain, e->W, e->H, e->prev_discs, discs);
-              e->prev_discs = discs;
-              discs.n = -1;
-            }
-          }
-          else if (rain_agent_step(e, h.hid)) {
-            const int8_t dead = K_DEAD;   // schedule.remove(self)
-            HIPOK(hipMemcpyAsync(d.sched_kind + h.slot, &dead, 1, hipMemcpyHostToDevice, st));
-            HIPOK(hipStreamSynchronize(st));
-            host_deaths++;
-          }
-        } else if (ev.kind == 1) {
-          block_step(e, ev.ref);
-        } else {
-          const int k = svc_find(e, ev.ref);
-          if (k < 0) continue;
-          if (ev.kind == 2) svc_start(e, e->svc[k]);
-          else {
-            auto& v = e->svc[k];
-            if (v.id >= 0) e->sv_live[(size_t)(v.type == TS_TRIP_SERVICE_FOOD ? 0 : e->gen.T.total_service_vehicles_food) + v.id] = 0;
-            if (v.type == TS_TRIP_SERVICE_FOOD) e->C.live_service_food--; else e->C.live_service_waste--;
-            e->svc.erase(e->svc.begin() + k);
-          }
-        }
-      }
-      return TS_OK;
-    };
-    e->hint[0] = 0; e->hint[1] = 0; e->hint[2] = arr_read; e->hint[3] = 0;
-    int done = 0;
-    for (size_t pi = 0; pi <= points.size(); pi++) {
-      const bool last = pi == points.size();
-      const uint32_t rank_limit = last ? NO_RANK : points[pi].rank;
-      const int target = last ? nS : (int)points[pi].rank;
-      int round_no = 0, pending_bound = nS;
-      HIPOK(hipMemsetAsync(d.cnt->pend_n, 0, sizeof(int) * 2, st));
-      while (done < target) {
-        const int chunk = round_no == 0 ? 1 : 4;
-        e->amap_valid = false;   // the rounds below move vehicles and switch lights
-        for (int rr = 0; rr < chunk; rr++, round_no++) {
-          if ((e->epoch % EPOCHS) == 0) {  // epoch prefix wrapped: stale keys would win again -> clear once
-            size_t n = (size_t)e->N;
-            hipLaunchKernelGGL(k_claims_reset, dim3(nblk((long long)n)), dim3(BLK), 0, st, d.cell, (int)n);
-            HIPOK(hipMemsetAsync(d.gclaim_r, 0xFF, (size_t)std::max(d.G, 1) * 4, st));
-          }
-          const uint32_t prefix = (EPOCHS - 1) - (e->epoch % EPOCHS);
-          e->epoch++;
-          const int in = round_no & 1, out = in ^ 1;   // round r reads list[r & 1] (none in round 0), writes the other
-          const int32_t* in_list = round_no == 0 ? nullptr : e->pend_list[in];
-          const int grid_items = round_no == 0 ? nS : pending_bound;
-          HIPOK(hipMemsetAsync(&d.cnt->pend_n[out], 0, sizeof(int), st));
-          const int flat = round_no == 0 && d.gc_n > 0 && e->groups_scheduled == d.G && P.light_algorithm != TS_LIGHTS_DISABLED;
-          LAUNCH(e, PK_MOVE_CLAIM, grid_items, k_move_claim, dim3(nblk(grid_items)), dim3(BLK), d, P, nS, prefix, in_list,
-                 &d.cnt->pend_n[in], rank_limit, flat);
-          if (flat) LAUNCH(e, PK_MOVE_CLAIM, d.gc_n, k_move_claim_groups, dim3(nblk(d.gc_n)), dim3(BLK), d, prefix, rank_limit);
-          LAUNCH(e, PK_MOVE_RESOLVE, grid_items, k_move_resolve, dim3(nblk(grid_items)), dim3(BLK), d, P, nS, prefix,
-                 rank_clock, elapsed0, in_list, &d.cnt->pend_n[in], e->pend_list[out], &d.cnt->pend_n[out], rank_limit);
-          e->C.move_rounds++;
-        }
-        HIPOK(hipMemcpyAsync(e->hint, &d.cnt->resolved, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        int now = e->hint[0];
-        if (now == done && now < target) return fail(e, TS_E_DEVICE, "move phase made no progress (internal error)");
-        done = now;
-        pending_bound = std::max(1, target - done);
-      }
-      const int dev_error = e->hint[3], dev_deaths = e->hint[1];
-      { int rc = run_window(last ? NO_RANK : rank_limit); if (rc) return rc; }
-      if (!last && points[pi].kind == 2) {
-        // step_decide of the vehicle whose turn it is (vehicle_base.py:669-670), alone: draws from the stream where it stands,
-        // searches on the maps as they are, flags / parking / despawn applied before anybody else looks
-        const int i = points[pi].ref;
-        d.elapsed = e->C.elapsed;
-        e->amap_valid = false;
-        d.dec_expect = i + 1;
-        HIPOK(hipMemsetAsync(&d.cnt->dec_arrived, 0, sizeof(int), st));
-        int rc = decide_range(i, i + 1);
-        d.dec_expect = 0;
-        if (rc) return rc;
-        int after[2] = {0, 0};
-        HIPOK(hipMemcpyAsync(&after[0], &d.cnt->dec_arrived, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(&after[1], &d.cnt->arr_n, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        if (after[0] == i + 1) hipLaunchKernelGGL(k_decide_despawn, dim3(1), dim3(64), 0, st, d, P, i, -1);
-        if (svc_on && after[1] > arr_read) {
-          const int first = arr_read;
-          rc = fetch_records(after[1]);
-          if (rc) return rc;
-          hipLaunchKernelGGL(k_decide_arrive, dim3(nblk(after[1] - first)), dim3(BLK), 0, st, d, first, after[1]);
-          for (size_t k = 0; k + 2 < recs.size(); k += 3)
-            if (recs[k + 2] == AR_DECIDE) { int q = svc_find(e, recs[k + 1]); if (q >= 0) svc_start(e, e->svc[q]); }
-        }
-        e->amap_valid = false;
-        e->hint[3] = dev_error; e->hint[1] = dev_deaths;
-        continue;      // (its movement belongs to the rounds in front of the next point)
-      }
-      if (!last) {
-        const Point& pt = points[pi];
-        if (pt.kind == 0) {
-          // the generator's turn: DynamicTrafficAgent.step on the host
-          int rc = generator_step(e);
-          if (rc) return rc;
-        } else {
-          const int k = svc_find(e, pt.ref);
-          if (k >= 0) { int rc = svc_finish(e, e->svc[k]); if (rc) return rc; }
-        }
-        // mark the agent's slot as stepped
-        const uint8_t one = 1;
-        HIPOK(hipMemcpyAsync(d.resolved + pt.slot, &one, 1, hipMemcpyHostToDevice, st));
-        done += 1;
-        HIPOK(hipMemcpyAsync(&d.cnt->resolved, &done, sizeof(int), hipMemcpyHostToDevice, st));
-        HIPOK(hipStreamSynchronize(st));
-      }
-      e->hint[3] = dev_error; e->hint[1] = dev_deaths;
-    }
-    if (e->hint[3]) return fail(e, e->hint[3], "device-side error: a vehicle despawned inside the decide phase without the host expecting it (internal error)");
-    if (discs.n >= 0)   // RainManager.step ran: rain_map is exactly the union of the discs it saw
-    {
-      hipLaunchKernelGGL(k_rain_map, dim3(nblk((long long)e->N)), dim3(BLK), 0, st, d.rain, e->W, e->H, e->prev_discs, discs);
-      e->prev_discs = discs;
-    }
-    e->C.agent_steps += sched_vehicles_at_shuffle;
-    const int vehicle_deaths = e->hint[1];
-    const int deaths = vehicle_deaths + host_deaths;
-    if (deaths > 0) {
-      int na = 0, ns = 0;
-      int rc = compact(e, 0, e->n_active, &na); if (rc) return rc;   // spawns of this tick are part of the lists by now
-      rc = compact(e, 1, e->n_sched, &ns); if (rc) return rc;
-      e->n_active = na; e->n_sched = ns; e->n_sched_vehicles -= vehicle_deaths;
-      if (e->clock_slot >= 0 && e->mixed_order) {
-        // the clock never dies, but dead vehicles scheduled before it shift its slot: find it again
-        std::vector<int8_t> kinds(ns);
-        HIPOK(hipMemcpy(kinds.data(), d.sched_kind, ns, hipMemcpyDeviceToHost));
-        e->clock_slot = -1;
-        for (int q = 0; q < ns; q++) if (kinds[q] == TS_AGENT_CLOCK) { e->clock_slot = q; break; }
-      }
-    }
-  }
-  host_prof(e, PH_MOVE_WALL, now_ms() - t_move0, nS);
+  if (ts.nS > 0) TRY(move_phase(e, ts));
+  host_prof(e, PH_MOVE_WALL, now_ms() - t_move0, ts.nS);
   if (e->clock_slot >= 0 && !e->gen.armed) e->C.elapsed += P.time_per_step_seconds;  // an armed generator did it in its step
   e->C.step_count++;
   if (e->prof) { HIPOK(hipStreamSynchronize(st)); prof_collect(e); }
@@ -1263,7 +1277,7 @@ int ts_create(const TsWorld* w, const TsParams* params, ts_handle* out) {
   }
   ok &= hipMemcpyAsync(e->d_crc, table, sizeof(table), hipMemcpyHostToDevice, st) == hipSuccess;
   ok &= hipHostMalloc((void**)&e->hcnt, sizeof(DevCnt)) == hipSuccess;
-  ok &= hipHostMalloc((void**)&e->hint, sizeof(int) * 16) == hipSuccess;
+  ok &= hipHostMalloc((void**)&e->hm, sizeof(HostMirror)) == hipSuccess;
   ok &= hipStreamSynchronize(st) == hipSuccess;
   (void)hipFree(t_allowed); (void)hipFree(t_road_type); (void)hipFree(t_inter); (void)hipFree(t_node);
   if (!ok) return bail(TS_E_DEVICE);
@@ -1314,7 +1328,7 @@ int ts_destroy(ts_handle e) {
   if (e->quad_stream) { (void)hipStreamSynchronize(e->quad_stream); (void)hipStreamDestroy(e->quad_stream); }
   if (e->quad_ev0) (void)hipEventDestroy(e->quad_ev0);
   if (e->quad_ev1) (void)hipEventDestroy(e->quad_ev1);
-  if (e->hint) (void)hipHostFree(e->hint);
+  if (e->hm) (void)hipHostFree(e->hm);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   uint32_t* hw = e->h_words;
   delete e;                       // stops the producer threads before their ring storage goes away
@@ -1608,9 +1622,9 @@ static int add_vehicles_core(ts_handle e, int n, std::vector<int32_t>& start, st
   SpawnArgs a{ds, dg, dp, dl, dof, dser};
   hipLaunchKernelGGL(k_spawn, dim3(nblk(n)), dim3(BLK), 0, st, e->d, e->P, a, n, e->n_vehicles_total, e->n_active,
                      e->n_sched, e->C.elapsed, e->d_overflow, e->d_total, (e->d.amap && e->amap_valid) ? 1 : 0);
-  HIPOK(hipMemcpyAsync(e->hint, e->d_total, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPOK(hipMemcpyAsync(&e->hm->scratch, e->d_total, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPOK(hipStreamSynchronize(st));
-  if (e->hint[0] > 0) hipLaunchKernelGGL(k_spawn_serial, dim3(1), dim3(64), 0, st, e->d, e->d_overflow, e->hint[0]);
+  if (e->hm->scratch > 0) hipLaunchKernelGGL(k_spawn_serial, dim3(1), dim3(64), 0, st, e->d, e->d_overflow, e->hm->scratch);
   HIPOK(hipStreamSynchronize(st));
   // live_* counters (city_model.py:1910-1918)
   long long add_int = 0, add_thr = 0;
@@ -1642,15 +1656,13 @@ static int add_vehicle_planned(ts_handle e, int start, int goal, int pop_type) {
 // self.path = self._compute_path() for a vehicle standing on `start` with target `goal` (both already on the
 // device): city._path_cache first, then the phase 0-4 planner on the maps as they are now
 static int plan_vehicle(ts_handle e, int vid, int start, int goal) {
-  int rc;
   const uint64_t key = ((uint64_t)(uint32_t)start << 32) | (uint32_t)goal;
   Dev& d = e->d;
   if (e->P.pathfinding_cache) {
     auto it = e->path_cache.find(key);
     if (it != e->path_cache.end()) {
       const auto& cp = it->second;
-      rc = pool_make_room(e, cp.words.size() + 1);
-      if (rc) return rc;
+      TRY(pool_make_room(e, cp.words.size() + 1));
       uint32_t off = (uint32_t)e->pool_used;
       int len = cp.len, zero = 0;
       if (!cp.words.empty()) HIPOK(hipMemcpy(d.pool + off, cp.words.data(), cp.words.size() * 4, hipMemcpyHostToDevice));
@@ -1661,24 +1673,20 @@ static int plan_vehicle(ts_handle e, int vid, int start, int goal) {
       return pool_to_device(e);
     }
   }
-  if (!e->density_valid) { rc = ensure_density(e, d.occ_snap); if (rc) return rc; e->density_valid = true; }
-  rc = ensure_slots(e);
-  if (rc) return rc;
-  rc = ensure_amap(e);
-  if (rc) return rc;
+  if (!e->density_valid) { TRY(ensure_density(e, d.occ_snap)); e->density_valid = true; }
+  TRY(ensure_slots(e));
+  TRY(ensure_amap(e));
   for (int attempt = 0; attempt < 3; attempt++) {
     hipLaunchKernelGGL(k_spawn_plan, dim3(1), dim3(64), 0, e->stream, d, e->P, e->slots, vid, e->d_status);
-    HIPOK(hipMemcpyAsync(e->hint, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPOK(hipMemcpyAsync(&e->hm->scratch, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     HIPOK(hipStreamSynchronize(e->stream));
-    if (e->hint[0] != -2) break;
-    rc = pool_make_room(e, (size_t)e->slots.cap + (1u << 16));  // pool full: make room and plan again
-    if (rc) return rc;
+    if (e->hm->scratch != -2) break;
+    TRY(pool_make_room(e, (size_t)e->slots.cap + (1u << 16)));  // pool full: make room and plan again
   }
-  if (e->hint[0] == -2) return fail(e, TS_E_CAPACITY, "path pool exhausted while planning a spawn");
-  if (e->hint[0] < 0) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
-  const int len = e->hint[0];
-  rc = pool_from_device(e);
-  if (rc) return rc;
+  const int len = e->hm->scratch;
+  if (len == -2) return fail(e, TS_E_CAPACITY, "path pool exhausted while planning a spawn");
+  if (len < 0) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
+  TRY(pool_from_device(e));
   uint16_t fl = 0;
   HIPOK(hipMemcpy(&fl, d.flags + vid, 2, hipMemcpyDeviceToHost));
   if (e->P.pathfinding_cache && len > 0 && !(fl & (VF_OVER | VF_DETOUR))) {
@@ -1779,16 +1787,7 @@ int ts_remove_vehicle(ts_handle e, int32_t spawn_idx, int32_t population_type) {
   if (fl & VF_SVC) return fail(e, TS_E_UNSUPPORTED, "service vehicles cannot be removed by the host");
   hipLaunchKernelGGL(k_remove_one, dim3(1), dim3(64), 0, e->stream, d, spawn_idx, (int)population_type);
   // the lists close up at once (the reference's list.remove / schedule.remove): the next tick shuffles the live keys
-  int na = 0, ns = 0;
-  int rc = compact(e, 0, e->n_active, &na); if (rc) return rc;
-  rc = compact(e, 1, e->n_sched, &ns); if (rc) return rc;
-  e->n_active = na; e->n_sched = ns; e->n_sched_vehicles -= 1;
-  if (e->clock_slot >= 0 && e->mixed_order) {
-    std::vector<int8_t> kinds(ns);
-    HIPOK(hipMemcpy(kinds.data(), d.sched_kind, ns, hipMemcpyDeviceToHost));
-    e->clock_slot = -1;
-    for (int q = 0; q < ns; q++) if (kinds[q] == TS_AGENT_CLOCK) { e->clock_slot = q; break; }
-  }
+  TRY(compact_lists(e, 1));
   HIPOK(hipMemsetAsync(&d.cnt->deaths, 0, sizeof(int), e->stream));
   e->amap_valid = false;
   return sync_counters(e);
@@ -2050,20 +2049,17 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
     return fail(e, TS_E_INVALID, "astar endpoints out of bounds");
   if (maximum_steps < e->N && maximum_steps > A_STEPS_MAX)
     return fail(e, TS_E_UNSUPPORTED, "a binding maximum_steps above 4094 is not carried (use >= width * height for 'unlimited')");
-  int rc = ensure_density(e, e->d.occ);  // "evaluated on the engine's current maps"
-  if (rc) return rc;
+  TRY(ensure_density(e, e->d.occ));  // "evaluated on the engine's current maps"
   e->density_valid = false;
-  rc = ensure_slots(e);
-  if (rc) return rc;
+  TRY(ensure_slots(e));
   e->amap_valid = false;
-  rc = ensure_amap(e);
-  if (rc) return rc;
+  TRY(ensure_amap(e));
   e->amap_valid = false;
   hipLaunchKernelGGL(k_astar_single, dim3(1), dim3(64), 0, e->stream, e->d, e->P, e->slots, sy * e->W + sx, gy * e->W + gx, soft,
                      ignore_flow, maximum_steps, e->d_status);
-  HIPOK(hipMemcpyAsync(e->hint, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPOK(hipMemcpyAsync(&e->hm->scratch, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPOK(hipStreamSynchronize(e->stream));
-  const int len = e->hint[0];
+  const int len = e->hm->scratch;
   if (len < 0) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
   if (len > cap_cells) return TS_E_CAPACITY;
   if (len > 0) {
