@@ -1,0 +1,61 @@
+"""A resume proxy for the checkpoint tests: it looks like one engine (trafficsimulation_amd._capi.CApi) to the existing
+comparators, but switches engines in the middle of a run.
+
+Every call made on engine A before its first `step` is recorded (the set-up: create, lights, schedule, seeds, generator,
+vehicles).  Once `switch_at` ticks have run, the proxy saves A, replays the recorded set-up on a fresh engine B, loads the
+blob into B, closes A and from then on delegates everything to B.  `trace_util.replay_and_compare` and friends then check a
+run that changed engines mid-way against the reference, tick by tick."""
+from __future__ import annotations
+
+from trafficsimulation_amd._lib import new_engine
+
+
+class ResumeProxy:
+    def __init__(self, switch_at, make_engine=new_engine, save_every=False):
+        """switch_at: the tick count after which the engines change (None: never).  save_every: also save (and throw the blob
+        away) after every tick - a save must not change what the source computes afterwards."""
+        self._eng = make_engine()
+        self._make = make_engine
+        self._setup = []
+        self._ticks = 0
+        self._switch_at = switch_at
+        self._save_every = save_every
+        self.switched = False
+        self.blob_sizes = []
+
+    @property
+    def engine(self):
+        return self._eng
+
+    def __getattr__(self, name):
+        attr = getattr(self._eng, name)
+        if not callable(attr) or self._ticks > 0 or name == "step":
+            return attr
+
+        def recorded(*args, **kwargs):
+            self._setup.append((name, args, kwargs))
+            return attr(*args, **kwargs)
+        return recorded
+
+    def _switch(self):
+        blob = self._eng.checkpoint_save()
+        self.blob_sizes.append(len(blob))
+        b = self._make()
+        for name, args, kwargs in self._setup:
+            getattr(b, name)(*args, **kwargs)
+        b.checkpoint_load(blob)
+        self._eng.close()
+        self._eng = b
+        self.switched = True
+
+    def step(self, n=1):
+        for _ in range(n):
+            if not self.switched and self._switch_at is not None and self._ticks == self._switch_at:
+                self._switch()
+            self._eng.step(1)
+            self._ticks += 1
+            if self._save_every:
+                self.blob_sizes.append(len(self._eng.checkpoint_save()))
+
+    def close(self):
+        self._eng.close()

@@ -1,0 +1,94 @@
+"""CityModel checkpoints: copy.deepcopy, pickle and save / CityModel.load give a second model with an engine of its own
+that continues the run exactly."""
+import copy
+import os
+import pickle
+import sys
+
+import numpy as np
+import pytest
+
+from trafficsimulation_amd import _capi as capi
+from trafficsimulation_amd import worldgen
+from trafficsimulation_amd.mesa_api import CityModel, VehicleAgent
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+
+
+def snapshot(m):
+    e = m.engine
+    c = e.counters()
+    return {"maps": [e.map(w) for w in (capi.MAP_OCCUPANCY, capi.MAP_STOP, capi.MAP_STUCK, capi.MAP_RAIN)],
+            "veh": e.vehicles(), "meta": e.vehicle_meta(), "groups": e.groups(), "blocks": e.blocks(),
+            "rng": [e.rng_fingerprint(capi.RNG_GLOBAL), e.rng_fingerprint(capi.RNG_SCHEDULER)],
+            "counters": [getattr(c, f) for f, _ in capi.TsCounters._fields_], "stats": str(e.cached_stats()),
+            "step_count": m.step_count, "n_agents": len(m.active_vehicle_agents),
+            "ids": sorted(str(v.id) for v in m.active_vehicle_agents)}
+
+
+def assert_same(a, b, ctx):
+    for k in a:
+        if k == "maps":
+            for i, (p, q) in enumerate(zip(a[k], b[k])):
+                assert np.array_equal(p, q), f"{ctx}: map {i}"
+        elif isinstance(a[k], np.ndarray):
+            assert np.array_equal(a[k], b[k]), f"{ctx}: {k}"
+        else:
+            assert a[k] == b[k], f"{ctx}: {k}"
+
+
+@pytest.fixture(scope="module")
+def model():
+    from run_city import TRAFFIC
+    m = CityModel(200, 200, seed=1, traffic=dict(TRAFFIC))
+    # one vehicle of the caller's own, so that the custom-id map has something to carry
+    ents, exits = m.get_start_blocks(), m.get_exit_blocks()
+    VehicleAgent("my_car", m, ents[0], exits[-1], population_type="internal")
+    for _ in range(50):
+        m.step()
+    yield m
+    m.close()
+
+
+def test_deepcopy_is_an_independent_twin(model):
+    before = snapshot(model)
+    twin = copy.deepcopy(model)
+    assert twin.engine.h.value != model.engine.h.value
+    assert_same(before, snapshot(twin), "right after the copy")
+    for _ in range(50):
+        twin.step()
+    assert_same(before, snapshot(model), "the original after stepping the copy")
+    assert twin.step_count == model.step_count + 50
+    for _ in range(50):
+        model.step()
+    assert_same(snapshot(model), snapshot(twin), "both after 50 more ticks")
+    assert "my_car" in {str(v.id) for v in twin.active_vehicle_agents} | {str(v.id) for v in twin._vehicles.values()}
+    twin.close()
+
+
+def test_pickle_round_trip(model):
+    other = pickle.loads(pickle.dumps(model))
+    assert_same(snapshot(model), snapshot(other), "after the round trip")
+    for _ in range(10):
+        model.step()
+        other.step()
+    assert_same(snapshot(model), snapshot(other), "10 ticks later")
+    other.close()
+
+
+def test_save_and_load_without_worldgen(model, tmp_path, monkeypatch):
+    path = str(tmp_path / "city.npz")
+    model.save(path)
+
+    def no_worldgen(*a, **k):
+        raise AssertionError("CityModel.load ran world-gen")
+    monkeypatch.setattr(worldgen, "generate_world", no_worldgen)
+    loaded = CityModel.load(path)
+    assert_same(snapshot(model), snapshot(loaded), "after the load")
+    for _ in range(20):
+        model.step()
+        loaded.step()
+    assert_same(snapshot(model), snapshot(loaded), "20 ticks later")
+    loaded.close()

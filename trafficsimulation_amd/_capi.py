@@ -613,6 +613,40 @@ class CApi:
         self._chk(self._f("counters")(self.h, C.byref(c)))
         return c
 
+    # ---- checkpoints (include/trafficsim_checkpoint.h) ----------------------------------------------
+    def _ckpt_fn(self, name: str):
+        """The checkpoint entries, bound on first use: the CPU oracle shares this class and has none of them."""
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no checkpoints")
+        fn.restype = C.c_int
+        fn.argtypes = {"checkpoint_size": [C.c_void_p, C.POINTER(C.c_uint64)],
+                       "checkpoint_save": [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
+                       "checkpoint_load": [C.c_void_p, C.c_void_p, C.c_uint64]}[name]
+        return fn
+
+    def checkpoint_size(self) -> int:
+        """Exact size in bytes of a checkpoint of the current state."""
+        n = C.c_uint64()
+        self._chk(self._ckpt_fn("checkpoint_size")(self.h, C.byref(n)))
+        return n.value
+
+    def checkpoint_save(self) -> bytes:
+        """Every piece of dynamic state as one canonical blob (between steps only)."""
+        fn = self._ckpt_fn("checkpoint_save")
+        n = self.checkpoint_size()
+        buf = np.empty(max(n, 1), dtype=np.uint8)
+        got = C.c_uint64()
+        self._chk(fn(self.h, buf.ctypes.data, n, C.byref(got)))
+        return buf[:got.value].tobytes()
+
+    def checkpoint_load(self, blob) -> None:
+        """Replace all dynamic state with a blob from checkpoint_save of an engine built from the same world."""
+        fn = self._ckpt_fn("checkpoint_load")
+        a = np.frombuffer(bytes(blob) if not isinstance(blob, (bytes, bytearray, np.ndarray)) else blob, dtype=np.uint8)
+        a = np.ascontiguousarray(a)
+        self._chk(fn(self.h, a.ctypes.data if a.size else None, a.size))
+
     def astar(self, sx, sy, gx, gy, soft_obstacles=False, ignore_flow=False, maximum_steps=0x7FFFFFFF):
         cap = self.W * self.H
         out = np.zeros((cap, 2), dtype=np.int32)

@@ -1184,6 +1184,16 @@ int ts_create(const TsWorld* w, const TsParams* params, ts_handle* out) {
   memset(&e->C, 0, sizeof(e->C));
   e->P = *params;
   e->W = w->width; e->H = w->height; e->N = w->width * w->height;
+  {
+    Fp fw;
+    fw.mix((uint64_t)(uint32_t)w->width << 32 | (uint32_t)w->height);
+    const size_t n = (size_t)w->width * w->height;
+    fw.bytes(w->allowed_dirs_map, n); fw.bytes(w->is_road_map, n); fw.bytes(w->road_type_map, n); fw.bytes(w->intersection_map, n);
+    e->fp_world = fw.h;
+    Fp fpar;   // (every named field; the struct's trailing padding is not part of it)
+    fpar.bytes(params, offsetof(TsParams, pathfinding_batching) + sizeof(params->pathfinding_batching));
+    e->fp_params = fpar.h;
+  }
   Dev& d = e->d;
   d.W = e->W; d.H = e->H; d.N = e->N;
   d.W8 = (e->W + 7) / 8; d.H8 = (e->H + 7) / 8;
@@ -1408,6 +1418,20 @@ int ts_set_lights(ts_handle e, const TsLightTables* t) {
   if (t->g_neighbors) nb.assign(t->g_neighbors, t->g_neighbors + (size_t)G * 8);
   const int32_t* nc = t->g_neighbors_ctor ? t->g_neighbors_ctor : t->g_neighbors;
   if (nc) nbc.assign(nc, nc + (size_t)G * 8);
+  {
+    // checkpoint fingerprint of the tables (checkpoint.h)
+    Fp f;
+    f.mix((uint64_t)(uint32_t)G << 32 | (uint32_t)L);
+    auto ragged = [&](const int32_t* off, const int32_t* v, int n, int per) { f.bytes(off, (size_t)(n + 1) * 4); f.bytes(v, (size_t)off[n] * per * 4); };
+    ragged(t->g_light_off, t->light_xy, G, 2);
+    ragged(t->light_ctrl_off, t->light_ctrl_xy, L, 2);
+    ragged(t->g_ns_off, t->g_ns, G, 1); ragged(t->g_ew_off, t->g_ew, G, 1);
+    ragged(t->g_icell_off, t->g_icell_xy, G, 2);
+    ragged(t->g_ns_in_off, t->g_ns_in_xy, G, 2); ragged(t->g_ns_out_off, t->g_ns_out_xy, G, 2);
+    ragged(t->g_ew_in_off, t->g_ew_in_xy, G, 2); ragged(t->g_ew_out_off, t->g_ew_out_xy, G, 2);
+    f.bytes(nb.data(), nb.size() * 4); f.bytes(nbc.data(), nbc.size() * 4);
+    e->fp_lights = f.h;
+  }
   for (int g = 0; g < G * 4; g++)
     if (nb[g * 2 + 1] >= G || nbc[g * 2 + 1] >= G) return fail(e, TS_E_INVALID, "neighbor group index out of range");
   { int rc = up(&d.g_nb, nb.data(), nb.size()); if (rc) return rc; }
@@ -1545,6 +1569,35 @@ int ts_set_traffic_generator(ts_handle e, const TsTrafficTables* t) {
   if (n_sv > 0 && !e->d.arr) {
     e->d.arr_cap = 1 << 16;
     HIPOK(dalloc(e, &e->d.arr, (size_t)e->d.arr_cap * 3));
+  }
+  {
+    // checkpoint fingerprint of the tables (checkpoint.h): every scalar and array the generator, the blocks and the
+    // service fleet read
+    Fp f;
+    // (field by field: the structs have padding)
+    const int32_t ints[] = {t->n_blocks, t->n_highway_entrances, t->n_highway_exits, t->internal_population_per_day,
+                            t->passing_population_per_day, t->start_offset_seconds, t->n_zones, t->total_service_vehicles_food,
+                            t->total_service_vehicles_waste, t->service_load_time, t->gradual_city_block_resources,
+                            t->food_consumption_ticks, t->waste_production_ticks, t->needs_food_type_mask,
+                            t->produces_waste_type_mask, t->statistics_update_interval, t->blk_inner_cells ? 1 : 0};
+    const double dbls[] = {t->service_max_load_food, t->service_max_load_waste, t->food_capacity_per_cell, t->waste_capacity_per_cell};
+    f.bytes(ints, sizeof(ints)); f.bytes(dbls, sizeof(dbls));
+    for (int z = 0; z < t->n_zones; z++) {
+      const TsTrafficZone& Z = t->zones[z];
+      const int32_t zi[3] = {Z.start_hour, Z.end_hour, Z.n_internal};
+      f.bytes(zi, sizeof(zi)); f.bytes(&Z.through_distribution, 8);
+      f.bytes(Z.origin_type, sizeof(Z.origin_type)); f.bytes(Z.dest_type, sizeof(Z.dest_type)); f.bytes(Z.fraction, sizeof(Z.fraction));
+    }
+    const int nb = t->n_blocks;
+    f.bytes(t->blk_type, (size_t)nb * 4);
+    f.bytes(t->blk_entr_off, (size_t)(nb + 1) * 4); f.bytes(t->blk_entr_xy, (size_t)t->blk_entr_off[nb] * 8);
+    f.bytes(t->highway_entrances_xy, (size_t)std::max(0, t->n_highway_entrances) * 8);
+    f.bytes(t->highway_exits_xy, (size_t)std::max(0, t->n_highway_exits) * 8);
+    if (t->blk_inner_cells) {
+      f.bytes(t->blk_inner_cells, (size_t)nb * 4);
+      f.bytes(t->blk_service_off, (size_t)(nb + 1) * 4); f.bytes(t->blk_service_xy, (size_t)t->blk_service_off[nb] * 8);
+    }
+    e->fp_traffic = f.h;
   }
   G.pending.clear();
   G.current_day = 0;
@@ -2071,3 +2124,5 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
 }
 
 }  // extern "C"
+
+#include "checkpoint.h"

@@ -680,6 +680,7 @@ class CityModel:
         # "service_food", "service_waste", ...} arms the engine's generator; it draws day 0 from the global stream now
         self._service_cfg = dict(traffic or {})
         self._traffic_armed = traffic is not None
+        self._defaults = dict(defaults or {})
         if traffic is not None:
             engine.set_traffic_generator(tables, internal_per_day=traffic.get("P_int", 10000),
                                          passing_per_day=traffic.get("P_thr", 2400),
@@ -995,6 +996,84 @@ class CityModel:
 
     def close(self):
         self.engine.close()
+
+    # ---- checkpoints (include/trafficsim_checkpoint.h): save / load, copy.deepcopy and pickle --------------------------
+    def _checkpoint_state(self) -> dict:
+        """Everything a second model needs: the world tables, the constructor's settings, the facade's own state and the
+        engine's blob."""
+        import json
+        self._flush_host_writes()
+        blob = self.engine.checkpoint_save()
+        vs = sorted(self._vehicles.items())
+        def xy(c):
+            return (-1, -1) if c is None else (int(c.position[0]), int(c.position[1]))
+        config = dict(defaults=self._defaults, traffic=self._service_cfg if self._traffic_armed else None, seed=self._seed,
+                      step_count=int(self.step_count), n_spawned=int(self._n_spawned))
+        st = {"t/" + k: np.asarray(v) for k, v in self.tables.items()}
+        st.update({
+            "config_json": np.asarray(json.dumps(config)),
+            "veh_spawn": np.asarray([i for i, _ in vs], dtype=np.int64),
+            "veh_id": np.asarray([str(v.id) for _, v in vs], dtype=str),
+            "veh_kind": np.asarray([1 if isinstance(v, ServiceVehicleAgent) else 0 for _, v in vs], dtype=np.int8),
+            "veh_pop": np.asarray([str(v.population_type) for _, v in vs], dtype=str),
+            "veh_type": np.asarray([str(v.vehicle_type) for _, v in vs], dtype=str),
+            "veh_start": np.asarray([xy(v.__dict__.get("start_cell")) for _, v in vs], dtype=np.int32).reshape(-1, 2),
+            "veh_target": np.asarray([xy(v.__dict__.get("_static_target")) for _, v in vs], dtype=np.int32).reshape(-1, 2),
+            "engine_blob": np.frombuffer(blob, dtype=np.uint8),
+        })
+        return st
+
+    def _restore(self, st, engine: Optional[capi.CApi] = None):
+        """__init__ from a _checkpoint_state (the world from its tables: no world-gen), then the blob."""
+        import json
+        cfg = json.loads(str(np.asarray(st["config_json"])))
+        tables = {k[2:]: np.asarray(st[k]) for k in st if k.startswith("t/")}
+        CityModel.__init__(self, tables=tables, seed=cfg["seed"], defaults=cfg["defaults"], traffic=cfg["traffic"], engine=engine)
+        self.engine.checkpoint_load(np.asarray(st["engine_blob"], dtype=np.uint8))
+        self.step_count, self._n_spawned = int(cfg["step_count"]), int(cfg["n_spawned"])
+        for k, i in enumerate(np.asarray(st["veh_spawn"])):
+            klass = ServiceVehicleAgent if int(st["veh_kind"][k]) else VehicleAgent
+            v = object.__new__(klass)
+            v.id = str(st["veh_id"][k])
+            v.unique_id = str_to_unique_int(v.id)
+            v.model = v.city_model = self
+            sx, sy = (int(q) for q in st["veh_start"][k])
+            v.start_cell = None if sx < 0 else self.cell(sx, sy)
+            tx, ty = (int(q) for q in st["veh_target"][k])
+            if tx >= 0 or klass is VehicleAgent:
+                v._static_target = None if tx < 0 else self.cell(tx, ty)
+            v.population_type, v.vehicle_type = str(st["veh_pop"][k]), str(st["veh_type"][k])
+            v.base_color = Defaults.VEHICLE_BASE_COLOR
+            v._spawn_idx = int(i)
+            self._vehicles[v._spawn_idx] = v
+            self._vehicle_by_uid[v.unique_id] = v
+        self._invalidate()
+        return self
+
+    def save(self, path) -> None:
+        """One .npz (no pickled objects) from which CityModel.load resumes this run exactly."""
+        with open(path, "wb") as f:
+            np.savez(f, **self._checkpoint_state())
+
+    @classmethod
+    def load(cls, path, engine: Optional[capi.CApi] = None) -> "CityModel":
+        """The model `save` wrote: the engine is rebuilt from the stored world tables (world-gen does not run) and takes
+        the stored state; stepping it continues the saved run bit for bit."""
+        with np.load(path, allow_pickle=False) as z:
+            st = {k: z[k] for k in z.files}
+        return cls.__new__(cls)._restore(st, engine)
+
+    def __deepcopy__(self, memo):
+        """A second model with an engine of its own (same library), in the state of this one."""
+        other = type(self).__new__(type(self))
+        memo[id(self)] = other
+        return other._restore(self._checkpoint_state(), capi.CApi(self.engine.lib, self.engine.prefix))
+
+    def __getstate__(self):
+        return self._checkpoint_state()
+
+    def __setstate__(self, st):
+        self._restore(st)
 
 
 def agent_portrayal(agent):
