@@ -25,6 +25,7 @@ from trafficsimulation_amd._lib import new_engine
 from trafficsimulation_amd.world import load_trace
 from tests.trace_util import setup_from_trace, check_initial, replay_and_compare, trace_path
 rank, local, world = tdist.env_rank()
+os.environ.update(%(rank_env)r.get(rank, {}))      # (this rank's own engine settings, read when its engine plans)
 d = tdist.init("gloo", rank, world)
 res = {}
 for name in %(traces)r:
@@ -40,7 +41,8 @@ for name in %(traces)r:
     n = replay_and_compare(api, tr)          # raises on the first tick that differs from the reference
     c = api.counters()
     res[name] = dict(ticks=n, astar_calls=int(c.astar_calls), want_calls=int(tr["astar_calls_spawn"]) + int(tr["astar_per_tick"].sum()),
-                     exchanges=sr.calls, bytes=sr.bytes_sent, fp=list(api.rng_fingerprint(capi.RNG_GLOBAL)))
+                     exchanges=sr.calls, bytes=sr.bytes_sent, fp=list(api.rng_fingerprint(capi.RNG_GLOBAL)),
+                     quad_jobs=api.debug_quad_stats()["jobs"])
     api.close()
 with open(os.path.join(%(outdir)r, "rank%%d.json" %% rank), "w") as f:      # (one file per rank: lines printed to the
     json.dump(dict(rank=rank, res=res), f)                                  # shared stdout of the ranks can interleave)
@@ -55,19 +57,43 @@ def test_ranks_sharded_replans_match_the_reference(world, device_direct, tight_p
     (ts_set_replan_sharding_device; the collective itself is gloo here) and once with the host-staged form."""
     # closed populations, then the agents that step on the host inside the shuffled order (traffic generator spawning and
     # planning mid-tick, service vehicles with their arrival records, rain): every rank runs those redundantly
-    traces = ["full_64_s1", "full_96_s8", "faults_64_s9", "carve_96_s10", "dta_64_s12", "rain_96_s14", "config1_64_s11", "despawn_96_s25", "startgoal_96_s27"]
-    if world > 2:
-        traces = ["full_96_s8", "faults_64_s9", "dta_64_s12", "config1_64_s11", "startgoal_96_s27"]
+    traces = TRACES_2 if world == 2 else TRACES_N
     port = str(29541 + world + (10 if device_direct else 0) + (20 if tight_pool else 0) + (40 if quads else 0))
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = {}
     if quads:           # (every rank's share of every queue on k_replan_quad, its hand-backs on k_replan beside it)
         env["TS_QUAD"], env["TS_QUAD_MIN"] = "1", "1"
     if tight_pool:      # (almost no room reserved in the path pool: planners find it full, the pool is garbage-collected / grown INSIDE the
         env["TS_DEBUG_POOL_PER_ENTRY"] = "2"      # sharded tick, and the export must not rely on the pool's growth to size its buffer)
+    _run_ranks_and_check(world, device_direct, traces, port, env, {})
+
+
+TRACES_2 = ["full_64_s1", "full_96_s8", "faults_64_s9", "carve_96_s10", "dta_64_s12", "rain_96_s14", "config1_64_s11", "despawn_96_s25", "startgoal_96_s27"]
+TRACES_N = ["full_96_s8", "faults_64_s9", "dta_64_s12", "config1_64_s11", "startgoal_96_s27"]
+
+
+@pytest.mark.parametrize("rank0_classes", [None, "1"])
+def test_ranks_that_plan_on_different_searchers_match_the_reference(rank0_classes):
+    """Whether a rank sends a queue to k_replan_quad is its own decision (TS_QUAD, TS_QUAD_MIN, and the quads' memory, which
+    comes from that rank's free device memory).  Rank 0 plans every queue with the quads (all classes but the most expensive
+    one; with TS_QUAD_CLASSES=1 only class 0, so k_replan serves classes 3, 2 and 1 beside them), rank 1 with k_replan alone.
+    Both must still deal the queue out the same way - entry j of the whole sorted queue is rank j % world's, whichever kernel
+    serves it - or some vehicles are planned twice and others not at all: every rank matches the reference at every tick,
+    and the searches of the two ranks add up to the reference's."""
+    rank_env = {0: {"TS_QUAD": "1", "TS_QUAD_MIN": "1"}, 1: {"TS_QUAD": "0"}}
+    if rank0_classes:
+        rank_env[0]["TS_QUAD_CLASSES"] = rank0_classes
+    port = str(29661 + (1 if rank0_classes else 0))
+    rows = _run_ranks_and_check(2, True, TRACES_2, port, {}, rank_env)
+    assert sum(rows[0]["res"][name]["quad_jobs"] for name in TRACES_2) > 0          # rank 0 did plan on the quads ...
+    assert all(rows[1]["res"][name]["quad_jobs"] == 0 for name in TRACES_2)         # ... and rank 1 never
+
+
+def _run_ranks_and_check(world, device_direct, traces, port, env_all, rank_env):
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0", **env_all)
     with tempfile.TemporaryDirectory() as outdir:
         path = os.path.join(outdir, "worker.py")
         with open(path, "w") as f:
-            f.write(WORKER % dict(root=ROOT, traces=traces, device_direct=device_direct, outdir=outdir))
+            f.write(WORKER % dict(root=ROOT, traces=traces, device_direct=device_direct, outdir=outdir, rank_env=rank_env))
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                "--master-addr", "127.0.0.1", "--master-port", port, path]
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -89,6 +115,7 @@ def test_ranks_sharded_replans_match_the_reference(world, device_direct, tight_p
         assert sum(rb["res"][name]["bytes"] for rb in rows) > 0
         if world == 2:
             assert all(rb["res"][name]["bytes"] > 0 for rb in rows)       # both ranks planned something
+    return rows
 
 
 NCCL_WORKER = r'''

@@ -224,7 +224,7 @@ def _pair_full(size, vehicles, seed, extra=None, carves=False):
     return hip_api, cpu_api
 
 
-def _compare_full(h, c, ticks, every=1):
+def _compare_full(h, c, ticks, every=1, close=True):
     for t in range(ticks):
         h.step(1)
         c.step(1)
@@ -245,8 +245,9 @@ def _compare_full(h, c, ticks, every=1):
     for f in ("stuck", "live_through", "count_completed_through", "total_distance_through", "agent_steps", "overtaking",
               "in_stuck_detour", "collisions", "malfunctions", "astar_calls", "elapsed", "step_count"):
         assert getattr(ch, f) == getattr(cc, f), f
-    h.close()
-    c.close()
+    if close:
+        h.close()
+        c.close()
     return ch
 
 

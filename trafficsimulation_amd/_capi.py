@@ -613,6 +613,23 @@ class CApi:
         self._chk(self._f("counters")(self.h, C.byref(c)))
         return c
 
+    QUAD_STATS = ("jobs", "handbacks", "window", "heap", "budget", "path_buffer", "policy_bail", "policy_overflow",
+                  "searches", "epoch_wraps", "passes")
+
+    def debug_quad_stats(self) -> dict:
+        """Debugging hook (ts_debug_quad_stats, not part of include/trafficsim.h): the quad searcher's counters over this
+        engine's quad passes - entries it took, hand-backs to k_replan in all and by reason, searches started, table-epoch
+        wraps, passes."""
+        fn = getattr(self.lib, self.prefix + "debug_quad_stats", None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}debug_quad_stats: this engine has no quad searcher")
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        out = np.zeros(len(self.QUAD_STATS), dtype=np.int64)
+        n = self._chk(fn(self.h, out.ctypes.data, len(out)))
+        assert n == len(out), f"ts_debug_quad_stats reports {n} counters, this wrapper knows {len(out)}"
+        return dict(zip(self.QUAD_STATS, (int(v) for v in out)))
+
     # ---- checkpoints (include/trafficsim_checkpoint.h) ----------------------------------------------
     def _ckpt_fn(self, name: str):
         """The checkpoint entries, bound on first use: the CPU oracle shares this class and has none of them."""

@@ -1175,17 +1175,25 @@ __device__ int g_rtrace_cap = 0;
 #endif
 struct RQueue {
   int32_t* l[4]; int n[4]; int32_t *retry_list, *owned_list; int rank, world;
+  int pos0[4];   // position of class c's first entry in the whole queue (classes 3, 2, 1, 0 in turn, whatever class_mask serves)
   // vehicles k_replan_quad (astar_quad.h) hands back while both kernels run: entries appear in fb_list (-1 = not yet
   // written; tickets from quad_n[2]) until all fb_waves quad waves have counted themselves out in quad_n[3]
   int32_t* fb_list; int fb_waves, fb_cap;   // fb_cap: entries the quads were given = the most they can hand back
 };
+// where each class list starts in the whole queue - classes 3, 2, 1, 0 in turn, every class counted whichever kernel serves it:
+// the sharded mode deals entries out by this position, so that a rank that sends some classes to k_replan_quad and a rank that
+// does not agree on who owns what
+__device__ __forceinline__ void replan_class_pos0(const Dev& d, int* pos0) {
+  const int f3 = d.cnt->replan_n[3], f2 = d.cnt->replan_n[2], f1 = d.cnt->replan_n[1];
+  pos0[3] = 0; pos0[2] = f3; pos0[1] = f3 + f2; pos0[0] = f3 + f2 + f1;
+}
 __device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParams& P, AScratch* S, const RQueue& q) {
   const int n3 = uni(q.n[3]), n2 = uni(q.n[2]), n1 = uni(q.n[1]), n0 = uni(q.n[0]);
   if (threadIdx.x == 0) g_job = atomicAdd(&d.cnt->replan_n[5], 1);
   __syncthreads();
   const int j = uni(g_job);
   __syncthreads();
-  int i;
+  int i, pos = j;
   if (j >= n3 + n2 + n1 + n0) {
     if (q.fb_waves == 0) return 0;
     // this launch's own lists are done: serve the hand-back list.  An entry is only ever claimed once it has been produced
@@ -1225,14 +1233,15 @@ __device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParam
     __syncthreads();
     if (i < 0) return 0;
   }
-  else if (j < n3) i = q.l[3][j];
-  else if (j < n3 + n2) i = q.l[2][j - n3];
-  else if (j < n3 + n2 + n1) i = q.l[1][j - n3 - n2];
-  else i = q.l[0][j - n3 - n2 - n1];
+  else if (j < n3) { i = q.l[3][j]; pos = q.pos0[3] + j; }
+  else if (j < n3 + n2) { i = q.l[2][j - n3]; pos = q.pos0[2] + j - n3; }
+  else if (j < n3 + n2 + n1) { i = q.l[1][j - n3 - n2]; pos = q.pos0[1] + j - n3 - n2; }
+  else { i = q.l[0][j - n3 - n2 - n1]; pos = q.pos0[0] + j - n3 - n2 - n1; }
   i = uni(i);
-  // (sharded mode: the queue is in the same total order on every rank - run_replans sorts it by (key, index) - and entry j
-  // of it is rank j % world's; hand-backs of this rank's own quads are this rank's)
-  if (q.world > 1 && j < n3 + n2 + n1 + n0 && (j % q.world) != q.rank) return 1;
+  // (sharded mode: the queue is in the same total order on every rank - run_replans sorts it by (key, index) - and the entry
+  // at position pos of it is rank pos % world's, whichever kernel serves its class on this rank; hand-backs of this rank's own
+  // quads are this rank's)
+  if (q.world > 1 && j < n3 + n2 + n1 + n0 && (pos % q.world) != q.rank) return 1;
   // the most expensive classes are a tick's critical path (its longest search bounds it): their waves take the issue slots
   // of their SIMD first, the five waves beside them fill in behind (`s_setprio`; TS_NO_PRIO: a build without it)
 #ifndef TS_NO_PRIO
@@ -1278,6 +1287,7 @@ TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_replan(Dev d, TsParams P, 
   scratch_bind(sl, blockIdx.x, S);
   RQueue q;
   for (int c = 0; c < 4; c++) { q.l[c] = lists.l[c]; q.n[c] = ((class_mask >> c) & 1) ? d.cnt->replan_n[c] : 0; }
+  replan_class_pos0(d, q.pos0);
   q.retry_list = retry_list; q.owned_list = owned_list; q.rank = rank; q.world = world;
   q.fb_list = fb_list; q.fb_waves = fb_waves; q.fb_cap = fb_cap;
   while (uni(replan_turn(d, P, &S, q))) {}

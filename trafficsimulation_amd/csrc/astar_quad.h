@@ -54,14 +54,24 @@ static_assert(((size_t)16 * QL + 64) * 8 * TS_QUAD_WAVES_PER_CU <= 160 * 1024 - 
 #endif
 constexpr int QT_MAX = TS_QUAD_WINDOW;       // table window: at most 1152 x 1152 cells around the search's start (a multiple of 8)
 static_assert(QT_MAX % 8 == 0, "the table window is 8 x 8-tiled");
-constexpr int Q_CELLS = 4096;               // path buffer capacity per search (cells)
-constexpr int Q_SPILL = 7936;               // heap slots per search beyond LDS (HBM)
+#ifndef TS_QUAD_CELLS
+#define TS_QUAD_CELLS 4096
+#endif
+constexpr int Q_CELLS = TS_QUAD_CELLS;      // path buffer capacity per search (cells)
+#ifndef TS_QUAD_SPILL
+#define TS_QUAD_SPILL 7936
+#endif
+constexpr int Q_SPILL = TS_QUAD_SPILL;      // heap slots per search beyond LDS (HBM)
 #ifndef TS_QUAD_MAX_EXP
 #define TS_QUAD_MAX_EXP (1 << 17)
 #endif
 constexpr int Q_MAX_EXP = TS_QUAD_MAX_EXP;  // expansions after which a quad hands its search (and vehicle) to k_replan
 constexpr uint32_t Q_DIST_MASK = (1u << 22) - 1, Q_STAMP_SHIFT = 24, Q_DIR_SHIFT = 22;
 enum { QS_NEEDJOB = 0, QS_POLICY = 1, QS_SEARCH = 2, QS_FOUND = 3, QS_EMPTY = 4, QS_ABANDON = 5, QS_IDLE = 6 };
+// the quads' own diagnostics (QSlots::stats, added up per engine by run_quad_pass, read by ts_debug_quad_stats): hand-backs
+// to k_replan by reason, searches started, table-epoch wraps.  Not simulation state: never exchanged, never checkpointed.
+enum { QST_WINDOW = 1, QST_HEAP = 2, QST_BUDGET = 3, QST_PATHBUF = 4, QST_BAIL = 5, QST_OVERFLOW = 6, QST_SEARCHES = 7, QST_WRAPS = 8,
+       QST_N = 16 };
 
 struct QSlots {
   int n_slots;            // searches = quads: sixteen per wave
@@ -74,6 +84,7 @@ struct QSlots {
   int32_t* cells;         // per slot 5 * Q_CELLS + 3 * MAXB
   int32_t* log;           // per slot 3 * QLOG
   uint32_t* slot_epoch;
+  unsigned long long* stats;   // QST_N counters (QST_*)
 };
 constexpr int Q_DWORDS = (QL + Q_SPILL) / 16 + 4;
 constexpr int Q_HEAP_MAX = (QL + Q_SPILL) < (32 * QL - 2) ? (QL + Q_SPILL) : (32 * QL - 2);   // largest heap a quad carries
@@ -104,7 +115,7 @@ struct QState {
   int soft;
   int n_exp, n_relax;
   unsigned long long xpre;  // heap entry hs - 1 when it lies beyond LDS (requested at the end of the previous turn)
-  int why;                  // why the search was abandoned (1 window / g, 2 heap, 3 expansion budget, 4 path buffer): ts_debug statistics
+  int why;                  // why the search was abandoned (QST_WINDOW / g, QST_HEAP, QST_BUDGET, QST_PATHBUF): QSlots::stats
 #ifdef TS_QUAD_PROF
   long long pf[8], pt;
 #endif
@@ -368,12 +379,12 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
     if (is_goal) { st = QS_FOUND; break; }
     if (stale) break;
     s.n_exp++;
-    if (s.n_exp > Q_MAX_EXP) { st = QS_ABANDON; s.why = 3; break; }   // a long search: k_replan's single search is the faster one
-    if (relax & 16) { st = QS_ABANDON; s.why = 1; break; }
+    if (s.n_exp > Q_MAX_EXP) { st = QS_ABANDON; s.why = QST_BUDGET; break; }   // a long search: k_replan's single search is the faster one
+    if (relax & 16) { st = QS_ABANDON; s.why = QST_WINDOW; break; }
     if (relax == 0) break;
     const int n_new = __builtin_popcount((unsigned)relax);
     // (a heap the spill holds and whose slots' ancestors 5 and up all lie in LDS: (i + 1) / 32 - 1 < QL)
-    if (s.hs + n_new > Q_HEAP_MAX) { st = QS_ABANDON; s.why = 2; break; }
+    if (s.hs + n_new > Q_HEAP_MAX) { st = QS_ABANDON; s.why = QST_HEAP; break; }
     s.n_relax += n_new;
     if (ok) K.tab[t_ix] = (uint32_t)ngi | ((uint32_t)j << Q_DIR_SHIFT) | s.stamp;   // dist / came_from (226-227)
     const int nf0 = qperm<QP_B0>(nf_l), nf1 = qperm<QP_B1>(nf_l), nf2 = qperm<QP_B2>(nf_l), nf3 = qperm<QP_B3>(nf_l);
@@ -438,7 +449,7 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
 }
 
 struct QReq { int start, goal, soft, cap; int32_t* out; };
-struct QQueue { int32_t* l[4]; int n[4]; int32_t *retry_list, *fallback_list, *owned_list; int rank, world; };
+struct QQueue { int32_t* l[4]; int n[4]; int pos0[4]; int32_t *retry_list, *fallback_list, *owned_list; int rank, world; };
 
 __device__ __forceinline__ void quad_scratch_bind(const QSlots& qs, int slot, AScratch& S) {
   S.tab = nullptr; S.gq = nullptr; S.gd = nullptr; S.heap_cap = 0; S.epoch = 0;
@@ -473,7 +484,7 @@ __device__ __attribute__((noinline)) int quad_policy(const Dev& d, const TsParam
       atomicAdd((unsigned long long*)&d.cnt->astar_relax, (unsigned long long)S.relaxations);
       if (q.owned_list) q.owned_list[atomicAdd(&d.cnt->replan_n[6], 1)] = i;
     } else if (r == DV_POOL_FULL) q.retry_list[atomicAdd(&d.cnt->replan_n[4], 1)] = i;
-    else { atomicAdd(&d.cnt->dbg[r == DV_BAIL ? 5 : 6], 1); __hip_atomic_store(&q.fallback_list[atomicAdd(&d.cnt->quad_n[0], 1)], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }     // DV_BAIL, DV_OVERFLOW: k_replan takes the vehicle
+    else { atomicAdd(&qs.stats[r == DV_BAIL ? QST_BAIL : QST_OVERFLOW], 1ull); __hip_atomic_store(&q.fallback_list[atomicAdd(&d.cnt->quad_n[0], 1)], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }     // DV_BAIL, DV_OVERFLOW: k_replan takes the vehicle
   }
   return r;
 }
@@ -488,6 +499,7 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
   const bool one = j == 0;
   QQueue q;
   for (int c = 0; c < 4; c++) { q.l[c] = lists.l[c]; q.n[c] = ((class_mask >> c) & 1) ? d.cnt->replan_n[c] : 0; }
+  replan_class_pos0(d, q.pos0);
   q.retry_list = retry_list; q.fallback_list = fallback_list; q.owned_list = owned_list; q.rank = rank; q.world = world;
   const int n3 = q.n[3], n2 = q.n[2], n1 = q.n[1], n0 = q.n[0];
   QConst K;
@@ -511,6 +523,7 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
   QReq req;
   req.start = req.goal = req.soft = req.cap = 0; req.out = nullptr;
   int st = QS_NEEDJOB, job = -1, n_done = 0;
+  unsigned n_started = 0, n_wraps = 0;      // (QST_SEARCHES / QST_WRAPS of this quad: counted out once, at the end)
 #ifdef TS_QUAD_PROF
   long long pf_t0 = clock64(), pf_search = 0, pf_turns = 0, pf_quadturns = 0;
   for (int k = 0; k < 8; k++) s.pf[k] = 0;
@@ -544,7 +557,7 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
             }
           wave_mem_sync();
         }
-        if (len < 0) { st = QS_ABANDON; s.why = 4; }
+        if (len < 0) { st = QS_ABANDON; s.why = QST_PATHBUF; }
         else {
           int32_t* lg = qs.log + (size_t)slot * (3 * QLOG) + 3 * n_done;
           lg[0] = len; lg[1] = s.n_exp; lg[2] = s.n_relax;
@@ -553,7 +566,7 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
         }
       }
       if (st == QS_ABANDON) {
-        if (one) atomicAdd(&d.cnt->dbg[s.why & 7], 1);
+        if (one) atomicAdd(&qs.stats[s.why & 7], 1ull);
         if (one) __hip_atomic_store(&fallback_list[atomicAdd(&d.cnt->quad_n[0], 1)], job, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         st = QS_NEEDJOB;
       }
@@ -562,12 +575,12 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
         if (one) t = atomicAdd(&d.cnt->quad_n[1], 1);
         t = quad_first(t);
         if (t >= n3 + n2 + n1 + n0) { st = QS_IDLE; break; }
-        int i;
-        if (t < n3) i = q.l[3][t];
-        else if (t < n3 + n2) i = q.l[2][t - n3];
-        else if (t < n3 + n2 + n1) i = q.l[1][t - n3 - n2];
-        else i = q.l[0][t - n3 - n2 - n1];
-        if (world > 1 && (t % world) != rank) continue;      // (position in the totally ordered queue, as in replan_turn)
+        int i, pos;
+        if (t < n3) { i = q.l[3][t]; pos = q.pos0[3] + t; }
+        else if (t < n3 + n2) { i = q.l[2][t - n3]; pos = q.pos0[2] + t - n3; }
+        else if (t < n3 + n2 + n1) { i = q.l[1][t - n3 - n2]; pos = q.pos0[1] + t - n3 - n2; }
+        else { i = q.l[0][t - n3 - n2 - n1]; pos = q.pos0[0] + t - n3 - n2 - n1; }
+        if (world > 1 && (pos % world) != rank) continue;    // (position in the whole, totally ordered queue, as in replan_turn)
         job = i; n_done = 0;
         st = QS_POLICY;
       }
@@ -576,7 +589,9 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
         if (r != DV_SUSPEND) { st = QS_NEEDJOB; continue; }
         // ---- a fresh search (113-128): new epoch for the table, start record, one-entry heap
         epoch++;
+        n_started++;
         if (epoch > 255u) {
+          n_wraps++;
           const size_t n = qs.tab_entries;
           for (size_t t = (size_t)j; t < n; t += 4) K.tab[t] = 0u;
           epoch = 1;
@@ -625,7 +640,11 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
     for (int k = 0; k < 8; k++) atomicAdd((unsigned long long*)&d.cnt->qprof[k], (unsigned long long)s.pf[k]);
   }
 #endif
-  if (one) qs.slot_epoch[slot] = epoch;
+  if (one) {
+    qs.slot_epoch[slot] = epoch;
+    if (n_started) atomicAdd(&qs.stats[QST_SEARCHES], (unsigned long long)n_started);
+    if (n_wraps) atomicAdd(&qs.stats[QST_WRAPS], (unsigned long long)n_wraps);
+  }
   // every hand-back of this wave is published before the wave counts itself out (k_replan's replan_turn waits on both)
   __threadfence();
   if (lane == 0) atomicAdd(&d.cnt->quad_n[3], 1);

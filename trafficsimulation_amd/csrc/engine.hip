@@ -165,9 +165,14 @@ int run_quad_pass(E* e, const RLists& rl) {
   if (nq > 0) HIPOK(hipStreamWaitEvent(st, e->quad_ev1, 0));
   prof_end(e, tok);
   int qn[4] = {0, 0, 0, 0};
+  unsigned long long qst[QST_N];
   HIPOK(hipMemcpyAsync(hm.replan_n, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
   HIPOK(hipMemcpyAsync(&hm.error, &d.cnt->error, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPOK(hipMemcpyAsync(qst, e->qslots.stats, sizeof(qst), hipMemcpyDeviceToHost, st));
   TRY(read_back(e, qn, d.cnt->quad_n, sizeof(int) * 4));
+  HIPOK(hipMemsetAsync(e->qslots.stats, 0, sizeof(qst), st));
+  for (int k = 0; k < QST_N; k++) e->quad_stats[k] += (long long)qst[k];
+  e->quad_passes++;
   if (g_trace_launches) { fprintf(stderr, "[done] replanning pass with the quads\n"); fflush(stderr); }
   if (hm.error == TS_E_CAPACITY) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
   const int fb = qn[0], retry = hm.replan_n[4];
@@ -188,9 +193,14 @@ int run_quad_pass(E* e, const RLists& rl) {
   }
 #endif
   if (getenv("TS_DEBUG_REPLAN")) {
-    int dbg[8];
-    HIPOK(hipMemcpy(dbg, d.cnt->dbg, sizeof(dbg), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[replan] hand-backs so far by reason: window / g %d, heap %d, expansion budget %d, path buffer %d, policy (step-limited / contraflow search) %d, other %d\n", dbg[1], dbg[2], dbg[3], dbg[4], dbg[5], dbg[6]);
+    const long long* qs = e->quad_stats;
+    fprintf(stderr, "[replan] quad hand-backs this pass by reason: window / g %llu, heap %llu, expansion budget %llu, path buffer %llu, "
+            "policy bail (step-limited / contraflow search) %llu, policy overflow %llu; %llu searches started, %llu table-epoch wraps\n",
+            qst[QST_WINDOW], qst[QST_HEAP], qst[QST_BUDGET], qst[QST_PATHBUF], qst[QST_BAIL], qst[QST_OVERFLOW], qst[QST_SEARCHES], qst[QST_WRAPS]);
+    fprintf(stderr, "[replan] quad hand-backs so far %lld of %lld jobs: window / g %lld, heap %lld, expansion budget %lld, path buffer %lld, "
+            "policy bail %lld, policy overflow %lld; %lld searches started, %lld table-epoch wraps\n",
+            e->quad_fallbacks, e->quad_jobs, qs[QST_WINDOW], qs[QST_HEAP], qs[QST_BUDGET], qs[QST_PATHBUF], qs[QST_BAIL], qs[QST_OVERFLOW],
+            qs[QST_SEARCHES], qs[QST_WRAPS]);
     fprintf(stderr, "[replan] tick %lld: %d entries to the quads (%d waves of %d), %d to k_replan (%d waves); handed over %d, pool-full %d, %.2f ms\n",
             (long long)e->C.step_count, nq, qgrid, e->qslots.n_slots / 16, nw, wgrid, fb, retry, now_ms() - tl);
   }
@@ -2070,6 +2080,20 @@ int ts_debug_read(ts_handle e, int32_t* out8) {
     fprintf(stderr, "[kprof] top %lld | issue loads %lld | sift-down %lld | goal+stale %lld | evaluate %lld | commit stores %lld | pushes %lld | loop %lld\n", pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], pr[6], pr[7]);
   }
   return TS_OK;
+}
+
+// debugging hook (not part of include/trafficsim.h): the quad searcher's counters over this engine's quad passes, as int64 -
+// [0] entries given to k_replan_quad, [1] hand-backs to k_replan, [2 .. 7] hand-backs by reason (window / g, heap, expansion
+// budget, path buffer, policy bail, policy overflow), [8] searches started, [9] table-epoch wraps, [10] quad passes.  Writes
+// min(n, TS_QUAD_STATS_N) words and returns TS_QUAD_STATS_N.
+constexpr int TS_QUAD_STATS_N = 11;
+int ts_debug_quad_stats(ts_handle e, int64_t* out, int32_t n) {
+  if (!e || (!out && n > 0) || n < 0) return TS_E_INVALID;
+  const long long* qs = e->quad_stats;
+  const long long v[TS_QUAD_STATS_N] = {e->quad_jobs, e->quad_fallbacks, qs[QST_WINDOW], qs[QST_HEAP], qs[QST_BUDGET], qs[QST_PATHBUF],
+                                        qs[QST_BAIL], qs[QST_OVERFLOW], qs[QST_SEARCHES], qs[QST_WRAPS], e->quad_passes};
+  for (int k = 0; k < std::min<int>(n, TS_QUAD_STATS_N); k++) out[k] = v[k];
+  return TS_QUAD_STATS_N;
 }
 
 int ts_set_device(int32_t device) {
