@@ -7,7 +7,7 @@ device code only; no GPU needed):
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "trafficsimulation_amd", "csrc")
-WANT = ["k_replan", "k_replan_quad", "quad_policy", "replan_turn", "k_astar_single", "k_spawn_plan", "k_decide_main", "k_decide_pre",
+WANT = ["k_replan", "k_replan_quad", "quad_policy", "replan_turn", "k_astar_single", "k_astar_batch", "k_spawn_plan", "k_decide_main", "k_decide_pre",
         "k_move_claim", "k_move_resolve", "k_amap_build"]
 r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-pthread", "--offload-arch=gfx950", "--cuda-device-only", "-c",
                     "-o", "/dev/null", "engine.hip", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:], cwd=CSRC, capture_output=True, text=True)

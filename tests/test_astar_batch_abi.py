@@ -1,0 +1,118 @@
+"""The batched pathfinder entries (include/trafficsim_astar_batch.h) without a GPU: the header and the exported symbols, the
+oracle-backed CApi - which shares the class and has no batch entry - constructing and refusing it cleanly, and the Python
+operator `pathfinding.astar_hip_batch` (argument handling, result shape, engine cache) against the reference KATs with
+the oracle library behind it."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from trafficsimulation_amd import _capi as capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def batch_symbols():
+    src = open(os.path.join(ROOT, "include", "trafficsim_astar_batch.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", src)))
+
+
+def test_header_declares_the_batch_entries():
+    assert batch_symbols() == ["ts_astar_batch", "ts_astar_batch_device", "ts_astar_batch_fetch"]
+
+
+def test_batch_entries_stay_out_of_the_main_header():
+    src = open(os.path.join(ROOT, "include", "trafficsim.h")).read()
+    assert "astar_batch" not in re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def test_hip_library_exports_the_batch_entries():
+    import __graft_entry__ as ge
+    ge.build_hip()
+    from trafficsimulation_amd._lib import LIB_PATH
+    lib = ctypes.CDLL(LIB_PATH)
+    for s in batch_symbols():
+        assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
+
+
+def oracle_api():
+    from oracle import pyoracle
+    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
+
+
+def test_oracle_capi_still_constructs_and_refuses_batches():
+    api = oracle_api()
+    assert api.prefix == "tso_" and not api.has_astar_batch
+    for call in (lambda: api.astar_batch(np.zeros((1, 7), np.int32)), api.astar_batch_fetch, api.astar_batch_device):
+        with pytest.raises(capi.EngineError) as ex:
+            call()
+        assert ex.value.code == capi.TS_E_UNSUPPORTED
+
+
+def test_query_rows():
+    q = capi.CApi.astar_queries(np.array([[1, 2, 3, 4]]))
+    assert q.dtype == np.int32 and q.tolist() == [[1, 2, 3, 4, 0, 0, 0x7FFFFFFF]]
+    q = capi.CApi.astar_queries(np.array([[1, 2, 3, 4, 1, 0, 2 ** 40]], dtype=np.int64))
+    assert q.tolist() == [[1, 2, 3, 4, 1, 0, 0x7FFFFFFF]]
+    assert capi.CApi.astar_queries([]).shape == (0, 7)
+    with pytest.raises(ValueError):
+        capi.CApi.astar_queries(np.zeros((3, 5), np.int32))
+    with pytest.raises(ValueError):
+        capi.CApi.astar_queries(np.zeros((3, 7), np.float32))
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_batched_operator_signature(golden_dir, tag):
+    """astar_hip_batch - the reference's `astar_tensorflow_batch` signature - on every third KAT query, one call per
+    (soft, ignore_flow, maximum_steps) mode; with the oracle behind it the operator answers pair by pair."""
+    from oracle import pyoracle
+    from trafficsimulation_amd import pathfinding
+    k = np.load(os.path.join(golden_dir, "astar_kats.npz"))
+    H, W = k[f"{tag}_is_road_map"].shape
+    maps = dict(occupancy_map=k[f"{tag}_occupancy_map"], stop_map=k[f"{tag}_stop_map"], is_road_map=k[f"{tag}_is_road_map"],
+                road_type_map=k[f"{tag}_road_type_map"], allowed_dirs_map=k[f"{tag}_allowed_dirs_map"])
+    q, off, xy = k[f"{tag}_queries"], k[f"{tag}_path_off"], k[f"{tag}_path_xy"]
+    picked = list(range(0, len(q), 3))
+    modes = sorted(set((int(q[j, 4]), int(q[j, 5]), int(q[j, 6])) for j in picked))
+    assert len(modes) > 1
+    try:
+        checked = 0
+        for soft, ign, maxs in modes:
+            js = [j for j in picked if (int(q[j, 4]), int(q[j, 5]), int(q[j, 6])) == (soft, ign, maxs)]
+            got = pathfinding.astar_hip_batch(W, H, [tuple(q[j, 0:2]) for j in js], [tuple(q[j, 2:4]) for j in js],
+                                              respect_awareness=False, awareness_range=10, density_map=k[f"{tag}_density32"],
+                                              maximum_steps=maxs, ignore_flow=bool(ign), soft_obstacles=bool(soft),
+                                              _engine_factory=pyoracle.load, **maps)
+            assert isinstance(got, list) and len(got) == len(js)
+            for j, path in zip(js, got):
+                assert path == [tuple(p) for p in xy[off[j]:off[j + 1]].tolist()], f"query {j}: {q[j]}"
+                assert all(isinstance(c, tuple) and len(c) == 2 for c in path)
+            checked += len(js)
+        assert checked == len(picked)
+        assert len(pathfinding._cache) == 1
+        # the single operator finds the batched one's engine: one instance per set of static maps
+        pathfinding.astar_hip(W, H, 1, 1, 2, 2, respect_awareness=False, awareness_range=10, density_map=None,
+                              _engine_factory=pyoracle.load, **maps)
+        assert len(pathfinding._cache) == 1
+        assert pathfinding.astar_hip_batch(W, H, [], [], respect_awareness=False, awareness_range=10, density_map=None,
+                                           _engine_factory=pyoracle.load, **maps) == []
+        with pytest.raises(ValueError):
+            pathfinding.astar_hip_batch(W, H, [(1, 1), (2, 2)], [(3, 3)], respect_awareness=False, awareness_range=10,
+                                        density_map=None, _engine_factory=pyoracle.load, **maps)
+    finally:
+        pathfinding.release()
+
+
+def test_batched_operator_defaults_are_the_references():
+    import inspect
+    from trafficsimulation_amd import pathfinding
+    sig = inspect.signature(pathfinding.astar_hip_batch)
+    names = [n for n in sig.parameters if not n.startswith("_")]
+    assert names == ["width", "height", "starts", "goals", "occupancy_map", "stop_map", "is_road_map", "road_type_map",
+                     "allowed_dirs_map", "respect_awareness", "awareness_range", "density_map", "maximum_steps", "ignore_flow",
+                     "soft_obstacles"]
+    assert (sig.parameters["maximum_steps"].default, sig.parameters["ignore_flow"].default,
+            sig.parameters["soft_obstacles"].default) == (3_000, False, True)

@@ -1,0 +1,436 @@
+"""ts_astar_batch (include/trafficsim_astar_batch.h; kernels in csrc/astar_batch.h): many A* queries in one launch, against
+the reference's KATs, against the oracle beyond fixture size, and against the single-query entry ts_astar - results, counters,
+and that a batch between ticks leaves a run exactly as it was."""
+import os
+
+import numpy as np
+import pytest
+
+from trafficsimulation_amd import _capi as capi
+from trafficsimulation_amd import _lib
+from trafficsimulation_amd.world import load_trace
+from tests import test_gpu_parity as P
+from tests.test_gpu_forced_paths import small_engine
+from tests.trace_util import replay_and_compare, setup_from_trace, trace_path
+
+pytestmark = pytest.mark.gpu
+
+ASTAR_FIELDS = ("astar_calls", "astar_expansions", "astar_relaxations")
+
+
+@pytest.fixture()
+def hip():
+    api = _lib.new_engine()
+    yield api
+    api.close()
+
+
+def kat_engine(api, k, tag, params=None):
+    api.create(k[f"{tag}_allowed_dirs_map"], k[f"{tag}_is_road_map"], k[f"{tag}_road_type_map"], k[f"{tag}_intersection_map"],
+               params or api.default_params())
+    api.debug_set_occupancy(k[f"{tag}_occupancy_map"])
+    api.upload_map(capi.MAP_STOP, k[f"{tag}_stop_map"])
+    return api
+
+
+def assert_kat_batch(api, q, off, xy, ctx=""):
+    got_off, got_xy = api.astar_batch(q[:, :7])
+    assert got_off.dtype == np.int64 and got_xy.dtype == np.int32 and got_xy.shape == (got_off[-1], 2)
+    if not np.array_equal(got_off, off):
+        i = int(np.argmax(np.diff(got_off) != np.diff(off)))
+        raise AssertionError(f"{ctx}query {i} {q[i]}: path length {got_off[i + 1] - got_off[i]}, want {off[i + 1] - off[i]}")
+    if not np.array_equal(got_xy, xy):
+        c = int(np.argwhere(got_xy != xy)[0][0])
+        i = int(np.searchsorted(off, c, side="right") - 1)
+        raise AssertionError(f"{ctx}query {i} {q[i]}: path differs at cell {c - off[i]}")
+    return got_off, got_xy
+
+
+def paths_of(off, xy):
+    return [xy[off[i]:off[i + 1]].tobytes() for i in range(len(off) - 1)]
+
+
+def counters_dict(api):
+    c = api.counters()
+    return {f: getattr(c, f) for f, _ in capi.TsCounters._fields_}
+
+
+# ---- 1. the reference KATs in one launch ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_kats_in_one_launch(hip, golden_dir, tag):
+    k = np.load(os.path.join(golden_dir, "astar_kats.npz"))
+    q, off, xy = k[f"{tag}_queries"], k[f"{tag}_path_off"], k[f"{tag}_path_xy"]
+    kat_engine(hip, k, tag)
+    assert len(q) == 260
+    c0 = hip.counters().astar_calls
+    assert_kat_batch(hip, q, off, xy)
+    assert int((np.diff(off) > 0).sum()) > 50
+    assert hip.counters().astar_calls - c0 == len(q)
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_fov_kats_in_one_launch_per_range(golden_dir, tag):
+    k = np.load(os.path.join(golden_dir, "astar_fov_kats.npz"))
+    q, off, xy = k[f"{tag}_queries"], k[f"{tag}_path_off"], k[f"{tag}_path_xy"]
+    assert len(q) == 240
+    nonempty = 0
+    for aw in sorted(set(int(a) for a in q[:, 7])):
+        api = _lib.new_engine()
+        try:
+            p = api.default_params()
+            p.respect_awareness = 1
+            p.vehicle_awareness_range = aw
+            kat_engine(api, k, tag, p)
+            sel = np.flatnonzero(q[:, 7] == aw)
+            want_len = np.diff(off)[sel]
+            want_off = np.concatenate([[0], np.cumsum(want_len)]).astype(np.int64)
+            want_xy = np.concatenate([xy[off[i]:off[i + 1]] for i in sel] + [np.zeros((0, 2), np.int32)]).astype(np.int32)
+            assert_kat_batch(api, q[sel], want_off, want_xy, ctx=f"awareness {aw}: ")
+            nonempty += int((want_len > 0).sum())
+        finally:
+            api.close()
+    assert nonempty > 100
+
+
+# ---- 2. few slots, a long queue, and no trace of the order of service ------------------------------------------------------
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_three_slots_and_a_permuted_queue(monkeypatch, hip, golden_dir, tag):
+    monkeypatch.setenv("TS_ASTAR_SLOTS", "3")        # (read when the engine's first search sets its slots up)
+    k = np.load(os.path.join(golden_dir, "astar_kats.npz"))
+    q, off, xy = k[f"{tag}_queries"], k[f"{tag}_path_off"], k[f"{tag}_path_xy"]
+    kat_engine(hip, k, tag)
+    first = paths_of(*assert_kat_batch(hip, q, off, xy))
+    info = hip.debug_batch_info()
+    assert (info["slots"], info["last_waves"], info["last_usable"]) == (3, 3, 3), info      # three waves walked the 260 queries
+    rng = np.random.RandomState(5)
+    perm = np.concatenate([rng.permutation(len(q)), rng.randint(0, len(q), 40)])
+    got = paths_of(*hip.astar_batch(q[perm, :7]))
+    assert len(got) == len(q) + 40
+    for i, j in enumerate(perm):
+        assert got[i] == first[j], f"entry {i} (query {j})"
+
+
+def test_a_small_staging_arena_is_grown_and_nothing_counted_twice(monkeypatch, hip, golden_dir):
+    """The arena's first guess far too small: most paths find it full, the host grows it and queues only those again."""
+    monkeypatch.setenv("TS_DEBUG_BATCH_STAGE", "96")
+    k = np.load(os.path.join(golden_dir, "astar_kats.npz"))
+    q, off, xy = k["a_queries"], k["a_path_off"], k["a_path_xy"]
+    assert off[-1] > 96 * 4
+    kat_engine(hip, k, "a")
+    twin = kat_engine(_lib.new_engine(), k, "a")
+    try:
+        monkeypatch.delenv("TS_DEBUG_BATCH_STAGE")
+        assert_kat_batch(twin, q, off, xy)
+        monkeypatch.setenv("TS_DEBUG_BATCH_STAGE", "96")
+        for rep in range(2):
+            a0, b0 = counters_dict(hip), counters_dict(twin)
+            assert_kat_batch(hip, q, off, xy, ctx=f"pass {rep}: ")
+            assert hip.debug_batch_info()["last_passes"] == 2      # (every batch starts from the 96-cell guess again)
+            monkeypatch.delenv("TS_DEBUG_BATCH_STAGE")
+            assert_kat_batch(twin, q, off, xy)
+            assert twin.debug_batch_info()["last_passes"] == 1
+            monkeypatch.setenv("TS_DEBUG_BATCH_STAGE", "96")
+            a1, b1 = counters_dict(hip), counters_dict(twin)
+            assert a1["astar_calls"] - a0["astar_calls"] == len(q)
+            for f in ASTAR_FIELDS:
+                assert a1[f] - a0[f] == b1[f] - b0[f], f
+    finally:
+        twin.close()
+
+
+# ---- 3. the spill form of the search loop, table epochs that wrap -----------------------------------------------------------
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_smallheap_build_with_wrapping_epochs(monkeypatch, golden_dir, tag):
+    """128 heap slots in LDS and epochs that wrap after 300 searches: on 3 slots every wave walks ~87 queries of a batch, so
+    the fourth batch on one engine has every slot's table cleared and its epochs restarted inside the run."""
+    monkeypatch.setenv("TS_ASTAR_SLOTS", "3")
+    k = np.load(os.path.join(golden_dir, "astar_kats.npz"))
+    q, off, xy = k[f"{tag}_queries"], k[f"{tag}_path_off"], k[f"{tag}_path_xy"]
+    api = small_engine()
+    try:
+        kat_engine(api, k, tag)
+        for rep in range(5):
+            assert_kat_batch(api, q, off, xy, ctx=f"batch {rep}: ")
+            info = api.debug_batch_info()
+            assert (info["slots"], info["last_waves"]) == (3, 3), info      # 5 x 260 searches on 3 slots: 433 per slot on average, epochs wrap at 300
+        assert api.counters().astar_calls == 5 * len(q)
+    finally:
+        api.close()
+
+
+# ---- 4. against the oracle beyond fixture size ---------------------------------------------------------------------------
+def random_queries(tables, n, seed, reach=(12, 70, 12, 8)):
+    """n seeded queries between road cells: a quarter each strict / soft / ignore-flow / soft with a step limit of 6 or 20, the
+    endpoints at most reach[mode] cells apart per axis (strict searches stop at the first red light or vehicle and a step limit
+    at its few cells, so only short ones find anything; the soft ones cross a good part of the map); one in ten with a goal
+    that is no road cell, a few with start == goal."""
+    rng = np.random.RandomState(seed)
+    road = np.asarray(tables["is_road_map"]) == 1
+    ys, xs = np.nonzero(road)
+    nys, nxs = np.nonzero(~road)
+    q = np.zeros((n, 7), np.int32)
+    for i in range(n):
+        mode = i % 4
+        s = rng.randint(len(xs))
+        sx, sy = int(xs[s]), int(ys[s])
+        near = np.flatnonzero((np.abs(xs - sx) <= reach[mode]) & (np.abs(ys - sy) <= reach[mode]))
+        g = near[rng.randint(len(near))]
+        gx, gy = int(xs[g]), int(ys[g])
+        if i % 10 == 3:
+            g = rng.randint(len(nxs))
+            gx, gy = int(nxs[g]), int(nys[g])
+        if i % 250 == 7:
+            gx, gy = sx, sy
+        q[i] = (sx, sy, gx, gy, int(mode in (1, 3)), int(mode == 2), int(rng.choice([6, 20])) if mode == 3 else 0x7FFFFFFF)
+    return q
+
+
+def test_3000_queries_against_the_oracle_at_512():
+    import bench
+    h, c = P._pair_full(512, 12_000, 7)
+    tables, routes, _ = bench.make_workload(512, 12_000, 7)
+    h2 = bench.setup(_lib.new_engine(), tables, routes, 7, policy="full")
+    try:
+        for api in (h, c, h2):
+            api.step(12)
+        for which in (capi.MAP_OCCUPANCY, capi.MAP_STOP):
+            assert np.array_equal(h.map(which), c.map(which)) and np.array_equal(h2.map(which), c.map(which))
+        assert int((h.map(capi.MAP_OCCUPANCY) == 1).sum()) > 5_000 and int((h.map(capi.MAP_STOP) == 1).sum()) > 0
+        q = random_queries(tables, 3_000, 11)
+        before, before2 = counters_dict(h), counters_dict(h2)
+        off, xy = h.astar_batch(q)
+        nonempty = [0, 0, 0, 0]
+        for i, a in enumerate(q):
+            want = c.astar(int(a[0]), int(a[1]), int(a[2]), int(a[3]), bool(a[4]), bool(a[5]), int(a[6]))
+            assert np.array_equal(xy[off[i]:off[i + 1]], want), f"query {i}: {a}"
+            single = h2.astar(int(a[0]), int(a[1]), int(a[2]), int(a[3]), bool(a[4]), bool(a[5]), int(a[6]))
+            assert np.array_equal(single, want), f"query {i}: {a} (ts_astar)"
+            nonempty[i % 4] += len(want) > 0
+        # (the oracle's own answers: every mode finds paths, and refuses some)
+        assert sum(nonempty) > 1_000 and all(50 < m < 750 for m in nonempty), nonempty
+        after, after2 = counters_dict(h), counters_dict(h2)
+        assert after["astar_calls"] - before["astar_calls"] == 3_000
+        for f in ASTAR_FIELDS:
+            assert after[f] - before[f] == after2[f] - before2[f], f
+        print(f"3000 queries: {after['astar_expansions'] - before['astar_expansions']} expansions, {off[-1]} path cells")
+    finally:
+        for api in (h, c, h2):
+            api.close()
+
+
+# ---- 5. a batch does not disturb the run ------------------------------------------------------------------------------------
+def state_of(api):
+    return dict(maps=[api.map(w) for w in (capi.MAP_OCCUPANCY, capi.MAP_STOP, capi.MAP_STUCK)], veh=api.vehicles(), grp=api.groups(),
+                rng=[api.rng_fingerprint(capi.RNG_GLOBAL), api.rng_fingerprint(capi.RNG_SCHEDULER)])
+
+
+def assert_same_state(a, b, ctx):
+    sa, sb = state_of(a), state_of(b)
+    for i, (p, r) in enumerate(zip(sa["maps"], sb["maps"])):
+        assert np.array_equal(p, r), f"{ctx}: map {i}"
+    assert np.array_equal(sa["veh"], sb["veh"]), f"{ctx}: vehicle rows"
+    assert np.array_equal(sa["grp"], sb["grp"]), f"{ctx}: group rows"
+    assert sa["rng"] == sb["rng"], f"{ctx}: RNG states"
+
+
+def road_queries(api_or_road, n, seed):
+    road = api_or_road
+    rng = np.random.RandomState(seed)
+    ys, xs = np.nonzero(road == 1)
+    s, g = rng.randint(len(xs), size=n), rng.randint(len(xs), size=n)
+    q = np.zeros((n, 7), np.int32)
+    q[:, 0], q[:, 1], q[:, 2], q[:, 3] = xs[s], ys[s], xs[g], ys[g]
+    q[:, 4] = np.arange(n) % 2
+    q[:, 6] = 0x7FFFFFFF
+    return q
+
+
+def test_batches_between_ticks_leave_a_trace_replay_alone():
+    tr = load_trace(trace_path("full_96_s8"))
+    a, b = _lib.new_engine(), _lib.new_engine()
+    try:
+        setup_from_trace(a, tr, explicit_paths=False)
+        setup_from_trace(b, tr, explicit_paths=False)
+        q = road_queries(np.asarray(tr["is_road_map"]), 200, 3)
+        T = len(tr["veh_off"]) - 1
+        for t in range(T):
+            off, xy = b.astar_batch(q)
+            assert len(off) == 201
+            a.step(1)
+            b.step(1)
+            assert_same_state(a, b, f"tick {t}")
+            ca, cb = counters_dict(a), counters_dict(b)
+            assert cb["astar_calls"] - ca["astar_calls"] == 200 * (t + 1)
+            assert {f: v for f, v in ca.items() if f not in ASTAR_FIELDS} == {f: v for f, v in cb.items() if f not in ASTAR_FIELDS}
+        a2 = _lib.new_engine()
+        try:      # ... and the undisturbed twin is the trace's run
+            setup_from_trace(a2, tr, explicit_paths=False)
+            assert replay_and_compare(a2, tr) == T
+            assert_same_state(a, a2, "end of trace")
+        finally:
+            a2.close()
+    finally:
+        a.close()
+        b.close()
+
+
+def test_batches_while_the_quads_hold_the_table_arena(monkeypatch):
+    """The slot rule.  TS_QUAD_SLOTS=1024 makes the quads' tables alias k_replan's table arena behind the side waves' slots (as
+    in test_hip_quad_and_wave_searchers_share_the_table_arena), and with the quads on every queue the shared part is theirs
+    between most ticks.  A batch of more queries than there are side slots must then run on the side slots only - it neither
+    clears the arena nor touches the quads' tables and epochs - and the run goes on exactly as its twin's."""
+    import bench
+    monkeypatch.setenv("TS_QUAD", "1")
+    monkeypatch.setenv("TS_QUAD_MIN", "1")
+    monkeypatch.setenv("TS_QUAD_SLOTS", "1024")
+    tables, routes, _ = bench.make_workload(512, 12_000, 7)
+    a = bench.setup(_lib.new_engine(), tables, routes, 7, policy="full")
+    b = bench.setup(_lib.new_engine(), tables, routes, 7, policy="full")
+    try:
+        q = random_queries(tables, 2_000, 21)
+        held = checked = 0
+        for t in range(8):
+            a.step(1)
+            b.step(1)
+            assert_same_state(a, b, f"tick {t}")
+            now = b.debug_batch_info()
+            off, xy = b.astar_batch(q)
+            info = b.debug_batch_info()
+            assert info["arena_quad"] == now["arena_quad"] == info["last_arena_quad"], (now, info)   # a batch never moves the arena
+            if info["last_arena_quad"]:
+                assert info["arena_shared"] == 1 and 0 < info["side_slots"] < min(info["slots"], len(q)), info
+                assert info["last_usable"] == info["side_slots"] and info["last_waves"] == info["side_slots"], info
+                held += 1
+            else:
+                assert info["last_waves"] == min(len(q), info["slots"]), info
+            if t in (2, 5):      # the batch's answers are ts_astar's, on the very same state
+                for i in range(0, len(q), 23):
+                    s = a.astar(*(int(v) for v in q[i, :4]), bool(q[i, 4]), bool(q[i, 5]), int(q[i, 6]))
+                    assert np.array_equal(xy[off[i]:off[i + 1]], s), f"tick {t} query {i}"
+                    checked += 1
+        assert held >= 1 and checked > 100, (held, checked)      # at least one batch fell while the quads held the arena
+        st_a, st_b = a.debug_quad_stats(), b.debug_quad_stats()
+        assert st_b["passes"] > 0 and st_b["jobs"] > 1_000, st_b
+        assert st_a == st_b
+    finally:
+        a.close()
+        b.close()
+
+
+# ---- 6. refusals -------------------------------------------------------------------------------------------------------------
+def test_refusals(hip):
+    tr = load_trace(trace_path("full_96_s8"))
+    setup_from_trace(hip, tr, explicit_paths=False)
+    W, H = int(tr["width"]), int(tr["height"])
+    assert (W, H) == (96, 96)
+    q = road_queries(np.asarray(tr["is_road_map"]), 10, 4)
+    with pytest.raises(capi.EngineError) as ex:       # nothing has been run yet
+        hip.astar_batch_fetch()
+    assert ex.value.code == capi.TS_E_INVALID
+    off0, xy0 = hip.astar_batch(q)
+    assert off0[-1] > 0
+    c0 = counters_dict(hip)
+    bad = q.copy()
+    bad[7, 2] = W
+    with pytest.raises(capi.EngineError) as ex:
+        hip.astar_batch(bad)
+    assert ex.value.code == capi.TS_E_INVALID and "7" in str(ex.value)
+    assert counters_dict(hip) == c0
+    off1, xy1 = hip.astar_batch_fetch()
+    assert np.array_equal(off0, off1) and np.array_equal(xy0, xy1)
+    bad = q.copy()
+    bad[4, 6] = 5000
+    with pytest.raises(capi.EngineError) as ex:
+        hip.astar_batch(bad)
+    assert ex.value.code == capi.TS_E_UNSUPPORTED and "4" in str(ex.value)
+    assert counters_dict(hip) == c0
+    off1, xy1 = hip.astar_batch_fetch()
+    assert np.array_equal(off0, off1) and np.array_equal(xy0, xy1)
+    ok = q.copy()
+    ok[4, 6] = W * H          # a limit that can never bind is accepted
+    assert np.array_equal(hip.astar_batch(ok)[0], off0)
+    off, xy = hip.astar_batch(np.zeros((0, 7), np.int32))
+    assert off.tolist() == [0] and xy.shape == (0, 2)
+    hip.astar_batch(q)
+    hip.step(1)
+    with pytest.raises(capi.EngineError) as ex:
+        hip.astar_batch_fetch()
+    assert ex.value.code == capi.TS_E_INVALID
+    with pytest.raises(capi.EngineError) as ex:
+        hip.astar_batch_device()
+    assert ex.value.code == capi.TS_E_INVALID
+
+
+# ---- 7. the device result and the facade ---------------------------------------------------------------------------------
+DEVICE_SCRIPT = r'''
+import os, sys
+sys.path.insert(0, %(root)r)
+import torch                     # (first: the engine library then shares torch's HIP runtime, as under torch.distributed.run)
+torch.cuda.init()
+import numpy as np
+from trafficsimulation_amd import _capi as capi
+from trafficsimulation_amd._lib import new_engine
+k = np.load(os.path.join(%(golden)r, "astar_kats.npz"))
+api = new_engine()
+api.create(k["b_allowed_dirs_map"], k["b_is_road_map"], k["b_road_type_map"], k["b_intersection_map"], api.default_params())
+api.debug_set_occupancy(k["b_occupancy_map"])
+api.upload_map(capi.MAP_STOP, k["b_stop_map"])
+off, xy = api.astar_batch(k["b_queries"])
+assert np.array_equal(off, k["b_path_off"]) and np.array_equal(xy, k["b_path_xy"])
+d_off, d_xy = api.astar_batch_device()
+assert d_off.is_cuda and d_xy.is_cuda and d_off.dtype == torch.int64 and d_xy.dtype == torch.int32
+assert d_off.device.index == torch.cuda.current_device() and tuple(d_xy.shape) == xy.shape
+assert np.array_equal(d_off.cpu().numpy(), off) and np.array_equal(d_xy.cpu().numpy(), xy)
+lens = d_off[1:] - d_off[:-1]          # the payload is usable where it lies
+assert int(lens.sum().item()) == xy.shape[0]
+api.close()
+print("DEVICE_OK")
+'''
+
+
+def test_device_tensors(golden_dir, tmp_path):
+    """astar_batch_device(): torch tensors over the engine's own memory, equal to the fetched arrays.  In a process of its
+    own that imports torch before it loads the engine, the way the torch-side callers (dist.py) run."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / "device_tensors.py"
+    script.write_text(DEVICE_SCRIPT % dict(root=root, golden=golden_dir))
+    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+def test_facade_find_paths():
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    from run_city import TRAFFIC
+    from trafficsimulation_amd import pathfinding
+    from trafficsimulation_amd.mesa_api import CityModel
+    m = CityModel(200, 200, seed=1, traffic=dict(TRAFFIC))
+    try:
+        for _ in range(30):
+            m.step()
+        before = state_of(m.engine)
+        rng = np.random.RandomState(2)
+        ys, xs = np.nonzero(m.is_road_map == 1)
+        s, g = rng.randint(len(xs), size=60), rng.randint(len(xs), size=60)
+        starts = [(int(xs[i]), int(ys[i])) for i in s]
+        goals = [(int(xs[i]), int(ys[i])) for i in g]
+        occ, stop = m.occupancy_map.copy(), np.asarray(m.stop_map).copy()
+        for soft in (False, True):
+            got = m.find_paths(starts, goals, soft_obstacles=soft)
+            assert len(got) == 60
+            if soft:      # (a strict search across the town stops at the first red light: few of those find anything)
+                assert sum(len(p) > 0 for p in got) > 20
+            for i in range(60):
+                want = pathfinding.astar_hip(200, 200, *starts[i], *goals[i], occ, stop, m.is_road_map, m.road_type_map,
+                                             m.allowed_dirs_map, soft_obstacles=soft)
+                assert got[i] == want, f"pair {i} soft={soft}"
+        assert m.find_paths([], []) == []
+        with pytest.raises(ValueError):
+            m.find_paths(starts, goals[:-1])
+        after = state_of(m.engine)
+        assert all(np.array_equal(p, r) for p, r in zip(before["maps"], after["maps"])) and np.array_equal(before["veh"], after["veh"])
+    finally:
+        pathfinding.release()
+        m.close()

@@ -670,3 +670,100 @@ class CApi:
         n = self._chk(self._f("astar")(self.h, sx, sy, gx, gy, int(soft_obstacles), int(ignore_flow),
                                        int(maximum_steps), out.ctypes.data, cap))
         return out[:n].copy()
+
+    # ---- query batches (include/trafficsim_astar_batch.h) -------------------------------------------
+    def _batch_fn(self, name: str):
+        """The batch entries, bound on first use: the CPU oracle shares this class and answers queries one by one."""
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no batched pathfinder")
+        fn.restype = C.c_int
+        fn.argtypes = {"astar_batch": [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)],
+                       "astar_batch_fetch": [C.c_void_p, C.c_void_p, C.c_void_p],
+                       "astar_batch_device": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int64)]}[name]
+        return fn
+
+    @property
+    def has_astar_batch(self) -> bool:
+        return self.prefix == "ts_" and hasattr(self.lib, "ts_astar_batch")
+
+    @staticmethod
+    def astar_queries(queries) -> np.ndarray:
+        """(n, 7) int32 rows sx, sy, gx, gy, soft_obstacles, ignore_flow, maximum_steps from an (n, 7) or (n, 4) integer
+        array; four columns mean a strict search that respects the flow and has no step limit."""
+        q = np.asarray(queries)
+        if q.size == 0:
+            return np.zeros((0, 7), dtype=np.int32)
+        if q.ndim != 2 or q.shape[1] not in (4, 7) or not np.issubdtype(q.dtype, np.integer):
+            raise ValueError(f"queries must be an (n, 7) or (n, 4) integer array, got {q.dtype} {q.shape}")
+        out = np.zeros((q.shape[0], 7), dtype=np.int32)
+        out[:, 6] = 0x7FFFFFFF
+        out[:, :q.shape[1]] = np.clip(q, -0x80000000, 0x7FFFFFFF)      # (what int32 cannot hold stays out of bounds / unlimited)
+        return np.ascontiguousarray(out)
+
+    def astar_batch_run(self, queries) -> int:
+        """ts_astar_batch: run the queries, leave the CSR result on the device; returns the total number of path cells."""
+        fn = self._batch_fn("astar_batch")
+        q = self.astar_queries(queries)
+        total = C.c_int64()
+        self._chk(fn(self.h, q.shape[0], q.ctypes.data if q.size else None, C.byref(total)))
+        return total.value
+
+    def astar_batch_fetch(self):
+        """The last batch's result on the host: (off int64[n + 1], xy int32[total, 2])."""
+        dev = self._batch_fn("astar_batch_device")
+        n, total = C.c_int32(), C.c_int64()
+        self._chk(dev(self.h, None, None, C.byref(n), C.byref(total)))
+        off = np.zeros(n.value + 1, dtype=np.int64)
+        xy = np.zeros((total.value, 2), dtype=np.int32)
+        self._chk(self._batch_fn("astar_batch_fetch")(self.h, off.ctypes.data, xy.ctypes.data if total.value else None))
+        return off, xy
+
+    def astar_batch(self, queries):
+        """Many A* queries on the current maps in one launch -> (off int64[n + 1], xy int32[total, 2]): CSR in query order,
+        off[i]:off[i + 1] the (x, y) cells of query i's path without its start cell, empty for 'no path'.  Every query is
+        answered exactly as `astar` answers it."""
+        self.astar_batch_run(queries)
+        return self.astar_batch_fetch()
+
+    BATCH_INFO = ("slots", "side_slots", "arena_shared", "arena_quad", "last_waves", "last_usable", "last_arena_quad",
+                  "last_passes", "device")
+
+    def debug_batch_info(self) -> dict:
+        """Debugging hook (ts_debug_batch_info, not part of the headers): the searcher slots as they are now (count, the side
+        waves' share, whether the quads' tables alias the arena / hold it) and what the last query batch ran on (waves of its
+        widest launch, slots it was allowed, whether the quads held the arena then, launches it took), and the engine's device."""
+        fn = getattr(self.lib, self.prefix + "debug_batch_info", None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}debug_batch_info: this engine has no batched pathfinder")
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        out = np.zeros(len(self.BATCH_INFO), dtype=np.int32)
+        n = self._chk(fn(self.h, out.ctypes.data, len(out)))
+        assert n == len(out), f"ts_debug_batch_info reports {n} words, this wrapper knows {len(out)}"
+        return dict(zip(self.BATCH_INFO, (int(v) for v in out)))
+
+    def astar_batch_device(self, device=None):
+        """The last batch's (off, xy) as torch tensors over the engine's own device memory (no copy; valid as long as the
+        result can be fetched).  `device`: default the device the engine was created on.  torch must have been imported before
+        the engine library was loaded (as the torch-side callers in dist.py do): the two then share one HIP runtime; loaded the
+        other way round torch finds no device, and this method says so."""
+        fn = self._batch_fn("astar_batch_device")
+        try:
+            import torch
+        except ImportError as ex:
+            raise RuntimeError("astar_batch_device needs torch (use astar_batch / astar_batch_fetch for host arrays)") from ex
+        p_off, p_xy, n, total = C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int64()
+        self._chk(fn(self.h, C.byref(p_off), C.byref(p_xy), C.byref(n), C.byref(total)))
+        from .dist import ShardedReplans
+        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        try:
+            off = ShardedReplans._wrap_device(p_off.value, (n.value + 1) * 8, device).view(torch.int64)
+        except RuntimeError as ex:
+            raise RuntimeError("astar_batch_device: torch cannot reach the engine's device - import torch before the engine "
+                               "library is loaded, or fetch to the host with astar_batch_fetch") from ex
+        if total.value == 0:
+            return off, torch.zeros((0, 2), dtype=torch.int32, device=device)
+        xy = ShardedReplans._wrap_device(p_xy.value, total.value * 8, device).view(torch.int32).view(-1, 2)
+        return off, xy

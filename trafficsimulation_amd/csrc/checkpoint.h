@@ -366,6 +366,7 @@ int ts_checkpoint_save(ts_handle e, void* dst, uint64_t cap, uint64_t* written) 
 
 int ts_checkpoint_load(ts_handle e, const void* src, uint64_t n) {
   if (!e) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   if (!src && n) return fail(e, TS_E_INVALID, "checkpoint: null blob");
   if (e->dist_world > 1) return fail(e, TS_E_STATE, "checkpoint: loading onto a handle with replan sharding is not supported");
   Dev& d = e->d;

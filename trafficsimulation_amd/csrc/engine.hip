@@ -38,6 +38,7 @@
 #include "dev.h"
 #include "astar.h"
 #include "astar_quad.h"
+#include "astar_batch.h"
 #include "kernels.h"
 #include "host_state.h"
 #include "host_shuffle.h"
@@ -1360,6 +1361,7 @@ const char* ts_last_error(ts_handle h) { return h ? h->err.c_str() : "null handl
 
 int ts_set_lights(ts_handle e, const TsLightTables* t) {
   if (!e || !t || t->n_groups < 0 || t->n_lights < 0) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   if (e->lights_set) return fail(e, TS_E_STATE, "ts_set_lights may be called once");
   const int W = e->W, H = e->H, G = t->n_groups, L = t->n_lights;
   Dev& d = e->d;
@@ -1768,6 +1770,7 @@ static int add_vehicles_any(ts_handle e, int32_t n, const int32_t* start_xy, con
                             const int32_t* population_type, const int32_t* off32, const int32_t* path_xy,
                             const int64_t* off64, const uint8_t* path_dirs) {
   if (!e || n < 0 || (n > 0 && (!start_xy || !goal_xy))) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   if (n == 0) return TS_OK;
   const int W = e->W, H = e->H;
   if (!(off32 && path_xy) && !(off64 && path_dirs)) {
@@ -1841,6 +1844,7 @@ int ts_add_vehicles_dirs(ts_handle e, int32_t n, const int32_t* start_xy, const 
 
 int ts_remove_vehicle(ts_handle e, int32_t spawn_idx, int32_t population_type) {
   if (!e) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   if (population_type != TS_POP_INTERNAL && population_type != TS_POP_THROUGH) population_type = TS_POP_UNDEFINED;
   if (spawn_idx < 0 || spawn_idx >= e->n_vehicles_total) return fail(e, TS_E_INVALID, "no such live vehicle");
   Dev& d = e->d;
@@ -1858,6 +1862,7 @@ int ts_remove_vehicle(ts_handle e, int32_t spawn_idx, int32_t population_type) {
 
 int ts_upload_map(ts_handle e, int32_t which, const int8_t* src) {
   if (!e || !src) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   int8_t* m = which == TS_MAP_STOP ? e->d.stop : which == TS_MAP_RAIN ? e->d.rain : nullptr;
   if (!m) return fail(e, TS_E_INVALID, "only stop_map and rain_map are host-writable");
   HIPOK(hipMemcpy(m, src, e->N, hipMemcpyHostToDevice));
@@ -1870,6 +1875,7 @@ int ts_upload_map(ts_handle e, int32_t which, const int8_t* src) {
 }
 int ts_debug_set_occupancy(ts_handle e, const int8_t* src) {
   if (!e || !src) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   HIPOK(hipMemcpy(e->d.occ, src, e->N, hipMemcpyHostToDevice));
   e->amap_valid = false;
   hipLaunchKernelGGL(k_plane_to_cells, dim3(nblk((long long)e->N)), dim3(BLK), 0, e->stream, e->d.cell, e->N, e->d.occ, 0);
@@ -1879,6 +1885,7 @@ int ts_debug_set_occupancy(ts_handle e, const int8_t* src) {
 
 int ts_step(ts_handle e, int32_t n_ticks) {
   if (!e || n_ticks < 0) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   if (!e->rng_global.seeded() || !e->rng_sched.seeded()) return fail(e, TS_E_STATE, "both RNG streams must be seeded before step");
   if (e->groups_scheduled != e->d.G && e->d.G > 0 && e->groups_scheduled != 0)
     return fail(e, TS_E_STATE, "every light group must be scheduled (or none)");
@@ -2025,6 +2032,7 @@ int ts_group_links(ts_handle e, int32_t group, int32_t repopulate) {
 }
 int ts_add_service_vehicle(ts_handle e, int32_t x, int32_t y, int32_t service_type) {
   if (!e || x < 0 || x >= e->W || y < 0 || y >= e->H) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   if (service_type != TS_TRIP_SERVICE_FOOD && service_type != TS_TRIP_SERVICE_WASTE) return fail(e, TS_E_INVALID, "service_type");
   if (e->blocks.empty()) return fail(e, TS_E_STATE, "service vehicles need the block tables (ts_set_traffic_generator)");
   if (e->fatal) return e->fatal;
@@ -2038,6 +2046,7 @@ int ts_rain_info(ts_handle e, TsRainInfo* out) {
 }
 int ts_rain_spawn(ts_handle e) {
   if (!e) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   if (!e->rain_manager) return fail(e, TS_E_STATE, "no RainManager is scheduled");
   if (!e->rng_global.seeded()) return fail(e, TS_E_STATE, "seed the global stream first");
   HIPOK(hipStreamSynchronize(e->stream));
@@ -2122,6 +2131,7 @@ int ts_profile_get(ts_handle e, int32_t id, double* total_ms, int64_t* launches,
 int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_t soft, int32_t ignore_flow,
              int32_t maximum_steps, int32_t* out_xy, int32_t cap_cells) {
   if (!e) return TS_E_INVALID;
+  e->batch.valid = false;   // (astar_batch_api.h: the last query batch's result ends here)
   if (sx < 0 || sx >= e->W || sy < 0 || sy >= e->H || gx < 0 || gx >= e->W || gy < 0 || gy >= e->H)
     return fail(e, TS_E_INVALID, "astar endpoints out of bounds");
   if (maximum_steps < e->N && maximum_steps > A_STEPS_MAX)
@@ -2150,3 +2160,4 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
 }  // extern "C"
 
 #include "checkpoint.h"
+#include "astar_batch_api.h"

@@ -863,6 +863,25 @@ class CityModel:
             self._stop_dirty = False
             self._invalidate()
 
+    # ---- route queries on the current state (include/trafficsim_astar_batch.h) -----------------------
+    def find_paths(self, starts, goals, soft_obstacles=False, ignore_flow=False, maximum_steps=None):
+        """Routes for many (start, goal) pairs on the model's current maps, all searches in one device launch: a list with
+        one path per pair - (x, y) tuples without the start cell, [] for "no path" - each equal to what the pathfinder
+        operator (`pathfinding.astar_hip`, i.e. `astar_numba`) returns for that pair.  The simulation is not disturbed."""
+        starts = np.asarray(starts, dtype=np.int64).reshape(-1, 2) if len(starts) else np.zeros((0, 2), np.int64)
+        goals = np.asarray(goals, dtype=np.int64).reshape(-1, 2) if len(goals) else np.zeros((0, 2), np.int64)
+        if len(starts) != len(goals):
+            raise ValueError(f"starts and goals must pair up: {len(starts)} starts, {len(goals)} goals")
+        self._flush_host_writes()
+        q = np.zeros((len(starts), 7), dtype=np.int64)
+        q[:, 0:2], q[:, 2:4] = starts, goals
+        q[:, 4], q[:, 5] = int(bool(soft_obstacles)), int(bool(ignore_flow))
+        q[:, 6] = 0x7FFFFFFF if maximum_steps is None else int(min(maximum_steps, 0x7FFFFFFF))
+        off, xy = self.engine.astar_batch(q)
+        self._invalidate()          # (the A* counters moved)
+        cells = list(map(tuple, xy.tolist()))
+        return [cells[off[i]:off[i + 1]] for i in range(len(starts))]
+
     # ---- getters used by the UI (city_model.py:1965-2149) ------------------------------------------
     @property
     def active_vehicle_agents(self):

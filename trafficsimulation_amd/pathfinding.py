@@ -71,6 +71,43 @@ def astar_hip(width: int, height: int, start_x: int, start_y: int, goal_x: int, 
     return [(int(x), int(y)) for x, y in xy]
 
 
+def astar_hip_batch(width: int, height: int, starts, goals, occupancy_map: np.ndarray, stop_map: np.ndarray,
+                    is_road_map: np.ndarray, road_type_map: np.ndarray, allowed_dirs_map: np.ndarray,
+                    respect_awareness: bool, awareness_range: int, density_map: Optional[np.ndarray],
+                    maximum_steps: int = 3_000, ignore_flow: bool = False, soft_obstacles: bool = True,
+                    _engine_factory: Optional[Callable] = None) -> List[List[Tuple[int, int]]]:
+    """The reference's "many vehicles at once" operator, `astar_tensorflow_batch(width, height, starts, goals,
+    occupancy_map, stop_map, is_road_map, road_type_map, allowed_dirs_map, respect_awareness, awareness_range, density_map,
+    maximum_steps=3_000, ignore_flow=False, soft_obstacles=True)` (astar_tensorflow_batch.py:383-399): names, order and
+    defaults are its own.  `starts` / `goals` are equally long sequences of (x, y); path i (cells as (x, y) tuples, start
+    excluded, [] for "no path") answers pair i.
+
+    The search semantics are those of `astar_numba` - the only A* this build carries - so every path equals what
+    `astar_hip` returns for the same pair, flags and maps; the searches run side by side on the device
+    (`ts_astar_batch`: one launch, one wavefront per search in flight) instead of one after the other.  The caveats of
+    `astar_hip` apply: `density_map` is not read (the engine derives it from `occupancy_map`), `respect_awareness` selects
+    an engine created with that flag, a binding `maximum_steps` must not exceed 4094 (a limit of width * height or more
+    never binds and is accepted; in between raises EngineError TS_E_UNSUPPORTED), and the library must be present."""
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1, 2) if len(starts) else np.zeros((0, 2), np.int64)
+    goals = np.asarray(goals, dtype=np.int64).reshape(-1, 2) if len(goals) else np.zeros((0, 2), np.int64)
+    if len(starts) != len(goals):
+        raise ValueError(f"starts and goals must pair up: {len(starts)} starts, {len(goals)} goals")
+    api = _engine_for(width, height, is_road_map, road_type_map, allowed_dirs_map, awareness_range, _engine_factory, respect_awareness)
+    api.debug_set_occupancy(occupancy_map)          # the dynamic planes as the caller sees them right now
+    api.upload_map(capi.MAP_STOP, stop_map)
+    limit = int(min(maximum_steps, 0x7FFFFFFF))
+    if not api.has_astar_batch:
+        # an engine without the batch entry - the CPU oracle, i.e. test infrastructure: the same queries one by one
+        return [[(int(x), int(y)) for x, y in api.astar(int(s[0]), int(s[1]), int(g[0]), int(g[1]), bool(soft_obstacles),
+                                                        bool(ignore_flow), limit)] for s, g in zip(starts, goals)]
+    q = np.zeros((len(starts), 7), dtype=np.int64)
+    q[:, 0:2], q[:, 2:4] = starts, goals
+    q[:, 4], q[:, 5], q[:, 6] = int(bool(soft_obstacles)), int(bool(ignore_flow)), limit
+    off, xy = api.astar_batch(q)
+    cells = list(map(tuple, xy.tolist()))
+    return [cells[off[i]:off[i + 1]] for i in range(len(starts))]
+
+
 def release():
     """Destroy the cached engine instances (device memory of every set of static maps seen so far)."""
     for entry in _cache.values():
