@@ -1,0 +1,311 @@
+"""Expected observation planes (include/trafficsim_observe.h) from a golden trace alone - no engine.
+
+The traces were recorded from the reference, so what is computed here is the reference's data:
+
+* PRESENT, WAITING and SPEED follow from `veh_rows` tick by tick (`sampled_delta`).
+* ENTER, replay mode (`enter_replay`): for traces in which no search ever runs (trace_util.NO_ASTAR_TRACES) every vehicle
+  keeps its spawn-time path, so the vehicle with steps_traveled = s has crossed v_path0_xy[0:s] and a vehicle that vanished
+  has crossed the rest of its path.  Exact.
+* ENTER, reconstruction mode (`enter_reconstruct`): for traces with replanning a move is rebuilt per vehicle and tick from
+  its old cell, its new cell, the growth k of steps_traveled and the row's `direction` (the direction of the last step):
+  the candidate chains are all walks of k steps between 4-neighbours over drivable cells from the old to the new cell that
+  end with a step in that direction.  Drivable (`drivable`): road cells, cells that carry a flow bit and cells a flow bit
+  points at - block entrances and service cells are no road cells, and vehicles start and end on them.  A candidate is
+  singled out when the rows show that the vehicle kept its path through the tick and that path begins with it
+  (`keeps_its_path`: the cooldown and the CRCs of the path before and after).  Exactly one candidate: exact.  Several
+  candidates, or the last move of a vehicle that vanished (its new cell and k are not recorded): the candidates' cells are
+  uncertain for that tick.
+
+Planes are (H, W) arrays indexed [y, x]; ENTER planes are stacked (4, H, W) in the engine's direction order N E S W
+(N is y + 1)."""
+import numpy as np
+
+from trafficsimulation_amd import _capi as capi
+
+V = {n: i for i, n in enumerate(capi.V_FIELDS)}
+DXY = ((0, 1), (1, 0), (0, -1), (-1, 0))     # N E S W as (dx, dy)
+MAX_MOVE = 5                                  # the most cells a vehicle moves per tick unless the trace's defaults say otherwise
+
+
+def n_ticks(tr):
+    return len(tr["veh_off"]) - 1
+
+
+def rows_at(tr, t):
+    """The vehicle rows after tick t; t = -1: the state before the first tick (every vehicle at its start, nothing travelled)."""
+    if t >= 0:
+        return tr["veh_rows"][tr["veh_off"][t]:tr["veh_off"][t + 1]]
+    n = len(tr["v_start_xy"])
+    rows = np.zeros((n, len(capi.V_FIELDS)), dtype=np.int32)
+    rows[:, V["spawn_idx"]] = np.arange(n)
+    rows[:, V["x"]], rows[:, V["y"]] = tr["v_start_xy"][:, 0], tr["v_start_xy"][:, 1]
+    # the spawn-time paths are recorded: their length and CRC as a row would carry them (the cooldown starts at its reset value)
+    off, xy = tr["v_path0_off"], tr["v_path0_xy"]
+    rows[:, V["path_len"]] = np.diff(off)
+    rows[:, V["path_crc"]] = np.array([capi.path_crc(xy[off[i]:off[i + 1]]) for i in range(n)], dtype=np.uint32).view(np.int32)
+    rows[:, V["cooldown"]] = cooldown_param(tr)
+    return rows
+
+
+def sampled_delta(tr, t):
+    """(3, H, W) uint32: what tick t adds to PRESENT, WAITING and SPEED."""
+    H, W = int(tr["height"]), int(tr["width"])
+    out = np.zeros((3, H, W), dtype=np.uint32)
+    rows = rows_at(tr, t)
+    x, y = rows[:, V["x"]], rows[:, V["y"]]
+    np.add.at(out[0], (y, x), 1)
+    waiting = (rows[:, V["stuck_ticks"]] > 0) & ((rows[:, V["flags"]] & capi.F_PARKED) == 0)
+    np.add.at(out[1], (y[waiting], x[waiting]), 1)
+    np.add.at(out[2], (y, x), rows[:, V["current_speed"]].astype(np.uint32))
+    return out
+
+
+def max_move(tr):
+    d = tr["defaults_json"] if "defaults_json" in tr else {}
+    return int((d or {}).get("VEHICLE_MAX_SPEED", MAX_MOVE))
+
+
+def _dir_of(ax, ay, bx, by):
+    return DXY.index((bx - ax, by - ay))
+
+
+def enter_replay(tr, t):
+    """(4, H, W) uint32: what tick t adds to the ENTER planes, for a trace whose vehicles never replan."""
+    H, W = int(tr["height"]), int(tr["width"])
+    out = np.zeros((4, H, W), dtype=np.uint32)
+    off, xy, start = tr["v_path0_off"], tr["v_path0_xy"], tr["v_start_xy"]
+    prev, cur = rows_at(tr, t - 1), rows_at(tr, t)
+    now = {int(r[V["spawn_idx"]]): int(r[V["steps_traveled"]]) for r in cur}
+    for r in prev:
+        i, s0 = int(r[V["spawn_idx"]]), int(r[V["steps_traveled"]])
+        plen = int(off[i + 1] - off[i])
+        s1 = now.get(i, plen)       # vanished: it has crossed the rest of its path
+        assert s0 <= s1 <= plen, f"tick {t}: vehicle {i} travelled {s0} -> {s1} on a path of {plen} cells"
+        for s in range(s0, s1):
+            bx, by = (int(q) for q in xy[off[i] + s])
+            ax, ay = (int(q) for q in (xy[off[i] + s - 1] if s > 0 else start[i]))
+            out[_dir_of(ax, ay, bx, by), by, bx] += 1
+    return out
+
+
+def drivable(tr):
+    """(H, W) int8: 1 where a vehicle can stand - road cells, cells with a flow bit (allowed_dirs_map, bit d = direction d),
+    cells a flow bit points at."""
+    road = np.asarray(tr["is_road_map"]) == 1
+    allowed = np.asarray(tr["allowed_dirs_map"])
+    H, W = road.shape
+    out = road | (allowed != 0)
+    for d, (dx, dy) in enumerate(DXY):
+        ys, xs = np.nonzero(allowed >> d & 1)
+        ys, xs = ys + dy, xs + dx
+        ok = (ys >= 0) & (ys < H) & (xs >= 0) & (xs < W)
+        out[ys[ok], xs[ok]] = True
+    return out.astype(np.int8)
+
+
+def _chains(road, ax, ay, bx, by, k, last_dir):
+    """Every walk of k steps over drivable cells from (ax, ay) to (bx, by) whose last step has direction last_dir (None:
+    any), as lists of (dir, x, y)."""
+    H, W = road.shape
+    found = []
+
+    def walk(x, y, left, acc):
+        if abs(bx - x) + abs(by - y) > left:
+            return
+        if left == 0:
+            found.append(list(acc))
+            return
+        for d, (dx, dy) in enumerate(DXY):
+            if left == 1 and last_dir is not None and d != last_dir:
+                continue
+            nx, ny = x + dx, y + dy
+            if 0 <= nx < W and 0 <= ny < H and road[ny, nx] == 1:
+                acc.append((d, nx, ny))
+                walk(nx, ny, left - 1, acc)
+                acc.pop()
+
+    walk(ax, ay, k, [])
+    return found
+
+
+def _gf2_times(mat, vec):
+    out, i = 0, 0
+    while vec:
+        if vec & 1:
+            out ^= mat[i]
+        vec >>= 1
+        i += 1
+    return out
+
+
+def crc32_combine(crc1, crc2, len2):
+    """CRC-32 of A || B from crc32(A), crc32(B) and len(B) in bytes (zlib's crc32_combine: appending len2 zero bytes to A is a
+    linear map over GF(2), applied by repeated squaring)."""
+    if len2 <= 0:
+        return crc1
+    odd = [0xEDB88320] + [1 << n for n in range(31)]           # the operator for one zero bit
+    even = [_gf2_times(odd, odd[n]) for n in range(32)]         # two zero bits
+    odd = [_gf2_times(even, even[n]) for n in range(32)]        # four
+    while True:
+        even = [_gf2_times(odd, odd[n]) for n in range(32)]     # (first pass: one zero byte)
+        if len2 & 1:
+            crc1 = _gf2_times(even, crc1)
+        len2 >>= 1
+        if not len2:
+            break
+        odd = [_gf2_times(even, even[n]) for n in range(32)]
+        if len2 & 1:
+            crc1 = _gf2_times(odd, crc1)
+        len2 >>= 1
+        if not len2:
+            break
+    return crc1 ^ crc2
+
+
+def cooldown_param(tr):
+    d = tr["defaults_json"] if "defaults_json" in tr else {}
+    return int((d or {}).get("PATHFINDING_COOLDOWN", 5))
+
+
+def keeps_its_path(tr, r, c, chain):
+    """Do the rows say that the vehicle drove `chain` along the path it had before the tick?  Yes when (1) its cooldown after
+    the tick is not the value every path computation resets it to (vehicle_base.py:147), so no search replaced its path
+    inside the tick, and (2) the CRC of the path before the tick is the CRC of the chain's cells followed by the path after
+    the tick (crc32_combine: the cells of the later path are not recorded, its CRC and length are)."""
+    pc = cooldown_param(tr)
+    if pc <= 0 or int(c[V["cooldown"]]) == pc:
+        return False
+    if int(r[V["path_len"]]) != len(chain) + int(c[V["path_len"]]):
+        return False
+    head = capi.path_crc([(x, y) for _, x, y in chain])
+    return crc32_combine(head, int(c[V["path_crc"]]) & 0xFFFFFFFF, 8 * int(c[V["path_len"]])) == (int(r[V["path_crc"]]) & 0xFFFFFFFF)
+
+
+def enter_reconstruct(tr, t):
+    """What tick t adds to the ENTER planes as far as the rows tell: a dict with
+      exact      (4, H, W) uint32, the moves with exactly one candidate chain
+      uncertain  (H, W) bool, the cells of the other moves' candidates (all four planes are unknown there)
+      unc_known  cells moved in moves with several candidates (their number is known, their cells are not)
+      unc_slack  the most cells the vehicles that vanished in this tick can have moved (the least is 0)
+      moved      cells moved by the vehicles alive before and after the tick."""
+    H, W = int(tr["height"]), int(tr["width"])
+    road = drivable(tr)
+    exact = np.zeros((4, H, W), dtype=np.uint32)
+    uncertain = np.zeros((H, W), dtype=bool)
+    unc_known = unc_slack = moved = 0
+    goals = tr["v_goal_xy"]
+    prev, cur = rows_at(tr, t - 1), rows_at(tr, t)
+    now = {int(r[V["spawn_idx"]]): r for r in cur}
+    mm = max_move(tr)
+    for r in prev:
+        i, ax, ay = int(r[V["spawn_idx"]]), int(r[V["x"]]), int(r[V["y"]])
+        c = now.get(i)
+        if c is not None:
+            k = int(c[V["steps_traveled"]]) - int(r[V["steps_traveled"]])
+            assert 0 <= k, f"tick {t}: vehicle {i} travelled backwards"
+            if k == 0:
+                continue
+            moved += k
+            # (flow bits do not narrow the candidates: contraflow overtakes and detours, and searches that ignore the flow, drive
+            # against them)
+            cands = _chains(road, ax, ay, int(c[V["x"]]), int(c[V["y"]]), k, int(c[V["direction"]]))
+            if len(cands) > 1:
+                kept = [ch for ch in cands if keeps_its_path(tr, r, c, ch)]
+                if len(kept) == 1:
+                    cands = kept
+            if len(cands) == 1:
+                for d, x, y in cands[0]:
+                    exact[d, y, x] += 1
+            else:
+                unc_known += k
+                for ch in cands:
+                    for _, x, y in ch:
+                        uncertain[y, x] = True
+        else:
+            # vanished: it arrived (at its goal where the trace knows it, anywhere within reach where it does not) after
+            # at most `mm` cells, or it was removed where it stood
+            # (a vehicle that has a base speed keeps it - _choose_new_speed only rolls when it is 0 - and moves no further)
+            base = int(r[V["base_speed"]])
+            longest = 0
+            for k in range(1, (min(base, mm) if base > 0 else mm) + 1):
+                if i < len(goals):
+                    cands = _chains(road, ax, ay, int(goals[i][0]), int(goals[i][1]), k, None)
+                else:
+                    cands = _reach(road, ax, ay, k)
+                for ch in cands:
+                    longest = max(longest, k)
+                    for _, x, y in ch:
+                        uncertain[y, x] = True
+            unc_slack += longest
+    return {"exact": exact, "uncertain": uncertain, "unc_known": unc_known, "unc_slack": unc_slack, "moved": moved}
+
+
+def _reach(road, ax, ay, k):
+    """Every walk of k steps over road cells from (ax, ay), wherever it ends."""
+    H, W = road.shape
+    found = []
+
+    def walk(x, y, left, acc):
+        if left == 0:
+            found.append(list(acc))
+            return
+        for d, (dx, dy) in enumerate(DXY):
+            nx, ny = x + dx, y + dy
+            if 0 <= nx < W and 0 <= ny < H and road[ny, nx] == 1:
+                acc.append((d, nx, ny))
+                walk(nx, ny, left - 1, acc)
+                acc.pop()
+
+    walk(ax, ay, k, [])
+    return found
+
+
+def uncertainty(tr, ticks=None):
+    """(share of uncertain moved cells among all moved cells, share of ticks without an uncertain cell) over the trace."""
+    T = n_ticks(tr) if ticks is None else min(ticks, n_ticks(tr))
+    unc = total = clean = 0
+    for t in range(T):
+        e = enter_reconstruct(tr, t)
+        unc += e["unc_known"] + e["unc_slack"]
+        total += e["moved"] + e["unc_slack"]
+        clean += 0 if e["uncertain"].any() else 1
+    return unc / max(total, 1), clean / max(T, 1)
+
+
+def read_planes(api):
+    """(7, H, W) uint32: every plane of an engine observing all of them."""
+    return np.stack([api.observe_plane(n) for n in capi.OBS_PLANES])
+
+
+def group_sums(tr, planes):
+    """[G][OG_FIELDS] int64 from (7, H, W) planes and the trace's own g_*_xy tables."""
+    G = len(tr["g_icell_off"]) - 1
+    out = np.zeros((G, len(capi.OG_FIELDS)), dtype=np.int64)
+    P = {n: planes[k].astype(np.int64) for k, n in enumerate(capi.OBS_PLANES)}
+    for g in range(G):
+        for axis, key in (("ns", "g_ns_in"), ("ew", "g_ew_in")):
+            xy = tr[key + "_xy"][tr[key + "_off"][g]:tr[key + "_off"][g + 1]]
+            out[g, capi.OG_FIELDS.index(axis + "_waiting")] = P["waiting"][xy[:, 1], xy[:, 0]].sum()
+            out[g, capi.OG_FIELDS.index(axis + "_present")] = P["present"][xy[:, 1], xy[:, 0]].sum()
+        xy = tr["g_icell_xy"][tr["g_icell_off"][g]:tr["g_icell_off"][g + 1]]
+        for n in capi.OBS_ENTER:
+            out[g, capi.OG_FIELDS.index(n)] = P[n][xy[:, 1], xy[:, 0]].sum()
+    return out
+
+
+def pooled(plane, f):
+    """numpy twin of ts_observe_pooled."""
+    H, W = plane.shape
+    oh, ow = -(-H // f), -(-W // f)
+    pad = np.zeros((oh * f, ow * f), dtype=np.uint64)
+    pad[:H, :W] = plane
+    return pad.reshape(oh, f, ow, f).sum(axis=(1, 3))
+
+
+def region_sums(plane, rects):
+    H, W = plane.shape
+    out = []
+    for x0, y0, x1, y1 in rects:
+        x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, W), min(y1, H)
+        out.append(int(plane[y0:y1, x0:x1].astype(np.uint64).sum()) if x1 > x0 and y1 > y0 else 0)
+    return np.asarray(out, dtype=np.uint64)

@@ -84,6 +84,17 @@ class TsRainInfo(C.Structure):
     _fields_ = [("has_manager", C.c_int32), ("n_rains", C.c_int32), ("cooldown", C.c_int32), ("counter", C.c_int32)]
 
 
+# include/trafficsim_observe.h: plane indices and the fields of ts_observe_groups
+OBS_PLANES = ["present", "waiting", "speed", "enter_n", "enter_e", "enter_s", "enter_w"]
+OBS_ENTER = OBS_PLANES[3:]
+OG_FIELDS = ["ns_waiting", "ns_present", "ew_waiting", "ew_present", "enter_n", "enter_e", "enter_s", "enter_w"]
+
+
+class TsObserveInfo(C.Structure):
+    _fields_ = [("plane_mask", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("ticks", C.c_int64),
+                ("device_bytes", C.c_uint64)]
+
+
 class TsCounters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "stuck", "collisions", "malfunctions", "overtaking", "in_stuck_detour", "parked", "live_internal",
@@ -726,6 +737,118 @@ class CApi:
         answered exactly as `astar` answers it."""
         self.astar_batch_run(queries)
         return self.astar_batch_fetch()
+
+    # ---- traffic observation (include/trafficsim_observe.h) ------------------------------------------
+    def _obs_fn(self, name: str):
+        """The observation entries, bound on first use: the CPU oracle shares this class and has none of them."""
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no traffic observation")
+        fn.restype = C.c_int
+        fn.argtypes = {"observe_start": [C.c_void_p, C.c_uint32],
+                       "observe_stop": [C.c_void_p],
+                       "observe_reset": [C.c_void_p],
+                       "observe_info": [C.c_void_p, C.POINTER(TsObserveInfo)],
+                       "observe_download": [C.c_void_p, C.c_int32, C.c_void_p],
+                       "observe_pooled": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+                       "observe_regions": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+                       "observe_groups": [C.c_void_p, C.c_void_p],
+                       "observe_device": [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]}[name]
+        return fn
+
+    @property
+    def has_observe(self) -> bool:
+        return self.prefix == "ts_" and hasattr(self.lib, "ts_observe_start")
+
+    @staticmethod
+    def _obs_plane(name) -> int:
+        if isinstance(name, str):
+            if name not in OBS_PLANES:
+                raise ValueError(f"unknown observation plane {name!r} (one of {', '.join(OBS_PLANES)})")
+            return OBS_PLANES.index(name)
+        return int(name)
+
+    def observe_start(self, planes=None):
+        """Allocate and zero the named planes (default: all of OBS_PLANES; names, indices or a ready bit mask) and observe from
+        the next tick on.  Starting again re-allocates and zeroes."""
+        fn = self._obs_fn("observe_start")
+        if planes is None:
+            mask = (1 << len(OBS_PLANES)) - 1
+        elif isinstance(planes, (int, np.integer)):
+            mask = int(planes)
+        else:
+            mask = 0
+            for p in ([planes] if isinstance(planes, str) else planes):
+                mask |= 1 << self._obs_plane(p)
+        if not 0 <= mask <= 0xFFFFFFFF:
+            raise ValueError(f"plane mask {mask} does not fit 32 bits")
+        self._chk(fn(self.h, mask))
+
+    def observe_stop(self):
+        self._chk(self._obs_fn("observe_stop")(self.h))
+
+    def observe_reset(self):
+        """Zero the planes and the tick count."""
+        self._chk(self._obs_fn("observe_reset")(self.h))
+
+    def observe_info(self) -> dict:
+        """{"planes": names held, "mask", "ticks", "width", "height", "device_bytes"}; no planes when observation is off."""
+        info = TsObserveInfo()
+        self._chk(self._obs_fn("observe_info")(self.h, C.byref(info)))
+        return {"planes": [n for k, n in enumerate(OBS_PLANES) if info.plane_mask >> k & 1], "mask": int(info.plane_mask),
+                "ticks": int(info.ticks), "width": int(info.width), "height": int(info.height),
+                "device_bytes": int(info.device_bytes)}
+
+    def observe_plane(self, name) -> np.ndarray:
+        """One whole plane as an (H, W) uint32 array."""
+        out = np.zeros((self.H, self.W), dtype=np.uint32)
+        self._chk(self._obs_fn("observe_download")(self.h, self._obs_plane(name), out.ctypes.data))
+        return out
+
+    def observe_pooled(self, name, factor: int) -> np.ndarray:
+        """The plane summed over factor x factor blocks on the device: (ceil(H / factor), ceil(W / factor)) uint64."""
+        fn = self._obs_fn("observe_pooled")
+        f = int(factor)
+        out = np.zeros((-(-self.H // f), -(-self.W // f)) if f >= 1 else (1, 1), dtype=np.uint64)
+        self._chk(fn(self.h, self._obs_plane(name), max(min(f, 0x7FFFFFFF), -1), out.ctypes.data))
+        return out
+
+    def observe_regions(self, name, rects) -> np.ndarray:
+        """Sums of the plane over rectangles (x0, y0, x1, y1), half-open, clipped to the map: uint64 [n]."""
+        fn = self._obs_fn("observe_regions")
+        r = np.ascontiguousarray(np.clip(np.asarray(rects, dtype=np.int64).reshape(-1, 4), -0x80000000, 0x7FFFFFFF), dtype=np.int32)
+        out = np.zeros(len(r), dtype=np.uint64)
+        self._chk(fn(self.h, self._obs_plane(name), len(r), r.ctypes.data if len(r) else None, out.ctypes.data if len(r) else None))
+        return out
+
+    def observe_groups(self) -> np.ndarray:
+        """[G][OG_FIELDS] int64: WAITING and PRESENT over every light group's ns_in / ew_in cells, the four ENTER planes
+        over its intersection cells."""
+        fn = self._obs_fn("observe_groups")
+        n = self._chk(self._f("num_groups")(self.h))
+        out = np.zeros((max(n, 1), len(OG_FIELDS)), dtype=np.int64)
+        self._chk(fn(self.h, out.ctypes.data))
+        return out[:n]
+
+    def observe_device(self, name, device=None):
+        """A plane as an (H, W) int32 torch tensor over the engine's own device memory (no copy; the bits are the plane's
+        uint32 counts; valid until observe_stop, the next observe_start or close).  torch must have been imported before the
+        engine library was loaded, as for astar_batch_device."""
+        fn = self._obs_fn("observe_device")
+        try:
+            import torch
+        except ImportError as ex:
+            raise RuntimeError("observe_device needs torch (use observe_plane for a host array)") from ex
+        ptr = C.c_void_p()
+        self._chk(fn(self.h, self._obs_plane(name), C.byref(ptr)))
+        from .dist import ShardedReplans
+        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        try:
+            t = ShardedReplans._wrap_device(ptr.value, self.W * self.H * 4, device)
+        except RuntimeError as ex:
+            raise RuntimeError("observe_device: torch cannot reach the engine's device - import torch before the engine "
+                               "library is loaded, or download with observe_plane") from ex
+        return t.view(torch.int32).view(self.H, self.W)
 
     BATCH_INFO = ("slots", "side_slots", "arena_shared", "arena_quad", "last_waves", "last_usable", "last_arena_quad",
                   "last_passes", "device")

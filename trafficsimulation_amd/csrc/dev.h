@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/trafficsim.h"
+#include "../../include/trafficsim_observe.h"
 
 #define BLK 256
 
@@ -144,6 +145,10 @@ struct Dev {
   uint32_t* words;      // ring mirror of the global MT19937 stream (tempered words), index = absolute & WORDS_MASK
   uint32_t *Cx, *rollrank, *rollD, *Tcum;
   DevCnt* cnt;
+  // traffic observation (observe.h): one separate uint32 plane per TS_OBS_* index, nullptr = not observed.  obs_enter is
+  // any of the four ENTER planes that is held (nullptr: none) - the one test the move kernel makes.
+  uint32_t* obs[TS_OBS_NPLANES];
+  uint32_t* obs_enter;
 };
 
 __device__ __forceinline__ int path_dir(const uint32_t* pool, uint32_t off, int k) {

@@ -39,6 +39,7 @@
 #include "astar.h"
 #include "astar_quad.h"
 #include "astar_batch.h"
+#include "observe.h"
 #include "kernels.h"
 #include "host_state.h"
 #include "host_shuffle.h"
@@ -1139,6 +1140,13 @@ int tick(E* e) {
   host_prof(e, PH_MOVE_WALL, now_ms() - t_move0, ts.nS);
   if (e->clock_slot >= 0 && !e->gen.armed) e->C.elapsed += P.time_per_step_seconds;  // an armed generator did it in its step
   e->C.step_count++;
+  // traffic observation (observe.h): the tick's ENTER increments were made by the move kernel; sample the live vehicles where
+  // they stand now (the lists are compacted: exactly the rows ts_download_vehicles would return)
+  if (e->obs_mask) {
+    if ((e->obs_mask & OBS_SAMPLED) && e->n_active > 0)
+      hipLaunchKernelGGL(k_obs_sample, dim3(nblk(e->n_active)), dim3(BLK), 0, st, d, e->n_active);
+    e->obs_ticks++;
+  }
   if (e->prof) { HIPOK(hipStreamSynchronize(st)); prof_collect(e); }
   return TS_OK;
 }
@@ -2161,3 +2169,4 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
 
 #include "checkpoint.h"
 #include "astar_batch_api.h"
+#include "observe_api.h"

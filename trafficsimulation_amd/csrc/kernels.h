@@ -279,6 +279,7 @@ __device__ __forceinline__ void vehicle_step_dev(const Dev& d, const TsParams& P
             set_occ(d, c, 0); set_occ(d, nc, 1);
             d.cell[c].stuck = 0; d.cell[nc].stuck = (k == 0 && was_stuck) ? 1 : 0;
             lastdir = nc == c + d.W ? 0 : nc == c + 1 ? 1 : nc == c - d.W ? 2 : 3;
+            if (d.obs_enter) obs_enter_dev(d, lastdir, nc);
             c = nc; moved++;
           }
         }
@@ -293,6 +294,7 @@ __device__ __forceinline__ void vehicle_step_dev(const Dev& d, const TsParams& P
         if (ncell.stop == 1 && k != m - 1) break;
         set_occ(d, c, 0); set_occ(d, nc, 1);
         d.cell[c].stuck = 0; d.cell[nc].stuck = (k == 0 && was_stuck) ? 1 : 0;
+        if (d.obs_enter) obs_enter_dev(d, nd, nc);
         c = nc; moved++; lastdir = nd;
       }
     }

@@ -882,6 +882,46 @@ class CityModel:
         cells = list(map(tuple, xy.tolist()))
         return [cells[off[i]:off[i + 1]] for i in range(len(starts))]
 
+    # ---- traffic observation (include/trafficsim_observe.h) ------------------------------------------
+    def observe(self, planes=None):
+        """Start accumulating per-cell observation planes on the device (default: all of `capi.OBS_PLANES`), from the next
+        step on; `planes=()` or False stops it.  Observation changes nothing the run computes and is not carried by save /
+        load / deepcopy / pickle: the model those give has observation off."""
+        if planes is False or (isinstance(planes, (list, tuple)) and len(planes) == 0):
+            self.engine.observe_stop()
+        else:
+            self.engine.observe_start(planes)
+
+    def observations(self) -> dict:
+        """{plane name: (H, W) uint32} for the planes held, plus "ticks"; with the four ENTER planes also "flow" (their sum,
+        uint64: how often a vehicle entered the cell), with SPEED and PRESENT also "mean_speed" (float64, NaN where no
+        vehicle was ever seen)."""
+        info = self.engine.observe_info()
+        out = {name: self.engine.observe_plane(name) for name in info["planes"]}
+        if all(n in out for n in capi.OBS_ENTER):
+            out["flow"] = sum(out[n].astype(np.uint64) for n in capi.OBS_ENTER)
+        if "speed" in out and "present" in out:
+            present = out["present"].astype(np.float64)
+            out["mean_speed"] = np.divide(out["speed"].astype(np.float64), present, out=np.full(present.shape, np.nan), where=present > 0)
+        out["ticks"] = info["ticks"]
+        return out
+
+    def intersection_report(self) -> List[dict]:
+        """Per light group, over the ticks observed: vehicle-ticks waiting on the N-S and on the W-E approaches (and the
+        vehicle-ticks present there), and the throughput - entries into the intersection's cells, in all and by direction."""
+        rows = self.engine.observe_groups()
+        ticks = self.engine.observe_info()["ticks"]
+        f = capi.OG_FIELDS.index
+        out = []
+        for g, r in enumerate(rows):
+            by_dir = {d: int(r[f("enter_" + d.lower())]) for d in "NESW"}
+            out.append({"group": self.intersection_light_groups[g].id if g < len(self.intersection_light_groups) else g,
+                        "index": g, "ticks": ticks,
+                        "waiting_ns": int(r[f("ns_waiting")]), "waiting_ew": int(r[f("ew_waiting")]),
+                        "present_ns": int(r[f("ns_present")]), "present_ew": int(r[f("ew_present")]),
+                        "throughput": sum(by_dir.values()), "throughput_by_direction": by_dir})
+        return out
+
     # ---- getters used by the UI (city_model.py:1965-2149) ------------------------------------------
     @property
     def active_vehicle_agents(self):
