@@ -8,7 +8,8 @@ tests/golden/*.npz:
 
   G1  world tables  (static maps, light-group tables, schedule layout, entrances/exits)
   G2  A* known-answer tests (astar_numba.py:243-281, all (soft, ignore_flow) modes)
-  G3  density map (city_model.py:1764-1778, real scipy.ndimage.uniform_filter)
+  G3  density map (city_model.py:1764-1778, real scipy.ndimage.uniform_filter), at r = 10 and at other radii
+  G2c A* known-answer tests under moved cost constants (COST_SETS; one process per set)
   G4  MT19937 streams from CPython's own `random` (random(), randint(1,5), shuffle)
   G5  per-tick traces of CityModel.step() (maps, per-vehicle tuples, RNG fingerprints)
   G6  per-tick light-group controller state
@@ -41,6 +42,58 @@ GATED = dict(PATHFINDING_COOLDOWN=10 ** 9, VEHICLE_STUCK_RECOMPUTE_THRESHOLD=10 
 CLOSED = dict(RAIN_ENABLED=False, INTERNAL_POPULATION_TRAFFIC_PER_DAY=0,
               PASSING_POPULATION_TRAFFIC_PER_DAY=0, TOTAL_SERVICE_VEHICLES_FOOD=0,
               TOTAL_SERVICE_VEHICLES_WASTE=0)
+
+# --------------------------------------------------------------------------------------
+# A* cost-constant sets (job astar_cost_kats; two of them also drive a trace each)
+# --------------------------------------------------------------------------------------
+# config.py's own values of every constant astar_numba.py binds at import (lines 11-24), plus the density window's radius
+COST_DEFAULTS = dict(VEHICLE_CONTRAFLOW_PENALTY=5000, VEHICLE_OBSTACLE_PENALTY_VEHICLE=1000, VEHICLE_OBSTACLE_PENALTY_STOP=500,
+                     VEHICLE_ROAD_TYPES_PENALTIES_ENABLED=True, VEHICLE_ROAD_TYPES_PENALTY_R1=0.5,
+                     VEHICLE_ROAD_TYPES_PENALTY_R2=5, VEHICLE_ROAD_TYPES_PENALTY_R3=50.0, VEHICLE_TURN_PENALTY_ENABLED=True,
+                     VEHICLE_TURN_PENALTY=10, VEHICLE_DYNAMIC_PENALTIES_ENABLED=True, VEHICLE_DYNAMIC_PENALTY_SCALE=4.0,
+                     VEHICLE_AWARENESS_RANGE=10)
+# astar_numba's module constant for each of them
+COST_MODULE_NAMES = dict(VEHICLE_CONTRAFLOW_PENALTY="CONTRA_PENALTY", VEHICLE_OBSTACLE_PENALTY_VEHICLE="VEHICLE_PENALTY",
+                         VEHICLE_OBSTACLE_PENALTY_STOP="STOP_PENALTY", VEHICLE_ROAD_TYPES_PENALTIES_ENABLED="ROAD_TYPES_PENALTY_ENABLED",
+                         VEHICLE_ROAD_TYPES_PENALTY_R1="ROAD_TYPES_PENALTY_R1", VEHICLE_ROAD_TYPES_PENALTY_R2="ROAD_TYPES_PENALTY_R2",
+                         VEHICLE_ROAD_TYPES_PENALTY_R3="ROAD_TYPES_PENALTY_R3", VEHICLE_TURN_PENALTY_ENABLED="VEHICLE_TURN_PENALTY_ENABLED",
+                         VEHICLE_TURN_PENALTY="VEHICLE_TURN_PENALTY", VEHICLE_DYNAMIC_PENALTIES_ENABLED="VEHICLE_DYNAMIC_PENALTIES_ENABLED",
+                         VEHICLE_DYNAMIC_PENALTY_SCALE="VEHICLE_DYNAMIC_PENALTY_SCALE")
+# name -> defaults: the overrides; half: the form the engine's searches must take (all penalties multiples of 0.5, scale <= 64,
+# veh * (1 + scale) * 2 < 2^21); occupancy: "base" = run_astar_kats' draw (1/8 of the road cells), "dense" = 1/4 of them;
+# may_coincide: exempt from the "10 % of the paths differ from the defaults' paths" condition, with the reason
+COST_SETS = {
+    "ints": dict(half=True, occupancy="base", defaults=dict(
+        VEHICLE_TURN_PENALTY=3, VEHICLE_CONTRAFLOW_PENALTY=700, VEHICLE_OBSTACLE_PENALTY_VEHICLE=100, VEHICLE_OBSTACLE_PENALTY_STOP=50,
+        VEHICLE_ROAD_TYPES_PENALTY_R1=2, VEHICLE_ROAD_TYPES_PENALTY_R2=0, VEHICLE_ROAD_TYPES_PENALTY_R3=9)),
+    "flags_off": dict(half=True, occupancy="base", may_coincide="no exemption needed in practice, but a map whose cheapest routes are "
+                      "also its shortest and straightest ones answers the same with and without the three penalties",
+                      defaults=dict(VEHICLE_TURN_PENALTY_ENABLED=False, VEHICLE_ROAD_TYPES_PENALTIES_ENABLED=False,
+                                    VEHICLE_DYNAMIC_PENALTIES_ENABLED=False)),
+    "turn0": dict(half=True, occupancy="base", may_coincide="a turn costs 0 instead of 10: only routes that traded a turn for a "
+                  "detour of < 10 change", defaults=dict(VEHICLE_TURN_PENALTY_ENABLED=True, VEHICLE_TURN_PENALTY=0)),
+    "quarter": dict(half=False, occupancy="base", defaults=dict(
+        VEHICLE_ROAD_TYPES_PENALTY_R1=2.25, VEHICLE_ROAD_TYPES_PENALTY_R2=0.75, VEHICLE_ROAD_TYPES_PENALTY_R3=9.25)),
+    # veh 320, not 333: 333 * 0.3 * d = 99.9 d is a whole number only for d a multiple of 10/999, which no float32 in (0, 1] is,
+    # so with 333 the truncation cases this set is here for cannot exist; 320 * 0.3 = 96 makes every density k/32 one
+    "nondyadic": dict(half=False, occupancy="dense", whole_cells=20, defaults=dict(
+        VEHICLE_ROAD_TYPES_PENALTY_R1=0.3, VEHICLE_ROAD_TYPES_PENALTY_R2=1.7, VEHICLE_ROAD_TYPES_PENALTY_R3=12.1,
+        VEHICLE_DYNAMIC_PENALTY_SCALE=0.3, VEHICLE_OBSTACLE_PENALTY_VEHICLE=320, VEHICLE_AWARENESS_RANGE=6)),
+    "scale_half": dict(half=True, occupancy="dense", whole_cells=20, defaults=dict(
+        VEHICLE_DYNAMIC_PENALTY_SCALE=0.3, VEHICLE_OBSTACLE_PENALTY_VEHICLE=1000, VEHICLE_AWARENESS_RANGE=3)),
+    "switch_lo": dict(half=True, occupancy="base", may_coincide="both sides of the switch run the same cost model, and the two "
+                      "scales price an occupied cell alike up to 0.8 %", defaults=dict(VEHICLE_DYNAMIC_PENALTY_SCALE=64.0, VEHICLE_OBSTACLE_PENALTY_VEHICLE=100)),
+    "switch_hi": dict(half=False, occupancy="base", may_coincide="as switch_lo",
+                      defaults=dict(VEHICLE_DYNAMIC_PENALTY_SCALE=64.5, VEHICLE_OBSTACLE_PENALTY_VEHICLE=100)),
+    "field_edge": dict(half=True, occupancy="base", defaults=dict(VEHICLE_DYNAMIC_PENALTY_SCALE=64.0, VEHICLE_OBSTACLE_PENALTY_VEHICLE=16000)),
+}
+ASTAR_INF = 0x3F3F3F3F
+
+
+def cost_constants(name):
+    """Every constant of COST_DEFAULTS under the set `name` ("defaults" = config.py untouched)."""
+    return {**COST_DEFAULTS, **(COST_SETS[name]["defaults"] if name != "defaults" else {})}
+
 
 SCENARIOS = {
     # config-2 style: car-following + move only (lights disabled, replans gated off)
@@ -148,6 +201,18 @@ SCENARIOS = {
                                              "PASSING_POPULATION_TRAFFIC_PER_DAY": 2000, "TOTAL_SERVICE_VEHICLES_FOOD": 3000,
                                              "TOTAL_SERVICE_VEHICLES_WASTE": 3000, "SERVICE_VEHICLE_LOAD_TIME": 1,
                                              "SERVICE_VEHICLE_MAX_LOAD_FOOD": 50, "PATHFINDING_BATCHING": False}),
+    # the shape of full_96_s8 with the A* cost constants moved (COST_SETS below): every search of a live run - spawn, replans,
+    # soft retries, contraflow detours - under non-default penalties.  PATHFINDING_COOLDOWN 2 and a stuck threshold of 10 make
+    # vehicles replan (and fall back to soft searches) several times as often as the defaults do, so that ~80 ticks record
+    # a few hundred searches beyond the spawn-time ones.
+    # ... all-integer penalties (half-unit searches, the only form the quad searcher runs) and a density window of r = 6
+    "costs_int_96_s31": dict(size=96, seed=31, vehicles=250, ticks=80,
+                             defaults={**CLOSED, **COST_SETS["ints"]["defaults"], "VEHICLE_AWARENESS_RANGE": 6,
+                                       "PATHFINDING_COOLDOWN": 2, "VEHICLE_STUCK_RECOMPUTE_THRESHOLD": 10}),
+    # ... non-dyadic road-type penalties and scale: searches in doubles, costs stored truncated
+    "costs_frac_96_s32": dict(size=96, seed=32, vehicles=250, ticks=80,
+                              defaults={**CLOSED, **COST_SETS["nondyadic"]["defaults"],
+                                        "PATHFINDING_COOLDOWN": 2, "VEHICLE_STUCK_RECOMPUTE_THRESHOLD": 10}),
 }
 
 
@@ -689,9 +754,220 @@ def run_astar_fov_kats():
     np.savez_compressed(os.path.join(HERE, "astar_fov_kats.npz"), **out)
 
 
-def run_density():
+def _cost_world(m, size, seed, occupancy):
+    """The dynamic state of run_astar_kats on a fresh world (same draws from the same stream): occupancy on 1/8 of the road
+    cells, red on about half of the lights; "dense" adds cells from a stream of its own until 1/4 of the road is occupied.
+    Returns (road cells, the stream, positioned where run_astar_kats draws its queries)."""
+    import random
+    prng = random.Random(seed * 7)
+    road = [(x, y) for y in range(size) for x in range(size) if m.is_road_map[y, x] == 1]
+    base = prng.sample(road, len(road) // 8)
+    for (x, y) in base:
+        m.occupancy_map[y, x] = 1
+    for tl in m.traffic_lights:
+        if prng.random() < 0.5:
+            tl.set_light_stop()
+    if occupancy == "dense":
+        taken = set(base)
+        rest = [c for c in road if c not in taken]
+        for (x, y) in random.Random(seed * 11).sample(rest, len(road) // 4 - len(base)):
+            m.occupancy_map[y, x] = 1
+    else:
+        assert occupancy == "base", occupancy
+    return road, prng
+
+
+def run_astar_cost_set(name, occupancy, out_path):
+    """One set of constants (or "defaults") in a process of its own: astar_numba.py binds its constants when it is imported."""
+    import numpy as np
+    from fractions import Fraction
+    _setup_paths()
+    import random
+    from Simulation.config import Defaults
+    Defaults.SAVE_TOTAL_RESULTS = False
+    Defaults.SAVE_INDIVIDUAL_RESULTS = False
+    for k, v in CLOSED.items():
+        setattr(Defaults, k, v)
+    consts = cost_constants(name)
+    for k, v in consts.items():
+        assert hasattr(Defaults, k), k
+        if name == "defaults":
+            assert getattr(Defaults, k) == v, (k, getattr(Defaults, k), v)      # COST_DEFAULTS is config.py's
+        setattr(Defaults, k, v)
+    from Simulation.city_model import CityModel
+    import importlib
+    an = importlib.import_module("Simulation.utilities.pathfinding.astar_numba")    # (the package rebinds the name to the function)
+    for k, mod_name in COST_MODULE_NAMES.items():
+        got = getattr(an, mod_name)
+        assert got == consts[k] and type(got) is type(consts[k]), (mod_name, got, consts[k])
+    aw = consts["VEHICLE_AWARENESS_RANGE"]
+    turn = consts["VEHICLE_TURN_PENALTY"] if consts["VEHICLE_TURN_PENALTY_ENABLED"] else 0
+    rmax = max(consts[f"VEHICLE_ROAD_TYPES_PENALTY_R{i}"] for i in (1, 2, 3)) if consts["VEHICLE_ROAD_TYPES_PENALTIES_ENABLED"] else 0
+    veh, scale = consts["VEHICLE_OBSTACLE_PENALTY_VEHICLE"], consts["VEHICLE_DYNAMIC_PENALTY_SCALE"]
+    dyn = consts["VEHICLE_DYNAMIC_PENALTIES_ENABLED"]
+    out = {}
+    for tag, size, seed, kw in (("a", 64, 21, {}), ("b", 80, 22, dict(carve_subblock_roads=True))):
+        random.seed(seed)
+        m = CityModel(width=size, height=size, seed=seed, **kw)
+        road, prng = _cost_world(m, size, seed, occupancy)
+        m._update_density_map()
+        assert Defaults.VEHICLE_AWARENESS_RANGE == aw
+        d32 = m.density_map.astype(np.float32)
+        dens64 = m.density_map.astype(np.float64)
+        occ_cells = [(x, y) for (x, y) in road if m.occupancy_map[y, x] == 1]
+        # no cost can reach INF: the costs along any chain of relaxations belong to distinct cells (a cell is only entered
+        # again at a smaller cost, and every step costs >= 1), so a cost is at most the sum over the cells of the map of the
+        # largest cost of entering each.  (The cruder "largest step x cells" is printed beside it; field_edge exceeds that.)
+        occ_pen = [int(veh * (1.0 + scale * float(dens64[y, x]))) if dyn else veh for (x, y) in occ_cells]
+        step_flat = 1 + turn + consts["VEHICLE_CONTRAFLOW_PENALTY"] + consts["VEHICLE_OBSTACLE_PENALTY_STOP"] + rmax
+        bound = size * size * step_flat + sum(occ_pen)
+        crude = size * size * (step_flat + max(occ_pen))
+        assert bound < ASTAR_INF, (name, tag, bound)
+        # occupied cells whose penalty veh * (1 + scale * density) is a whole number in exact arithmetic (scale as the decimal
+        # it is written as, density as the float32 it is stored as): in doubles it lands an ulp either side, int() decides
+        sc = Fraction(str(scale))
+        whole = sum(1 for (x, y) in occ_cells if (veh * (1 + sc * Fraction(float(d32[y, x])))).denominator == 1) if dyn else 0
+        queries, paths, poff = [], [], [0]
+        nq = 100
+        # (a strict search whose goal cell is occupied or red fails whatever the constants are: strict queries go to free cells)
+        free = [(x, y) for (x, y) in road if m.occupancy_map[y, x] == 0 and m.stop_map[y, x] == 0]
+        for q in range(nq):
+            mode = q % 4
+            soft, ign = bool(mode & 1), bool(mode & 2)
+            (sx, sy), (gx, gy) = prng.choice(road), prng.choice(road if soft else free)
+            maxs = 0x7FFFFFFF
+            if ign:
+                maxs = prng.choice([6, 20, 0x7FFFFFFF])
+                if maxs != 0x7FFFFFFF:      # bounded searches: pick a nearby goal (one the step limit does not rule out by itself)
+                    cands = [(x, y) for (x, y) in (road if soft else free) if 0 < abs(x - sx) + abs(y - sy) <= min(8, maxs)]
+                    if cands:
+                        gx, gy = prng.choice(cands)
+            elif not soft and (q // 4) % 4 != 3:
+                # strict searches that respect the flow: with 1/8 of the road occupied and half of the lights red nearly every
+                # long route is blocked, so three in four of them go to a goal within 10 cells
+                cands = [(x, y) for (x, y) in free if 0 < abs(x - sx) + abs(y - sy) <= 10]
+                if cands:
+                    gx, gy = prng.choice(cands)
+            p = an.astar_numba(size, size, sx, sy, gx, gy, m.occupancy_map, m.stop_map, m.is_road_map,
+                               m.road_type_map, m.allowed_dirs_map, respect_awareness=False, awareness_range=aw,
+                               density_map=dens64, soft_obstacles=soft, ignore_flow=ign, maximum_steps=maxs)
+            queries.append([sx, sy, gx, gy, int(soft), int(ign), maxs])
+            for c in p:
+                paths.append((int(c[0]), int(c[1])))
+            poff.append(len(paths))
+        wt = world_tables(m)
+        for k in ("allowed_dirs_map", "is_road_map", "road_type_map", "intersection_map"):
+            out[f"{tag}_{k}"] = wt[k]
+        out[f"{tag}_occupancy_map"] = m.occupancy_map.copy()
+        out[f"{tag}_stop_map"] = m.stop_map.copy()
+        out[f"{tag}_density32"] = d32
+        out[f"{tag}_queries"] = np.asarray(queries, dtype=np.int64)
+        out[f"{tag}_path_off"] = np.asarray(poff, dtype=np.int32)
+        out[f"{tag}_path_xy"] = np.asarray(paths, dtype=np.int32).reshape(-1, 2)
+        out[f"{tag}_stats"] = np.asarray([bound, crude, whole, len(occ_cells)], dtype=np.int64)
+    np.savez_compressed(out_path, **out)
+
+
+def run_astar_cost_kats():
+    """tests/golden/astar_cost_kats.npz: the A* KATs of run_astar_kats (same worlds, same dynamic state, 100 queries per world
+    over the four (soft, ignore_flow) modes, step-limited contraflow queries included) under every set of COST_SETS."""
+    import tempfile
+    import numpy as np
+    tmp = tempfile.mkdtemp(prefix="cost_kats_")
+    jobs = [(name, spec["occupancy"]) for name, spec in COST_SETS.items()] + [("defaults", "base"), ("defaults", "dense")]
+    procs = [(name, occ, subprocess.Popen([sys.executable, os.path.abspath(__file__), "astar_cost_set", name, occ,
+                                           os.path.join(tmp, f"{name}_{occ}.npz")], cwd="/tmp", stdout=subprocess.DEVNULL))
+             for name, occ in jobs]
+    for name, occ, p in procs:
+        assert p.wait() == 0, (name, occ)
+    load = lambda name, occ: np.load(os.path.join(tmp, f"{name}_{occ}.npz"))
+    dflt = {occ: load("defaults", occ) for occ in ("base", "dense")}
+    out = {"sets": np.asarray(json.dumps(list(COST_SETS)))}
+    problems = []
+    for tag in ("a", "b"):
+        for k in ("allowed_dirs_map", "is_road_map", "road_type_map", "intersection_map", "stop_map"):
+            out[f"{tag}_{k}"] = dflt["base"][f"{tag}_{k}"]
+        out[f"{tag}_occupancy_map_base"] = dflt["base"][f"{tag}_occupancy_map"]
+        out[f"{tag}_occupancy_map_dense"] = dflt["dense"][f"{tag}_occupancy_map"]
+    for name, spec in COST_SETS.items():
+        k = load(name, spec["occupancy"])
+        d = dflt[spec["occupancy"]]
+        out[f"{name}_params"] = np.asarray(json.dumps(spec["defaults"]))
+        out[f"{name}_occupancy"] = np.asarray(spec["occupancy"])
+        for tag in ("a", "b"):
+            for m in ("allowed_dirs_map", "is_road_map", "road_type_map", "intersection_map", "stop_map"):
+                assert np.array_equal(k[f"{tag}_{m}"], out[f"{tag}_{m}"]), (name, tag, m)
+            assert np.array_equal(k[f"{tag}_occupancy_map"], out[f"{tag}_occupancy_map_{spec['occupancy']}"])
+            q, off, xy = k[f"{tag}_queries"], k[f"{tag}_path_off"], k[f"{tag}_path_xy"]
+            assert np.array_equal(q, d[f"{tag}_queries"])
+            doff, dxy = d[f"{tag}_path_off"], d[f"{tag}_path_xy"]
+            nonempty = sum(1 for i in range(len(q)) if off[i + 1] > off[i])
+            differs = sum(1 for i in range(len(q)) if off[i + 1] > off[i]
+                          and not np.array_equal(xy[off[i]:off[i + 1]], dxy[doff[i]:doff[i + 1]]))
+            bound, crude, whole, n_occ = (int(v) for v in k[f"{tag}_stats"])
+            print(f"[astar_cost_kats/{name}/{tag}] {len(q)} queries, {nonempty} non-empty, {differs} differ from the defaults' paths, "
+                  f"{whole} whole-number penalty cells of {n_occ} occupied, cost bound {bound} (largest step x cells: {crude})")
+            if 2 * nonempty < len(q):
+                problems.append((name, tag, "fewer than half of the queries return a path", nonempty))
+            if "may_coincide" not in spec and 10 * differs < nonempty:
+                problems.append((name, tag, "fewer than 10 % of the paths differ from the defaults' paths", differs, nonempty))
+            if whole < spec.get("whole_cells", 0):
+                problems.append((name, tag, "too few whole-number penalty cells", whole))
+            out[f"{name}_{tag}_density32"] = k[f"{tag}_density32"]
+            out[f"{name}_{tag}_queries"] = q
+            out[f"{name}_{tag}_path_off"] = off
+            out[f"{name}_{tag}_path_xy"] = xy
+    assert not problems, problems      # (change the set or the dynamic state, not these conditions)
+    np.savez_compressed(os.path.join(HERE, "astar_cost_kats.npz"), **out)
+    print(f"[astar_cost_kats] size={os.path.getsize(os.path.join(HERE, 'astar_cost_kats.npz'))}")
+
+
+def _density_ref(road, occ, r):
+    """city_model.py:1764-1778 on given maps with scipy's own uniform_filter."""
     import numpy as np
     from scipy.ndimage import uniform_filter
+    o = occ.astype(np.float32)
+    so = uniform_filter(o, size=(2 * r + 1, 2 * r + 1), mode="constant", cval=0.0) * ((2 * r + 1) ** 2)
+    rd = road.astype(np.float32)
+    sr = uniform_filter(rd, size=(2 * r + 1, 2 * r + 1), mode="constant", cval=0.0) * ((2 * r + 1) ** 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = np.where(sr > 0, so / sr, 0.0)
+    assert d.dtype == np.float32, d.dtype
+    return d
+
+
+DENSITY_R_RADII = (1, 3, 6, 14, 16)
+DENSITY_R_SHAPES = ((64, 64), (50, 97), (21, 21), (8, 40), (5, 5), (1, 33), (33, 1))
+
+
+def run_density_r():
+    """tests/golden/density_r_kats.npz: the density map at radii other than the default 10, on maps down to a single row or
+    column (narrower than the window in one or both axes), an all-road fully occupied map and a map without roads."""
+    import numpy as np
+    rng = np.random.RandomState(6)
+    out, maps = {}, []
+    for (h, w) in DENSITY_R_SHAPES:
+        road = (rng.rand(h, w) < 0.4).astype(np.int8)
+        occ = ((rng.rand(h, w) < 0.4) & (road == 1)).astype(np.int8)
+        maps.append((f"{h}x{w}", road, occ))
+    for (h, w) in ((21, 21), (8, 40)):
+        maps.append((f"full_{h}x{w}", np.ones((h, w), dtype=np.int8), np.ones((h, w), dtype=np.int8)))
+        maps.append((f"noroad_{h}x{w}", np.zeros((h, w), dtype=np.int8), np.zeros((h, w), dtype=np.int8)))
+    for tag, road, occ in maps:
+        out[f"{tag}_road"], out[f"{tag}_occ"] = road, occ
+        for r in DENSITY_R_RADII:
+            out[f"{tag}_r{r}_density"] = _density_ref(road, occ, r)
+    out["maps"] = np.asarray(json.dumps([t for t, _, _ in maps]))
+    out["radii"] = np.asarray(DENSITY_R_RADII, dtype=np.int32)
+    np.savez_compressed(os.path.join(HERE, "density_r_kats.npz"), **out)
+    print(f"[density_r] {len(maps)} maps x {len(DENSITY_R_RADII)} radii")
+
+
+def run_density():
+    """density_kats.npz (r = 10) and, through run_density_r, density_r_kats.npz (the other radii)."""
+    import numpy as np
+    from scipy.ndimage import uniform_filter
+    run_density_r()
     rng = np.random.RandomState(5)
     out = {}
     for tag, (h, w) in (("a", (64, 64)), ("b", (50, 97)), ("c", (21, 21)), ("d", (8, 40))):
@@ -801,7 +1077,7 @@ def run_worlds():
 def main():
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     if what == "all":
-        jobs = ["mt", "density", "astar_kats", "astar_fov_kats", "worlds"] + list(SCENARIOS)
+        jobs = ["mt", "density", "astar_kats", "astar_fov_kats", "astar_cost_kats", "worlds"] + list(SCENARIOS)
         for j in jobs:
             subprocess.run([sys.executable, os.path.abspath(__file__), j], check=True, cwd="/tmp")
         return
@@ -813,6 +1089,12 @@ def main():
         run_astar_kats()
     elif what == "astar_fov_kats":
         run_astar_fov_kats()
+    elif what == "astar_cost_kats":
+        run_astar_cost_kats()
+    elif what == "astar_cost_set":      # (a child of astar_cost_kats: one set of constants per process)
+        run_astar_cost_set(sys.argv[2], sys.argv[3], sys.argv[4])
+    elif what == "density_r":      # density_r_kats.npz alone (density_kats.npz is left as it is)
+        run_density_r()
     elif what == "worlds":
         run_worlds()
     elif what == "stats":      # `make_golden.py stats <scenario>`: cached_stats_<scenario>.json only, the trace is left alone

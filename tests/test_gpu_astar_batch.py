@@ -92,6 +92,17 @@ def test_fov_kats_in_one_launch_per_range(golden_dir, tag):
     assert nonempty > 100
 
 
+@pytest.mark.parametrize("name,tag", P.K.COST_CASES)
+def test_cost_kats_in_one_launch(hip, golden_dir, name, tag):
+    """The reference's KATs under moved cost constants, one batch per set and world: the CSR equals the reference's paths and
+    what ts_astar answers query by query on the same engine."""
+    q, off, xy = P.K.cost_kat_case(hip, golden_dir, name, tag)
+    got_off, got_xy = assert_kat_batch(hip, q, off, xy, ctx=f"{name}/{tag}: ")
+    for i, (sx, sy, gx, gy, soft, ign, maxs) in enumerate(q):
+        one = hip.astar(int(sx), int(sy), int(gx), int(gy), bool(soft), bool(ign), int(maxs))
+        assert np.array_equal(one, got_xy[got_off[i]:got_off[i + 1]]), f"{name}/{tag} query {i}: {q[i]}"
+
+
 # ---- 2. few slots, a long queue, and no trace of the order of service ------------------------------------------------------
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_three_slots_and_a_permuted_queue(monkeypatch, hip, golden_dir, tag):

@@ -45,7 +45,13 @@ def test_smallheap_astar_fov_kats(golden_dir, tag):
     run_astar_fov_kats(small_engine, golden_dir, tag)
 
 
-@pytest.mark.parametrize("name", ["full_96_s8", "default_200_s20"])
+@pytest.mark.parametrize("name,tag", P.K.COST_CASES)
+def test_smallheap_astar_cost_kats(hip_small, golden_dir, name, tag):
+    """The reference's A* under moved cost constants on the spill form of both loops (half units and doubles)."""
+    P.K.run_astar_cost_kats(hip_small, golden_dir, name, tag)
+
+
+@pytest.mark.parametrize("name", ["full_96_s8", "default_200_s20", "costs_int_96_s31", "costs_frac_96_s32"])
 def test_smallheap_reproduces_reference_trace(hip_small, name):
     P.test_hip_reproduces_reference_trace(hip_small, name)
 

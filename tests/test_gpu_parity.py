@@ -7,7 +7,8 @@ import pytest
 
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd.world import load_trace
-from tests.trace_util import CLOSED_TRACES, DEFAULT_TRACES, DTA_TRACES, RAIN_TRACES, RECT_TRACES, SERVICE_TRACES, VARIANT_TRACES, DESPAWN_TRACES, NOBATCH_TRACES, check_initial, replay_and_compare, setup_from_trace, trace_path
+from tests import test_oracle_kats as K
+from tests.trace_util import CLOSED_TRACES, DEFAULT_TRACES, DTA_TRACES, RAIN_TRACES, RECT_TRACES, SERVICE_TRACES, VARIANT_TRACES, DESPAWN_TRACES, NOBATCH_TRACES, COST_TRACES, check_initial, replay_and_compare, setup_from_trace, trace_path
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +21,7 @@ def hip():
     api.close()
 
 
-@pytest.mark.parametrize("name", CLOSED_TRACES + DTA_TRACES + RAIN_TRACES + SERVICE_TRACES + RECT_TRACES + DEFAULT_TRACES + VARIANT_TRACES + DESPAWN_TRACES + NOBATCH_TRACES)
+@pytest.mark.parametrize("name", CLOSED_TRACES + DTA_TRACES + RAIN_TRACES + SERVICE_TRACES + RECT_TRACES + DEFAULT_TRACES + VARIANT_TRACES + DESPAWN_TRACES + NOBATCH_TRACES + COST_TRACES)
 def test_hip_reproduces_reference_trace(hip, name):
     """Every closed-population trace captured from the reference: car-following, the light controllers, the
     full replanning policy (GPU A*, phases 0-4), frequent strandings, sub-block roads, and the traffic generator
@@ -130,6 +131,21 @@ def test_hip_density_matches_scipy(hip, golden_dir, tag):
     hip.debug_set_occupancy(occ)
     got = hip.density()
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize("shape", K.DENSITY_R_MAPS)
+@pytest.mark.parametrize("r", K.DENSITY_R_RADII)
+def test_hip_density_radius_kats(hip, golden_dir, r, shape):
+    """k_density_pass0/1 at radii 1, 3, 6, 14, 16 against scipy's uniform_filter, bit for bit: windows clamped on one or both
+    axes (maps down to a single row or column), an all-road fully occupied map, a map without roads."""
+    K.run_density_radius_kat(hip, golden_dir, r, shape)
+
+
+@pytest.mark.parametrize("name,tag", K.COST_CASES)
+def test_hip_astar_cost_kats(hip, golden_dir, name, tag):
+    """ts_astar against the reference's astar_numba under moved cost constants: half-unit searches with non-default integers
+    and a non-dyadic scale, searches in doubles (costs stored truncated), both sides of astar_half_units' switch points."""
+    K.run_astar_cost_kats(hip, golden_dir, name, tag)
 
 
 def _pair(size, vehicles, seed, policy):
@@ -438,10 +454,11 @@ def test_hip_vs_oracle_long_run_word_ring_wraps():
 
 
 
-@pytest.mark.parametrize("name", ["full_96_s8", "default_200_s20", "faults_64_s9", "startgoal_96_s27"])
+@pytest.mark.parametrize("name", ["full_96_s8", "default_200_s20", "faults_64_s9", "startgoal_96_s27", "costs_int_96_s31"])
 def test_hip_quad_searcher_reproduces_reference_trace(monkeypatch, name):
     """k_replan_quad (astar_quad.h: sixteen searches per wave; by default only for queues of 262 144 entries and more) with k_replan beside it on the hand-backs,
-    forced on for every tick of a captured run: the same per-tick comparison against the reference's recorded state."""
+    forced on for every tick of a captured run: the same per-tick comparison against the reference's recorded state.
+    costs_int_96_s31 is the one run of the quads with non-default turn / obstacle / road-type penalties."""
     from trafficsimulation_amd._lib import new_engine
     monkeypatch.setenv("TS_QUAD", "1")
     monkeypatch.setenv("TS_QUAD_MIN", "1")
@@ -452,6 +469,26 @@ def test_hip_quad_searcher_reproduces_reference_trace(monkeypatch, name):
         n = replay_and_compare(api, tr)
         assert n == len(tr["veh_off"]) - 1
         assert api.counters().astar_calls == int(tr["astar_calls_spawn"]) + int(tr["astar_per_tick"].sum())
+        assert api.debug_quad_stats()["jobs"] > 0       # (the quads did take the queues)
+    finally:
+        api.close()
+
+
+def test_hip_keeps_the_quads_off_for_fractional_costs(monkeypatch):
+    """costs_frac_96_s32 with the quads asked for on every queue: its penalties are no multiples of 0.5, so the engine must
+    keep the quad searcher (half units only) off by itself - no quad pass runs and the run is still exact."""
+    from trafficsimulation_amd._lib import new_engine
+    monkeypatch.setenv("TS_QUAD", "1")
+    monkeypatch.setenv("TS_QUAD_MIN", "1")
+    api = new_engine()
+    try:
+        tr = load_trace(trace_path("costs_frac_96_s32"))
+        setup_from_trace(api, tr, explicit_paths=False)
+        n = replay_and_compare(api, tr)
+        assert n == len(tr["veh_off"]) - 1
+        assert api.counters().astar_calls == int(tr["astar_calls_spawn"]) + int(tr["astar_per_tick"].sum())
+        st = api.debug_quad_stats()
+        assert st["passes"] == 0 and st["jobs"] == 0, st
     finally:
         api.close()
 

@@ -68,6 +68,7 @@ PINNED = {
     "default_200_s20": (2991, 2771, 2571, 23, 177, 0, 0, 0, 5320),
     "rect_64x112_s19": (5528, 4168, 2706, 0, 1, 0, 1461, 0, 10845),
     "rect_96x64_s18": (2732, 2122, 2080, 6, 4, 0, 32, 0, 5293),
+    "costs_int_96_s31": (4369, 2594, 2396, 11, 149, 0, 38, 0, 8565),
 }
 # (every reason of a search's hand-back occurs on some trace)
 assert all(any(v[PINNED_KEYS.index(r)] > 0 for v in PINNED.values()) for r in ("window", "heap", "budget", "path_buffer"))
@@ -76,7 +77,9 @@ assert all(any(v[PINNED_KEYS.index(r)] > 0 for v in PINNED.values()) for r in ("
 TRACES = [("full_64_s1", False, False), ("faults_64_s9", False, False), ("config1_64_s11", False, False),
           ("full_96_s8", True, True), ("startgoal_96_s27", True, True), ("carve_96_s10", True, True),
           ("ring_r1_112_s22", True, True), ("default_200_s20", True, True),
-          ("rect_64x112_s19", False, True), ("rect_96x64_s18", True, False)]
+          ("rect_64x112_s19", False, True), ("rect_96x64_s18", True, False),
+          # non-default turn / obstacle / road-type penalties and a density window of r = 6 in the quads' half-unit costs
+          ("costs_int_96_s31", True, True)]
 
 
 @pytest.mark.parametrize("name,wx,wy", TRACES)

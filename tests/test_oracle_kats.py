@@ -1,4 +1,5 @@
 """CPU oracle vs golden vectors G2 (A*), G3 (density), G4 (MT19937)."""
+import json
 import os
 
 import numpy as np
@@ -67,6 +68,112 @@ def test_astar_kats(oracle, golden_dir, tag):
         assert np.array_equal(got, want), f"query {i}: {q[i]}"
         nonempty += len(want) > 0
     assert nonempty > 50
+
+
+# density_r_kats.npz: the window at radii other than 10, on maps down to one row / column (narrower than the window in one
+# or both axes), an all-road fully occupied map and a map without roads
+DENSITY_R_RADII = [1, 3, 6, 14, 16]
+DENSITY_R_MAPS = ["64x64", "50x97", "21x21", "8x40", "5x5", "1x33", "33x1", "full_21x21", "noroad_21x21", "full_8x40", "noroad_8x40"]
+
+
+def run_density_radius_kat(api, golden_dir, r, shape):
+    k = np.load(os.path.join(golden_dir, "density_r_kats.npz"))
+    road, occ, want = k[f"{shape}_road"], k[f"{shape}_occ"], k[f"{shape}_r{r}_density"]
+    p = api.default_params()
+    p.vehicle_awareness_range = r
+    z = np.zeros_like(road)
+    api.create(z.astype(np.uint8), road, z, z, p)
+    api.debug_set_occupancy(occ)
+    got = api.density()
+    assert got.dtype == np.float32 and got.shape == want.shape
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))  # bit-exact
+    if shape.startswith("full"):
+        assert np.all(want > 0.99)
+    if shape.startswith("noroad"):
+        assert not want.any()
+
+
+def test_density_radius_fixture_is_complete(golden_dir):
+    k = np.load(os.path.join(golden_dir, "density_r_kats.npz"))
+    assert json.loads(str(k["maps"])) == DENSITY_R_MAPS and k["radii"].tolist() == DENSITY_R_RADII
+
+
+@pytest.mark.parametrize("shape", DENSITY_R_MAPS)
+@pytest.mark.parametrize("r", DENSITY_R_RADII)
+def test_density_radius_kats(oracle, golden_dir, r, shape):
+    run_density_radius_kat(oracle, golden_dir, r, shape)
+
+
+# astar_cost_kats.npz: the reference's A* under moved cost constants (tests/golden/make_golden.py COST_SETS), 100 queries per
+# set and world.  name -> whether the engine's searches run in half units under the set (csrc/astar.h astar_half_units)
+COST_SETS = {"ints": True, "flags_off": True, "turn0": True, "quarter": False, "nondyadic": False, "scale_half": True,
+             "switch_lo": True, "switch_hi": False, "field_edge": True}
+COST_CASES = [(s, t) for s in COST_SETS for t in ("a", "b")]
+_cost_kats = {}
+
+
+def cost_kats(golden_dir):
+    if "k" not in _cost_kats:
+        z = np.load(os.path.join(golden_dir, "astar_cost_kats.npz"))
+        _cost_kats["k"] = {n: z[n] for n in z.files}
+    return _cost_kats["k"]
+
+
+def cost_kat_case(api, golden_dir, name, tag):
+    """An engine on world `tag` under the set `name` with the fixture's dynamic state -> (queries, path_off, path_xy)."""
+    k = cost_kats(golden_dir)
+    p = api.params_from_defaults(json.loads(str(k[f"{name}_params"])))
+    api.create(k[f"{tag}_allowed_dirs_map"], k[f"{tag}_is_road_map"], k[f"{tag}_road_type_map"], k[f"{tag}_intersection_map"], p)
+    api.debug_set_occupancy(k[f"{tag}_occupancy_map_{k[f'{name}_occupancy']}"])
+    api.upload_map(capi.MAP_STOP, k[f"{tag}_stop_map"])
+    return k[f"{name}_{tag}_queries"], k[f"{name}_{tag}_path_off"], k[f"{name}_{tag}_path_xy"]
+
+
+def run_astar_cost_kats(api, golden_dir, name, tag):
+    q, off, xy = cost_kat_case(api, golden_dir, name, tag)
+    # the density the penalties are scaled by, under the set's own awareness range (bit-exact)
+    assert np.array_equal(api.density().view(np.uint32), cost_kats(golden_dir)[f"{name}_{tag}_density32"].view(np.uint32))
+    assert len(q) == 100 and 2 * int((np.diff(off) > 0).sum()) >= len(q)
+    for i, (sx, sy, gx, gy, soft, ign, maxs) in enumerate(q):
+        got = api.astar(int(sx), int(sy), int(gx), int(gy), bool(soft), bool(ign), int(maxs))
+        assert np.array_equal(got, xy[off[i]:off[i + 1]]), f"{name}/{tag} query {i}: {q[i]}"
+
+
+@pytest.mark.parametrize("name,tag", COST_CASES)
+def test_astar_cost_kats(oracle, golden_dir, name, tag):
+    run_astar_cost_kats(oracle, golden_dir, name, tag)
+
+
+def half_units(p):
+    """csrc/astar.h astar_half_units, restated: every penalty a non-negative multiple of 0.5 below 2^20, 0 <= scale <= 64,
+    and the largest per-cell vehicle penalty in half units inside the snapshot's 22-bit field (veh (1 + scale) 2 < 2^21)."""
+    pens = [p.turn_penalty, p.contraflow_penalty, p.obstacle_penalty_vehicle, p.obstacle_penalty_stop,
+            p.road_type_penalty_r1, p.road_type_penalty_r2, p.road_type_penalty_r3]
+    return (all(0 <= v < 2 ** 20 and float(v * 2).is_integer() for v in pens) and 0.0 <= p.dynamic_penalty_scale <= 64.0
+            and p.obstacle_penalty_vehicle * (1.0 + p.dynamic_penalty_scale) * 2.0 < 2 ** 21)
+
+
+def test_cost_sets_select_the_form_they_were_made_for(oracle, golden_dir):
+    """Host only: which sets the engine searches in half units (the quad searcher's only form, penalties in the map
+    snapshot) and which in doubles.  The engine's own choice shows on the GPU: test_hip_quad_searcher_* run the two cost
+    traces with the quads forced on and read the quad counters."""
+    k = cost_kats(golden_dir)
+    assert json.loads(str(k["sets"])) == list(COST_SETS)
+    assert half_units(oracle.default_params())
+    for name, want in COST_SETS.items():
+        p = oracle.params_from_defaults(json.loads(str(k[f"{name}_params"])))
+        assert half_units(p) == want, name
+    # either side of the 22-bit field: veh * 65 * 2 against 2^21
+    p = oracle.params_from_defaults(json.loads(str(k["field_edge_params"])))
+    assert p.obstacle_penalty_vehicle == 16000 and p.dynamic_penalty_scale == 64.0
+    for veh, want in ((16131, True), (16132, False)):
+        p.obstacle_penalty_vehicle = veh
+        assert half_units(p) == want, veh
+    # and the traces that carry a set into a live run
+    from trafficsimulation_amd.world import load_trace
+    from tests.trace_util import trace_path
+    for trace, want in (("costs_int_96_s31", True), ("costs_frac_96_s32", False)):
+        assert half_units(oracle.params_from_defaults(load_trace(trace_path(trace))["defaults_json"])) == want, trace
 
 
 def run_astar_fov_kats(make_api, golden_dir, tag):

@@ -32,6 +32,9 @@ VARIANT_TRACES = ["unopt_96_s21", "ring_r1_112_s22", "noring_96_s23", "fwdrange_
 DESPAWN_TRACES = ["despawn_96_s25", "fov_96_s26", "startgoal_96_s27"]
 # PATHFINDING_BATCHING=False (vehicle_base.py:666-685): step_decide inside step(), in the shuffled order
 NOBATCH_TRACES = ["nobatch_full_96_s28", "nobatch_config1_64_s29", "nobatch_service_96_s30"]
+# the A* cost constants moved (tests/golden/make_golden.py COST_SETS): all-integer penalties with a density window of r = 6
+# (half-unit searches), and non-dyadic road-type penalties and scale (searches in doubles)
+COST_TRACES = ["costs_int_96_s31", "costs_frac_96_s32"]
 DEFAULT_TRACES = ["default_200_s20"]                   # CityModel() as the reference ships: 200 x 200, config.py untouched
 
 
