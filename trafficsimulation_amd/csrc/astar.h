@@ -64,7 +64,7 @@ constexpr int A_STEPS_MAX = (int)T_STEPS_MASK - 1;   // largest binding step lim
 
 __shared__ unsigned long long g_lq[LDS_HEAP];   // packed HQ: f in the low word, cell in the high word
 __shared__ int8_t g_ld[LDS_HEAP];
-__shared__ int g_job;   // k_replan: the work-queue entry the wave is on
+__shared__ int g_job;   // the work-queue entry the wave is on (wave_pop)
 
 // One searcher's scratch: LDS heap (above) + its slot of the HBM arena.
 struct AScratch {
@@ -86,7 +86,7 @@ struct AScratch {
   int q_start, q_goal, q_soft, q_cap;      // the search the policy is waiting for
   int32_t* q_out;
 };
-struct RLists { int32_t* l[6]; };       // replan work lists, see run_replans (engine.hip)
+struct RLists { int32_t* l[4]; };       // the replanning queue's class lists (RQueue)
 
 struct ASlots {
   int n_slots, heap_cap, cap, use_reach;
@@ -574,9 +574,9 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
   else r = C.half ? run(std::true_type{}, std::true_type{}) : run(std::false_type{}, std::true_type{});
   S.expansions += C.n_exp; S.relaxations += C.n_relax;
   if (C.lane == 0) {   // profiling aid: deepest heap / longest search any searcher has seen (ts_debug_read words 4, 5)
-    atomicMax(&d.cnt->dbg[4], C.max_heap);
-    atomicMax(&d.cnt->dbg[5], (int)min(C.n_exp, (long long)0x7FFFFFFF));
-    if (C.n_exp_spill) atomicAdd((unsigned long long*)&d.cnt->dbg[6], (unsigned long long)C.n_exp_spill);   // (dbg[6..7] as one 64-bit count)
+    atomicMax(&d.cnt->max_heap, C.max_heap);
+    atomicMax(&d.cnt->max_search_exp, (int)min(C.n_exp, (long long)0x7FFFFFFF));
+    if (C.n_exp_spill) atomicAdd((unsigned long long*)&d.cnt->spill_exp, (unsigned long long)C.n_exp_spill);
 #ifdef TS_KPROF
     for (int k = 0; k < 8; k++) d.cnt->prof[k] = C.prof[k];
 #endif
@@ -1124,13 +1124,26 @@ __global__ void k_decide_main(Dev d, TsParams P, int lo, int n_active, RLists li
     // work-queue class (largest first): what the vehicle's last replan cost, or what a search over this distance is
     // likely to cost
     const int h = cost_class_of_bits(replan_cost_bits(d, d.active[i]));
-    lists.l[h][atomicAdd(&d.cnt->replan_n[h], 1)] = i;
+    lists.l[h][atomicAdd(&d.cnt->replan.class_n[h], 1)] = i;
   }
 }
 
 // sort key of a replanning entry (run_replans): expected cost, largest first (bit length of the expansions, see cost_bits),
 // then the Morton index of the 32 x 32-cell block its vehicle stands in
 constexpr int REPLAN_KEY_BITS = 21;
+__device__ __forceinline__ uint32_t morton_block_key(int x, int y) {
+  const uint32_t bx = (uint32_t)x >> 5, by = (uint32_t)y >> 5;
+  uint32_t k = 0;
+  for (int b = 0; b < 8; b++) k |= ((bx >> b) & 1u) << (2 * b) | ((by >> b) & 1u) << (2 * b + 1);
+  return k;
+}
+__device__ __forceinline__ uint32_t replan_key(const Dev& d, int i) {
+  const int vid = d.active[i];
+  int x = 0, y = 0, bits = 0;
+  if (vid >= 0) { cell_xy(d, d.pos[vid], x, y); bits = min(replan_cost_bits(d, vid), 31); }
+  // (only the long searches are ordered by cost - 65 536 expansions and more, bit by bit; the bulk stays in plain spatial order)
+  return ((uint32_t)(31 - max(bits, 16)) << 16) | morton_block_key(x, y);
+}
 // The same with the entry itself (its decide-order index) below the key: a total order, the same on every rank of a sharded
 // run whatever order k_decide_main's atomics left the list in, so that ranks can split the queue by POSITION (entry j of
 // the sorted queue belongs to rank j % world: every rank gets every world-th search of every cost class and every
@@ -1138,13 +1151,7 @@ constexpr int REPLAN_KEY_BITS = 21;
 __global__ void k_replan_keys64(Dev d, const int32_t* list, int n, unsigned long long* keys) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  const int i = list[j];
-  const int vid = d.active[i];
-  int x = 0, y = 0, bits = 0;
-  if (vid >= 0) { cell_xy(d, d.pos[vid], x, y); bits = min(replan_cost_bits(d, vid), 31); }
-  uint32_t bx = (uint32_t)x >> 5, by = (uint32_t)y >> 5, k = 0;
-  for (int b = 0; b < 8; b++) k |= ((bx >> b) & 1u) << (2 * b) | ((by >> b) & 1u) << (2 * b + 1);
-  keys[j] = ((unsigned long long)(((uint32_t)(31 - max(bits, 16)) << 16) | k) << 32) | (unsigned long long)(uint32_t)i;
+  keys[j] = ((unsigned long long)replan_key(d, list[j]) << 32) | (unsigned long long)(uint32_t)list[j];
 }
 __global__ void k_replan_unkey64(const unsigned long long* keys, int n, int32_t* list) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1153,13 +1160,62 @@ __global__ void k_replan_unkey64(const unsigned long long* keys, int n, int32_t*
 __global__ void k_replan_keys(Dev d, const int32_t* list, int n, uint32_t* keys) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  const int vid = d.active[list[j]];
-  int x = 0, y = 0, bits = 0;
-  if (vid >= 0) { cell_xy(d, d.pos[vid], x, y); bits = min(replan_cost_bits(d, vid), 31); }
-  uint32_t bx = (uint32_t)x >> 5, by = (uint32_t)y >> 5, k = 0;
-  for (int b = 0; b < 8; b++) k |= ((bx >> b) & 1u) << (2 * b) | ((by >> b) & 1u) << (2 * b + 1);
-  // (only the long searches are ordered by cost - 65 536 expansions and more, bit by bit; the bulk stays in plain spatial order)
-  keys[j] = ((uint32_t)(31 - max(bits, 16)) << 16) | k;
+  keys[j] = replan_key(d, list[j]);
+}
+
+// ---- the replanning work queue ---------------------------------------------------------------------------------------
+// Vehicles whose step_decide needs a search wait in four class lists, by expected cost (k_decide_main files them, run_replans
+// sorts each).  The queue is classes 3, 2, 1, 0 in turn: a tick's replanning time is bounded below by its longest search, so
+// those start first and the short ones fill in behind.  Its counters are DevCnt::replan and the four words after it.  k_replan
+// (one wave per search) and k_replan_quad (astar_quad.h, sixteen per wave) serve it, each the classes of its `class_mask` with
+// a cursor of its own; pool-full entries go to retry_list for the host to run again.
+// Ownership by position (`world` > 1, the replicated-state multi-GPU mode): the queue is in the same total order on every
+// rank (run_replans sorts by (key, index)) and the entry at position pos of the WHOLE queue - every class counted, whichever
+// kernel serves it - is rank pos % world's.  What a rank plans goes to owned_list for ts_replan_export / ts_replan_import.
+// Hand-backs: a vehicle the quads cannot carry goes to handback_list - counted in handback_n, then stored (-1 = not yet
+// written).  k_replan's waves beside the quads (fb_waves = the quads' grid, 0 = none) serve that list once their own classes
+// are done: a ticket from handback_claimed, never beyond handback_n, so what is left when they stop is a suffix the host can
+// queue again; hand-backs of this rank's quads are this rank's.  They give up when all fb_waves quad waves have counted
+// themselves out in quad_waves_done and nothing more was produced, or when no counter has moved for about three seconds
+// (the kernels were not run side by side - a profiler or debugger serialising launches; k_replan_quad is then yet to run).
+// The host's part, one kernel argument.  fb_waves: k_replan only, the quads' grid (0: no quads beside it).
+struct RQueueArgs { RLists lists; int class_mask; int32_t *retry_list, *handback_list; int rank, world; int32_t* owned_list /* nullptr unless sharded */; int fb_waves; };
+struct RQueue {         // what a turn at the queue reads: the host's part + what rqueue_open fills on the device
+  RLists lists;
+  int n[4], pos0[4];    // class list lengths (0: not served by this launch); position of each class' first entry in the whole queue
+  int32_t *retry_list, *handback_list, *owned_list; int rank, world;
+};
+// k_replan's: + the quads beside it.  Apart from RQueue for the compiler's sake only: the queue goes to the turn functions through the stack, and fb_waves inside RQueue (or as a parameter) changes k_replan_quad's (k_replan's) scratch size
+struct RQueueFb : RQueue { int fb_waves; };
+__device__ __forceinline__ RQueue rqueue_open(const Dev& d, const RQueueArgs& a) {
+  RQueue q; const int* cn = d.cnt->replan.class_n;
+  q.lists = a.lists;
+  for (int c = 0; c < 4; c++) q.n[c] = ((a.class_mask >> c) & 1) ? cn[c] : 0;
+  q.pos0[3] = 0; q.pos0[2] = cn[3]; q.pos0[1] = cn[3] + cn[2]; q.pos0[0] = cn[3] + cn[2] + cn[1];
+  q.retry_list = a.retry_list; q.handback_list = a.handback_list; q.owned_list = a.owned_list; q.rank = a.rank; q.world = a.world;
+  return q;
+}
+// cursor value j (below the launch's total) -> the entry i and its position in the whole queue; false: another rank's
+__device__ __forceinline__ bool rqueue_entry(const RQueue& q, int j, int& i, int& pos) {
+  const int n3 = q.n[3], n2 = q.n[2], n1 = q.n[1];
+  if (j < n3) { i = q.lists.l[3][j]; pos = q.pos0[3] + j; }
+  else if (j < n3 + n2) { i = q.lists.l[2][j - n3]; pos = q.pos0[2] + j - n3; }
+  else if (j < n3 + n2 + n1) { i = q.lists.l[1][j - n3 - n2]; pos = q.pos0[1] + j - n3 - n2; }
+  else { i = q.lists.l[0][j - n3 - n2 - n1]; pos = q.pos0[0] + j - n3 - n2 - n1; }
+  return q.world <= 1 || (pos % q.world) == q.rank;
+}
+// lane 0 draws the next value of a queue cursor for the whole wave
+__device__ __forceinline__ int wave_pop(int* cursor) {
+  if (threadIdx.x == 0) g_job = atomicAdd(cursor, 1);
+  __syncthreads();
+  const int j = uni(g_job);
+  __syncthreads(); return j;
+}
+// searches that ended in a committed result, into the model's counters
+__device__ __forceinline__ void searcher_account(const Dev& d, long long calls, long long exp, long long relax) {
+  atomicAdd((unsigned long long*)&d.cnt->astar_calls, (unsigned long long)calls);
+  atomicAdd((unsigned long long*)&d.cnt->astar_exp, (unsigned long long)exp);
+  atomicAdd((unsigned long long*)&d.cnt->astar_relax, (unsigned long long)relax);
 }
 
 // One turn of a searcher wave at the replanning work queue: take the next entry, run the vehicle's step_decide with
@@ -1173,54 +1229,35 @@ __global__ void k_replan_keys(Dev d, const int32_t* list, int n, uint32_t* keys)
 __device__ int4* g_rtrace = nullptr;
 __device__ int g_rtrace_cap = 0;
 #endif
-struct RQueue {
-  int32_t* l[4]; int n[4]; int32_t *retry_list, *owned_list; int rank, world;
-  int pos0[4];   // position of class c's first entry in the whole queue (classes 3, 2, 1, 0 in turn, whatever class_mask serves)
-  // vehicles k_replan_quad (astar_quad.h) hands back while both kernels run: entries appear in fb_list (-1 = not yet
-  // written; tickets from quad_n[2]) until all fb_waves quad waves have counted themselves out in quad_n[3]
-  int32_t* fb_list; int fb_waves, fb_cap;   // fb_cap: entries the quads were given = the most they can hand back
-};
-// where each class list starts in the whole queue - classes 3, 2, 1, 0 in turn, every class counted whichever kernel serves it:
-// the sharded mode deals entries out by this position, so that a rank that sends some classes to k_replan_quad and a rank that
-// does not agree on who owns what
-__device__ __forceinline__ void replan_class_pos0(const Dev& d, int* pos0) {
-  const int f3 = d.cnt->replan_n[3], f2 = d.cnt->replan_n[2], f1 = d.cnt->replan_n[1];
-  pos0[3] = 0; pos0[2] = f3; pos0[1] = f3 + f2; pos0[0] = f3 + f2 + f1;
-}
-__device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParams& P, AScratch* S, const RQueue& q) {
+__device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParams& P, AScratch* S, const RQueueFb& q) {
   const int n3 = uni(q.n[3]), n2 = uni(q.n[2]), n1 = uni(q.n[1]), n0 = uni(q.n[0]);
-  if (threadIdx.x == 0) g_job = atomicAdd(&d.cnt->replan_n[5], 1);
-  __syncthreads();
-  const int j = uni(g_job);
-  __syncthreads();
+  const int j = wave_pop(&d.cnt->replan.cursor);
   int i, pos = j;
+  bool mine = true;
   if (j >= n3 + n2 + n1 + n0) {
     if (q.fb_waves == 0) return 0;
-    // this launch's own lists are done: serve the hand-back list.  An entry is only ever claimed once it has been produced
-    // (claimed <= produced at all times), so whatever is left when this wave gives up is a suffix the host can queue again.
-    // Giving up: all quad waves have counted themselves out, or nothing has moved for about three seconds (the two kernels
-    // were not run side by side - a profiler or debugger serialising launches; k_replan_quad is then yet to run).
+    // this launch's own lists are done: serve the hand-back list (the protocol and its give-up rule: see RQueue)
     if (threadIdx.x == 0) {
       int job = -1;
       long long t_last = wall_clock64();
       int seen = -1;
       for (;;) {
-        const int produced = __hip_atomic_load(&d.cnt->quad_n[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        int claimed = __hip_atomic_load(&d.cnt->quad_n[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int produced = __hip_atomic_load(&d.cnt->handback_n, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        int claimed = __hip_atomic_load(&d.cnt->handback_claimed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (claimed < produced) {
-          if (__hip_atomic_compare_exchange_strong(&d.cnt->quad_n[2], &claimed, claimed + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+          if (__hip_atomic_compare_exchange_strong(&d.cnt->handback_claimed, &claimed, claimed + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
             // (the producer stores the entry right after counting it: a running wave, a few hundred cycles at most)
-            do job = __hip_atomic_load(&q.fb_list[claimed], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); while (job < 0);
+            do job = __hip_atomic_load(&q.handback_list[claimed], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); while (job < 0);
             break;
           }
           continue;
         }
-        const int done = __hip_atomic_load(&d.cnt->quad_n[3], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        const int done = __hip_atomic_load(&d.cnt->quad_waves_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
         if (done >= q.fb_waves) {
-          if (__hip_atomic_load(&d.cnt->quad_n[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == produced) break;   // nothing more can come
+          if (__hip_atomic_load(&d.cnt->handback_n, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == produced) break;   // nothing more can come
           continue;
         }
-        const int mark = produced + done + __hip_atomic_load(&d.cnt->quad_n[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int mark = produced + done + __hip_atomic_load(&d.cnt->quad_cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const long long now = wall_clock64();
         if (mark != seen) { seen = mark; t_last = now; }
         else if (now - t_last > 300000000ll) break;          // 3 s of the 100 MHz clock
@@ -1233,15 +1270,9 @@ __device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParam
     __syncthreads();
     if (i < 0) return 0;
   }
-  else if (j < n3) { i = q.l[3][j]; pos = q.pos0[3] + j; }
-  else if (j < n3 + n2) { i = q.l[2][j - n3]; pos = q.pos0[2] + j - n3; }
-  else if (j < n3 + n2 + n1) { i = q.l[1][j - n3 - n2]; pos = q.pos0[1] + j - n3 - n2; }
-  else { i = q.l[0][j - n3 - n2 - n1]; pos = q.pos0[0] + j - n3 - n2 - n1; }
+  else mine = rqueue_entry(q, j, i, pos);
   i = uni(i);
-  // (sharded mode: the queue is in the same total order on every rank - run_replans sorts it by (key, index) - and the entry
-  // at position pos of it is rank pos % world's, whichever kernel serves its class on this rank; hand-backs of this rank's own
-  // quads are this rank's)
-  if (q.world > 1 && j < n3 + n2 + n1 + n0 && (pos % q.world) != q.rank) return 1;
+  if (!mine) return 1;
   // the most expensive classes are a tick's critical path (its longest search bounds it): their waves take the issue slots
   // of their SIMD first, the five waves beside them fill in behind (`s_setprio`; TS_NO_PRIO: a build without it)
 #ifndef TS_NO_PRIO
@@ -1263,33 +1294,20 @@ __device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParam
     if (r == DV_DONE) {  // work of attempts that are re-run after pool growth is not counted twice
       const int vid = d.active[i];
       if (S->calls > c0) d.tier_hint[vid] = (uint8_t)cost_bits(S->expansions - e0);
-      atomicAdd((unsigned long long*)&d.cnt->astar_calls, (unsigned long long)(S->calls - c0));
-      atomicAdd((unsigned long long*)&d.cnt->astar_exp, (unsigned long long)(S->expansions - e0));
-      atomicAdd((unsigned long long*)&d.cnt->astar_relax, (unsigned long long)(S->relaxations - r0));
-      if (q.owned_list) q.owned_list[atomicAdd(&d.cnt->replan_n[6], 1)] = i;
+      searcher_account(d, S->calls - c0, S->expansions - e0, S->relaxations - r0);
+      if (q.owned_list) q.owned_list[atomicAdd(&d.cnt->replan.owned_n, 1)] = i;
     } else if (r == DV_OVERFLOW) atomicExch(&d.cnt->error, TS_E_CAPACITY);
-    else if (r == DV_POOL_FULL) q.retry_list[atomicAdd(&d.cnt->replan_n[4], 1)] = i;
+    else if (r == DV_POOL_FULL) q.retry_list[atomicAdd(&d.cnt->replan.retry_n, 1)] = i;
   }
   return 1;
 }
 
-// Replanning vehicles: a work queue served by one wave per searcher slot.  The queue is the four class lists, the
-// most expensive class first (a tick's replanning time is bounded below by its longest search: start those first and
-// let the short ones fill in behind).  Every wave takes the next entry until the queue is empty; all 64 lanes run
-// the vehicle's step_decide together and share the work inside the searches.  Entries that find the path pool
-// full go to `retry_list` (counter replan_n[4]); replan_n[5] is the queue cursor.
-// `world` > 1: the replicated-state multi-GPU mode - this rank plans only the vehicles whose decide-order index is
-// congruent to `rank`; the results travel through ts_replan_export / ts_replan_import.
-// `class_mask`: the class lists this launch serves (the others belong to k_replan_quad, astar_quad.h).
-TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_replan(Dev d, TsParams P, ASlots sl, RLists lists, int32_t* retry_list, int rank, int world,
-                                               int32_t* owned_list, int class_mask, int32_t* fb_list, int fb_waves, int fb_cap) {
+// Replanning vehicles, one wave per searcher slot: every wave takes the next entry of the queue (RQueue) until it is empty;
+// all 64 lanes run the vehicle's step_decide together and share the work inside the searches.
+TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_replan(Dev d, TsParams P, ASlots sl, RQueueArgs qa) {
   AScratch S;
   scratch_bind(sl, blockIdx.x, S);
-  RQueue q;
-  for (int c = 0; c < 4; c++) { q.l[c] = lists.l[c]; q.n[c] = ((class_mask >> c) & 1) ? d.cnt->replan_n[c] : 0; }
-  replan_class_pos0(d, q.pos0);
-  q.retry_list = retry_list; q.owned_list = owned_list; q.rank = rank; q.world = world;
-  q.fb_list = fb_list; q.fb_waves = fb_waves; q.fb_cap = fb_cap;
+  const RQueueFb q = {rqueue_open(d, qa), qa.fb_waves};
   while (uni(replan_turn(d, P, &S, q))) {}
   if (threadIdx.x == 0) sl.slot_epoch[blockIdx.x] = S.epoch;
 }
@@ -1387,14 +1405,10 @@ TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_astar_single(Dev d, TsPara
   if (threadIdx.x) return;
   {  // probe figures (profiles/astar_probe.py): shader cycles and 100 MHz wall ticks the search took
     const long long dc = clock64() - c0, dw = wall_clock64() - w0;
-    d.cnt->dbg[0] = (int)(dc & 0xFFFFFFFF); d.cnt->dbg[1] = (int)(dc >> 32); d.cnt->dbg[2] = (int)(dw & 0xFFFFFFFF); d.cnt->dbg[3] = (int)(dw >> 32);
+    d.cnt->probe_cycles = dc; d.cnt->probe_wall = dw;
   }
   sl.slot_epoch[0] = S.epoch;
-  if (len >= 0) {
-    atomicAdd((unsigned long long*)&d.cnt->astar_calls, (unsigned long long)S.calls);
-    atomicAdd((unsigned long long*)&d.cnt->astar_exp, (unsigned long long)S.expansions);
-    atomicAdd((unsigned long long*)&d.cnt->astar_relax, (unsigned long long)S.relaxations);
-  }
+  if (len >= 0) searcher_account(d, S.calls, S.expansions, S.relaxations);
   *out_len = len;  // -1 = heap / output capacity exceeded; the path cells are in the slot's A buffer
 }
 
@@ -1420,11 +1434,7 @@ TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_spawn_plan(Dev d, TsParams
   for (int k = 0; k < 4; k++) if (v.ax_staged[k]) words += (v.ax_len[k] + 15) / 16;
   uint32_t off = 0;
   if (words > 0 && !pool_alloc<DM_WAVE>(d, words, off)) { if (one) *status = -2; return; }
-  if (one) {
-    atomicAdd((unsigned long long*)&d.cnt->astar_calls, (unsigned long long)S.calls);
-    atomicAdd((unsigned long long*)&d.cnt->astar_exp, (unsigned long long)S.expansions);
-    atomicAdd((unsigned long long*)&d.cnt->astar_relax, (unsigned long long)S.relaxations);
-  }
+  if (one) searcher_account(d, S.calls, S.expansions, S.relaxations);
   encode_cells(d, off, v.pos, S.P, len);
   d.path_off[vid] = off; d.path_len[vid] = len; d.path_cur[vid] = 0;
   off += (len + 15) / 16;

@@ -41,10 +41,7 @@ __global__ void k_batch_keys(const int32_t* __restrict__ q, int n, uint32_t* __r
   if (i >= n) return;
   const int32_t* a = q + (size_t)i * 7;
   const int cls = cost_class_of_bits(cost_bits_of_distance(abs(a[0] - a[2]) + abs(a[1] - a[3])));
-  const uint32_t bx = (uint32_t)a[0] >> 5, by = (uint32_t)a[1] >> 5;
-  uint32_t k = 0;
-  for (int b = 0; b < 8; b++) k |= ((bx >> b) & 1u) << (2 * b) | ((by >> b) & 1u) << (2 * b + 1);
-  keys[i] = ((uint32_t)(3 - cls) << 16) | k;
+  keys[i] = ((uint32_t)(3 - cls) << 16) | morton_block_key(a[0], a[1]);
   ident[i] = i;
 }
 
@@ -58,10 +55,7 @@ __global__ void k_batch_iota(int32_t* __restrict__ order, int n) {
 // is: inlined into the kernel's loop, the lane-0-only parts of consecutive turns (queue pop, bookkeeping) are threaded together
 // and lane 0 leaves the other 63 lanes; a call boundary is a point where the wave is whole again.
 __device__ __attribute__((noinline)) int batch_turn(const Dev& d, const TsParams& P, AScratch* S, const BatchQ& q) {
-  if (threadIdx.x == 0) g_job = atomicAdd(&q.ctl->cursor, 1);
-  __syncthreads();
-  const int j = uni(g_job);
-  __syncthreads();
+  const int j = wave_pop(&q.ctl->cursor);
   if (j >= q.n_run) return 0;
   const int qi = uni(q.order[j]);
   const int32_t* a = q.q + (size_t)qi * 7;
@@ -89,9 +83,7 @@ __device__ __attribute__((noinline)) int batch_turn(const Dev& d, const TsParams
   }
   if (threadIdx.x == 0) {
     q.soff[qi] = so; q.len[qi] = len;
-    atomicAdd((unsigned long long*)&d.cnt->astar_calls, (unsigned long long)(S->calls - c0));
-    atomicAdd((unsigned long long*)&d.cnt->astar_exp, (unsigned long long)(S->expansions - e0));
-    atomicAdd((unsigned long long*)&d.cnt->astar_relax, (unsigned long long)(S->relaxations - r0));
+    searcher_account(d, S->calls - c0, S->expansions - e0, S->relaxations - r0);
   }
   return 1;
 }

@@ -449,7 +449,6 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
 }
 
 struct QReq { int start, goal, soft, cap; int32_t* out; };
-struct QQueue { int32_t* l[4]; int n[4]; int pos0[4]; int32_t *retry_list, *fallback_list, *owned_list; int rank, world; };
 
 __device__ __forceinline__ void quad_scratch_bind(const QSlots& qs, int slot, AScratch& S) {
   S.tab = nullptr; S.gq = nullptr; S.gd = nullptr; S.heap_cap = 0; S.epoch = 0;
@@ -466,7 +465,7 @@ __device__ __forceinline__ void quad_scratch_bind(const QSlots& qs, int slot, AS
 
 // One pass of vehicle i's step_decide by the quad (see the header: re-run from the top after every search).  Kept out of
 // line like replan_turn.
-__device__ __attribute__((noinline)) int quad_policy(const Dev& d, const TsParams& P, const QSlots& qs, const QQueue& q, int slot, int i,
+__device__ __attribute__((noinline)) int quad_policy(const Dev& d, const TsParams& P, const QSlots& qs, const RQueue& q, int slot, int i,
                                                      int n_done, QReq& req) {
   AScratch S;
   quad_scratch_bind(qs, slot, S);
@@ -479,29 +478,22 @@ __device__ __attribute__((noinline)) int quad_policy(const Dev& d, const TsParam
     if (r == DV_DONE) {
       const int vid = d.active[i];
       if (S.calls > 0) d.tier_hint[vid] = (uint8_t)cost_bits(S.expansions);
-      atomicAdd((unsigned long long*)&d.cnt->astar_calls, (unsigned long long)S.calls);
-      atomicAdd((unsigned long long*)&d.cnt->astar_exp, (unsigned long long)S.expansions);
-      atomicAdd((unsigned long long*)&d.cnt->astar_relax, (unsigned long long)S.relaxations);
-      if (q.owned_list) q.owned_list[atomicAdd(&d.cnt->replan_n[6], 1)] = i;
-    } else if (r == DV_POOL_FULL) q.retry_list[atomicAdd(&d.cnt->replan_n[4], 1)] = i;
-    else { atomicAdd(&qs.stats[r == DV_BAIL ? QST_BAIL : QST_OVERFLOW], 1ull); __hip_atomic_store(&q.fallback_list[atomicAdd(&d.cnt->quad_n[0], 1)], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }     // DV_BAIL, DV_OVERFLOW: k_replan takes the vehicle
+      searcher_account(d, S.calls, S.expansions, S.relaxations);
+      if (q.owned_list) q.owned_list[atomicAdd(&d.cnt->replan.owned_n, 1)] = i;
+    } else if (r == DV_POOL_FULL) q.retry_list[atomicAdd(&d.cnt->replan.retry_n, 1)] = i;
+    else { atomicAdd(&qs.stats[r == DV_BAIL ? QST_BAIL : QST_OVERFLOW], 1ull); __hip_atomic_store(&q.handback_list[atomicAdd(&d.cnt->handback_n, 1)], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }     // DV_BAIL, DV_OVERFLOW: k_replan takes the vehicle
   }
   return r;
 }
 
-// Replanning vehicles, sixteen per wave: a work queue like k_replan's (class lists `class_mask` selects, most expensive
-// first; cursor quad_n[1]).  Every quad takes entries until the queue is empty; vehicles this searcher cannot carry go
-// to `fallback_list` (counter quad_n[0]) for k_replan.
-__global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs, RLists lists, int class_mask, int32_t* retry_list,
-                                                    int32_t* fallback_list, int rank, int world, int32_t* owned_list) {
+// Replanning vehicles, sixteen per wave: every quad takes the next entry of the queue (RQueue, astar.h) until it is empty;
+// vehicles this searcher cannot carry are handed back to k_replan.
+__global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs, RQueueArgs qa) {
   const int lane = (int)threadIdx.x, j = lane & 3;
   const int slot = (int)blockIdx.x * 16 + (lane >> 2);
   const bool one = j == 0;
-  QQueue q;
-  for (int c = 0; c < 4; c++) { q.l[c] = lists.l[c]; q.n[c] = ((class_mask >> c) & 1) ? d.cnt->replan_n[c] : 0; }
-  replan_class_pos0(d, q.pos0);
-  q.retry_list = retry_list; q.fallback_list = fallback_list; q.owned_list = owned_list; q.rank = rank; q.world = world;
-  const int n3 = q.n[3], n2 = q.n[2], n1 = q.n[1], n0 = q.n[0];
+  const RQueue q = rqueue_open(d, qa);
+  const int n_all = q.n[3] + q.n[2] + q.n[1] + q.n[0];
   QConst K;
   K.tab = (TS_GLOBAL uint32_t*)(uintptr_t)(qs.tab + (size_t)slot * qs.tab_entries);
   K.gq = (gu64p)(uintptr_t)(qs.gq + (size_t)slot * Q_SPILL);
@@ -567,20 +559,16 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
       }
       if (st == QS_ABANDON) {
         if (one) atomicAdd(&qs.stats[s.why & 7], 1ull);
-        if (one) __hip_atomic_store(&fallback_list[atomicAdd(&d.cnt->quad_n[0], 1)], job, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (one) __hip_atomic_store(&q.handback_list[atomicAdd(&d.cnt->handback_n, 1)], job, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         st = QS_NEEDJOB;
       }
       if (st == QS_NEEDJOB) {
         int t = 0;
-        if (one) t = atomicAdd(&d.cnt->quad_n[1], 1);
+        if (one) t = atomicAdd(&d.cnt->quad_cursor, 1);
         t = quad_first(t);
-        if (t >= n3 + n2 + n1 + n0) { st = QS_IDLE; break; }
+        if (t >= n_all) { st = QS_IDLE; break; }
         int i, pos;
-        if (t < n3) { i = q.l[3][t]; pos = q.pos0[3] + t; }
-        else if (t < n3 + n2) { i = q.l[2][t - n3]; pos = q.pos0[2] + t - n3; }
-        else if (t < n3 + n2 + n1) { i = q.l[1][t - n3 - n2]; pos = q.pos0[1] + t - n3 - n2; }
-        else { i = q.l[0][t - n3 - n2 - n1]; pos = q.pos0[0] + t - n3 - n2 - n1; }
-        if (world > 1 && (pos % world) != rank) continue;    // (position in the whole, totally ordered queue, as in replan_turn)
+        if (!rqueue_entry(q, t, i, pos)) continue;
         job = i; n_done = 0;
         st = QS_POLICY;
       }
@@ -647,7 +635,7 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
   }
   // every hand-back of this wave is published before the wave counts itself out (k_replan's replan_turn waits on both)
   __threadfence();
-  if (lane == 0) atomicAdd(&d.cnt->quad_n[3], 1);
+  if (lane == 0) atomicAdd(&d.cnt->quad_waves_done, 1);
 }
 
 }  // namespace

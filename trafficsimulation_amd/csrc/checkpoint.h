@@ -258,7 +258,8 @@ int ck_write(E* e, CkSink& s, uint64_t path_words, bool stage) {
     memcpy(&S.cnt, e->hcnt, sizeof(DevCnt));   // (sync_counters has just read it)
     // the bump allocator's position depends on the pool's layout, the profiling / debugging words are not state
     S.cnt.pool_used = 0;
-    memset(S.cnt.qprof, 0, sizeof(S.cnt.qprof)); memset(S.cnt.prof, 0, sizeof(S.cnt.prof)); memset(S.cnt.dbg, 0, sizeof(S.cnt.dbg));
+    memset(S.cnt.qprof, 0, sizeof(S.cnt.qprof)); memset(S.cnt.prof, 0, sizeof(S.cnt.prof));
+    S.cnt.probe_cycles = S.cnt.probe_wall = S.cnt.spill_exp = 0; S.cnt.max_heap = S.cnt.max_search_exp = 0;
   }
   s.val(S);
   // --- host containers (unordered ones in key order)

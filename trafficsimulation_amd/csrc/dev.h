@@ -33,6 +33,12 @@ constexpr uint32_t NO_RANK = 0xFFFFFFFFu;
 constexpr uint8_t F_DRAW_MALF = 1, F_DRAW_SWIPE = 2, F_DRAW_SPEED = 4;
 constexpr uint32_t WORDS_MASK = (1u << 23) - 1;  // = MTPipe::TW_CAP - 1
 
+struct ReplanCtl {  // the counters of the replanning work queue (RQueue, astar.h): DevCnt::replan, mirrored in HostMirror::replan
+  int class_n[4];  // class list lengths: k_decide_main counts, the replanning kernels read, requeue_in_list0 rewrites
+  int retry_n;     // entries that found the path pool full (retry_list): the replanning kernels count, the host reads
+  int cursor;      // k_replan's queue cursor: replan_turn pops, the host zeroes it with the whole struct
+  int owned_n, spare_;  // entries this rank planned (owned_list, sharded runs): the replanning kernels count, export_replans reads
+};
 struct DevCnt {
   long long stuck, collisions, malfunctions, overtaking, in_stuck_detour, parked, live_internal, live_through,
       completed_internal, completed_through, dist_internal, dist_through;
@@ -41,8 +47,11 @@ struct DevCnt {
   int deaths;      // vehicles removed this tick
   int arr_n;       // service records written this tick (Dev::arr)
   int error;       // sticky device-side error
-  int replan_n[8]; // replanning work queue: [0..3] class list lengths, [4] pool-full retries, [5] queue cursor, [6] entries this rank planned
-  int quad_n[4];   // k_replan_quad: [0] vehicles handed back to k_replan, [1] its queue cursor
+  ReplanCtl replan;      // the replanning work queue (RQueue, astar.h); the host mirrors it whole (HostMirror::replan)
+  int handback_n;        // the hand-back protocol (RQueue, astar.h; zeroed before a quad pass): produced - the quads count, replan_turn and the host read
+  int quad_cursor;       // the quads' queue cursor: the quads pop, replan_turn reads it as a sign of progress
+  int handback_claimed;  // hand-backs claimed: replan_turn's tickets, the host reads how many were served
+  int quad_waves_done;   // quad waves that have counted themselves out: k_replan_quad's last act, replan_turn waits on it
   unsigned long long pool_used;  // words handed out from the path pool (device-side bump allocator)
   long long astar_calls, astar_exp, astar_relax;
   long long errored_internal, errored_through;   // _despawn_check removals
@@ -52,8 +61,12 @@ struct DevCnt {
   int dec_arrived; // 1 + decide index of the vehicle that despawned inside this stretch of the decide phase (0 = none)
   long long qprof[8];  // TS_QUAD_PROF builds: cycles per segment of k_replan_quad's turn (lane 0 of every wave)
   long long prof[8];   // TS_KPROF builds: cycles per segment of the last search's loop
-  int dbg[8];      // debugging aid: first watchdog that fired inside a replanning kernel (code, vehicle index, values)
+  long long probe_cycles, probe_wall;  // diagnostics, not state: k_astar_single writes cycles / 100 MHz ticks of its search; ts_debug_read reads
+  int max_heap, max_search_exp;        // astar_wave raises: deepest heap / longest search so far; run_replans and ts_debug_read read
+  long long spill_exp;                 // astar_wave adds: expansions with part of the heap in HBM; run_replans and ts_debug_read read
 };
+static_assert(sizeof(DevCnt) == 408 && offsetof(DevCnt, replan) == 128 && offsetof(DevCnt, quad_waves_done) == 172 && offsetof(DevCnt, probe_cycles) == 376 &&
+              offsetof(DevCnt, spill_exp) == 400, "DevCnt is stored in checkpoints as it is (CK_VERSION 1): members keep their offsets");
 
 // Everything the hot kernels read or write about one grid cell, in one 32-byte sector: the four move-phase claim
 // words (plane 0 = writers of occupancy, 1 = readers of occupancy, 2 = writers of stop, 3 = readers of stop), the head

@@ -65,24 +65,18 @@ int read_back(E* e, void* dst, const void* src, size_t bytes) {
   return TS_OK;
 }
 
-// The replanning work queue (k_replan): replan_n[0..3] = class list lengths as k_decide_main left them (e->hm->replan_n),
-// lists 0..3 = the classes, list 4 = entries that found the path pool full.
-inline int replan_pending(const int* n8) { return n8[0] + n8[1] + n8[2] + n8[3]; }
+// entries in the replanning work queue (RQueue, astar.h) as k_decide_main or the last pass left it
+inline int replan_pending(const ReplanCtl& r) { return r.class_n[0] + r.class_n[1] + r.class_n[2] + r.class_n[3]; }
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 
 constexpr int SEG_VEHICLES = 1 << 20;   // vehicles per decide pass (bounds one pass' look-ahead into the MT19937 word ring)
-
-inline RLists replan_lists(const E* e) {
-  RLists rl;
-  for (int q = 0; q < 6; q++) rl.l[q] = e->replan_list[q];
-  return rl;
-}
 
 // Order class list h (n entries) by its sort key.  Sharded, the order must be total and the same on every rank: 64-bit keys
 // that end in the entry itself; otherwise key/value pairs.
 int sort_replan_list(E* e, int h, int n, bool sharded) {
   Dev& d = e->d;
   hipStream_t st = e->stream;
-  int32_t* list = e->replan_list[h];
+  int32_t* list = e->class_list.l[h];
   if ((size_t)n > e->cap_sortbuf) {
     const size_t nc = (size_t)n * 2;
     TRY(regrow(e, &e->sort_keys, 0, nc * 2));          // (room for 64-bit keys)
@@ -109,7 +103,7 @@ int sort_replan_list(E* e, int h, int n, bool sharded) {
 }
 
 // What is left of a replanning pass becomes the whole queue, in list 0: `left` entries of `handed_back` (the quads' hand-backs
-// k_replan did not get to), then the `retry` entries that found the path pool full, once there is room for them.  replan_n[6]
+// k_replan did not get to), then the `retry` entries that found the path pool full, once there is room for them.  owned_n
 // (the entries this rank planned) is kept.
 int requeue_in_list0(E* e, const int32_t* handed_back, int left, int retry) {
   Dev& d = e->d;
@@ -118,39 +112,46 @@ int requeue_in_list0(E* e, const int32_t* handed_back, int left, int retry) {
     d.pool_cap_words = e->pool_cap;
     TRY(pool_make_room(e, (size_t)retry * 1024 + (1u << 20)));
   }
-  if (left > 0) HIPOK(hipMemcpyAsync(e->replan_list[0], handed_back, (size_t)left * 4, hipMemcpyDeviceToDevice, st));
-  if (retry > 0) HIPOK(hipMemcpyAsync(e->replan_list[0] + left, e->replan_list[4], (size_t)retry * 4, hipMemcpyDeviceToDevice, st));
-  int* rn = e->hm->replan_n;
-  const int keep_owned = rn[6];
-  for (int q = 0; q < 8; q++) rn[q] = 0;
-  rn[0] = left + retry; rn[6] = keep_owned;
-  HIPOK(hipMemcpyAsync(d.cnt->replan_n, rn, sizeof(int) * 8, hipMemcpyHostToDevice, st));
+  if (left > 0) HIPOK(hipMemcpyAsync(e->class_list.l[0], handed_back, (size_t)left * 4, hipMemcpyDeviceToDevice, st));
+  if (retry > 0) HIPOK(hipMemcpyAsync(e->class_list.l[0] + left, e->retry_list, (size_t)retry * 4, hipMemcpyDeviceToDevice, st));
+  ReplanCtl& r = e->hm->replan;
+  const int keep_owned = r.owned_n;
+  r = ReplanCtl{};
+  r.class_n[0] = left + retry; r.owned_n = keep_owned;
+  HIPOK(hipMemcpyAsync(&d.cnt->replan, &r, sizeof(ReplanCtl), hipMemcpyHostToDevice, st));
   return TS_OK;
 }
 
+// The end of a replanning pass: the queue's counters and the sticky error come back; a search that outgrew its buffers fails the tick
+int replan_pass_done(E* e) {
+  HIPOK(hipMemcpyAsync(&e->hm->replan, &e->d.cnt->replan, sizeof(ReplanCtl), hipMemcpyDeviceToHost, e->stream));
+  TRY(read_back(e, &e->hm->error, &e->d.cnt->error, sizeof(int)));
+  return e->hm->error == TS_E_CAPACITY ? fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers") : TS_OK;
+}
+
 // The quad pass of a big queue (see run_replans): the classes in TS_QUAD_CLASSES go to k_replan_quad while k_replan serves the
-// others and the quads' hand-backs beside it.  What neither got to is queued again in list 0.
-int run_quad_pass(E* e, const RLists& rl) {
+// others and the quads' hand-backs beside it (RQueue, astar.h).  What neither got to is queued again in list 0.
+int run_quad_pass(E* e) {
   Dev& d = e->d;
   const TsParams& P = e->P;
   hipStream_t st = e->stream;
   HostMirror& hm = *e->hm;
-  const int quad_mask = getenv("TS_QUAD_CLASSES") ? atoi(getenv("TS_QUAD_CLASSES")) & 15 : 7;
-  int nq = 0, nw = 0;
-  for (int c = 0; c < 4; c++) { if ((quad_mask >> c) & 1) nq += hm.replan_n[c]; else nw += hm.replan_n[c]; }
+  const int quad_mask = env_int("TS_QUAD_CLASSES", 7) & 15;
+  int nq = 0, nw = 0, qgrid = 0;
+  for (int c = 0; c < 4; c++) { if ((quad_mask >> c) & 1) nq += hm.replan.class_n[c]; else nw += hm.replan.class_n[c]; }
   const double tl = now_ms();
   TRY(arena_to_quads(e));
-  HIPOK(hipMemsetAsync(d.cnt->quad_n, 0, sizeof(int) * 4, st));
+  HIPOK(hipMemsetAsync(&d.cnt->handback_n, 0, sizeof(int) * 4, st));      // (the four hand-back words, handback_n .. quad_waves_done)
   int tok = prof_begin(e, PK_REPLAN, nq + nw);
-  int qgrid = 0;
+  RQueueArgs qa = {.lists = e->class_list, .class_mask = quad_mask, .retry_list = e->retry_list, .handback_list = e->handback_list,
+                   .rank = e->dist_rank, .world = e->dist_world, .owned_list = e->dist_world > 1 ? e->owned_list : nullptr, .fb_waves = 0};
   if (nq > 0) {
-    HIPOK(hipMemsetAsync(e->replan_list[5], 0xFF, (size_t)nq * 4, st));     // (hand-back entries: -1 = not written yet)
+    HIPOK(hipMemsetAsync(e->handback_list, 0xFF, (size_t)nq * 4, st));     // (hand-back entries: -1 = not written yet)
     HIPOK(hipEventRecord(e->quad_ev0, st));
     HIPOK(hipStreamWaitEvent(e->quad_stream, e->quad_ev0, 0));
     qgrid = std::min((nq + 15) / 16, e->qslots.n_slots / 16);
     if (g_trace_launches) { fprintf(stderr, "[launch] k_replan_quad items=%d grid=%d\n", nq, qgrid); fflush(stderr); }
-    hipLaunchKernelGGL(k_replan_quad, dim3(qgrid), dim3(64), 0, e->quad_stream, d, P, e->qslots, rl, quad_mask, e->replan_list[4],
-                       e->replan_list[5], e->dist_rank, e->dist_world, e->dist_world > 1 ? e->owned_list : nullptr);
+    hipLaunchKernelGGL(k_replan_quad, dim3(qgrid), dim3(64), 0, e->quad_stream, d, P, e->qslots, qa);
     HIPOK(hipEventRecord(e->quad_ev1, e->quad_stream));
   }
   // (k_replan never holds anything the quads wait for: were the two launches ever serialised, it would simply find the
@@ -158,28 +159,25 @@ int run_quad_pass(E* e, const RLists& rl) {
   // k_replan's waves beside the quads serve the most expensive class and the quads' hand-backs: 512 of them for a wave that hands back
   // thousands, 384 once the previous wave handed back few (they take issue slots from the quads: measured on the bench workload's four
   // waves, 5 678 / 2 895 / 1 379 / 2 514 hand-backs: 4.18 / 3.65 / 3.22 / 2.69 s with 512, 4.56 / 3.33 / 2.88 / 2.44 s with 384)
-  const int side_waves = getenv("TS_QUAD_SIDE_WAVES") ? atoi(getenv("TS_QUAD_SIDE_WAVES"))
-                                                      : (e->quad_last_fb < 0 || e->quad_last_fb > 4096 ? 512 : 384);
+  const int side_waves = env_int("TS_QUAD_SIDE_WAVES", e->quad_last_fb < 0 || e->quad_last_fb > 4096 ? 512 : 384);
   const int wgrid = std::min(e->side_slots, std::max(std::min(nw, e->side_slots), nq > 0 ? side_waves : 1));
-  if (nw > 0 || nq > 0)
-    hipLaunchKernelGGL(k_replan, dim3(wgrid), dim3(64), 0, st, d, P, e->slots, rl, e->replan_list[4], e->dist_rank,
-                       e->dist_world, e->dist_world > 1 ? e->owned_list : nullptr, 15 & ~quad_mask, e->replan_list[5], qgrid, nq);
+  qa.class_mask = 15 & ~quad_mask; qa.fb_waves = qgrid;
+  if (nw > 0 || nq > 0) hipLaunchKernelGGL(k_replan, dim3(wgrid), dim3(64), 0, st, d, P, e->slots, qa);
   if (nq > 0) HIPOK(hipStreamWaitEvent(st, e->quad_ev1, 0));
   prof_end(e, tok);
-  int qn[4] = {0, 0, 0, 0};
+  struct { int handback_n, quad_cursor, handback_claimed, quad_waves_done; } hb{};   // (the four words, as in DevCnt)
   unsigned long long qst[QST_N];
-  HIPOK(hipMemcpyAsync(hm.replan_n, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
-  HIPOK(hipMemcpyAsync(&hm.error, &d.cnt->error, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPOK(hipMemcpyAsync(qst, e->qslots.stats, sizeof(qst), hipMemcpyDeviceToHost, st));
-  TRY(read_back(e, qn, d.cnt->quad_n, sizeof(int) * 4));
+  HIPOK(hipMemcpyAsync(&hb, &d.cnt->handback_n, sizeof(hb), hipMemcpyDeviceToHost, st));
+  const int rc = replan_pass_done(e);
+  if (rc && rc != TS_E_CAPACITY) return rc;   // (a capacity failure - fail() hands TS_E_CAPACITY back - waits until the pass' statistics are kept)
   HIPOK(hipMemsetAsync(e->qslots.stats, 0, sizeof(qst), st));
   for (int k = 0; k < QST_N; k++) e->quad_stats[k] += (long long)qst[k];
   e->quad_passes++;
   if (g_trace_launches) { fprintf(stderr, "[done] replanning pass with the quads\n"); fflush(stderr); }
-  if (hm.error == TS_E_CAPACITY) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
-  const int fb = qn[0], retry = hm.replan_n[4];
-  e->quad_jobs += nq; e->quad_fallbacks += fb;
-  e->quad_last_fb = fb;
+  TRY(rc);
+  const int retry = hm.replan.retry_n, fb = hb.handback_n;
+  e->quad_jobs += nq; e->quad_fallbacks += fb; e->quad_last_fb = fb;
 #ifdef TS_QUAD_PROF
   {
     long long pf[8];
@@ -187,11 +185,11 @@ int run_quad_pass(E* e, const RLists& rl) {
     fprintf(stderr, "[quadprof] wave cycles %lld, in the lockstep loop %lld, wave turns %lld, quad turns %lld: %.0f cycles per turn, %.1f quads per turn\n",
             pf[0], pf[1], pf[2], pf[3], pf[2] ? (double)pf[1] / (double)pf[2] : 0.0, pf[2] ? (double)pf[3] / (double)pf[2] : 0.0);
     HIPOK(hipMemset(d.cnt->prof, 0, sizeof(pf)));
-    long long qp[8];
-    HIPOK(hipMemcpy(qp, d.cnt->qprof, sizeof(qp), hipMemcpyDeviceToHost));
+    long long qf[8];
+    HIPOK(hipMemcpy(qf, d.cnt->qprof, sizeof(qf), hipMemcpyDeviceToHost));
     fprintf(stderr, "[quadprof] per wave turn: pop+loads %.0f, sift LDS %.0f, sift deep %.0f, goal/stale %.0f, eval %.0f, pushes(+skipped) %.0f, tail %.0f, between turns %.0f\n",
-            (double)qp[0] / pf[2], (double)qp[1] / pf[2], (double)qp[2] / pf[2], (double)qp[3] / pf[2], (double)qp[4] / pf[2], (double)qp[5] / pf[2], (double)qp[6] / pf[2], (double)qp[7] / pf[2]);
-    HIPOK(hipMemset(d.cnt->qprof, 0, sizeof(qp)));
+            (double)qf[0] / pf[2], (double)qf[1] / pf[2], (double)qf[2] / pf[2], (double)qf[3] / pf[2], (double)qf[4] / pf[2], (double)qf[5] / pf[2], (double)qf[6] / pf[2], (double)qf[7] / pf[2]);
+    HIPOK(hipMemset(d.cnt->qprof, 0, sizeof(qf)));
   }
 #endif
   if (getenv("TS_DEBUG_REPLAN")) {
@@ -208,16 +206,14 @@ int run_quad_pass(E* e, const RLists& rl) {
   }
   // what k_replan did not get to serve of the hand-backs (it only gives up on them when the two kernels were not run side
   // by side) and what found the path pool full is queued again
-  const int served = std::min(qn[2], fb);
-  return requeue_in_list0(e, e->replan_list[5] + served, fb - served, retry);
+  const int served = std::min(hb.handback_claimed, fb);
+  return requeue_in_list0(e, e->handback_list + served, fb - served, retry);
 }
 
-int run_replans(E* e) {   // e->hm->replan_n = the queue as k_decide_main left it
+int run_replans(E* e) {   // e->hm->replan = the queue as k_decide_main left it
   Dev& d = e->d;
   const TsParams& P = e->P;
-  hipStream_t st = e->stream;
   HostMirror& hm = *e->hm;
-  const RLists rl = replan_lists(e);
   TRY(ensure_slots(e));
   if (!e->density_valid) { TRY(ensure_density(e, d.occ_snap)); e->density_valid = true; }
   TRY(ensure_amap(e));
@@ -226,8 +222,8 @@ int run_replans(E* e) {   // e->hm->replan_n = the queue as k_decide_main left i
   // (TS_DEBUG_POOL_PER_ENTRY shrinks the reservation so that tests can walk the pool-full retry path)
   const char* dbg_per = getenv("TS_DEBUG_POOL_PER_ENTRY");
   const size_t per_entry = dbg_per ? (size_t)atoi(dbg_per) : 128;
-  TRY(pool_make_room(e, (size_t)replan_pending(hm.replan_n) * per_entry + (dbg_per ? 64u : (1u << 20))));
-  if (dbg_per) d.pool_cap_words = std::min(e->pool_cap, e->pool_used + (size_t)replan_pending(hm.replan_n) * per_entry + 64u);
+  TRY(pool_make_room(e, (size_t)replan_pending(hm.replan) * per_entry + (dbg_per ? 64u : (1u << 20))));
+  if (dbg_per) d.pool_cap_words = std::min(e->pool_cap, e->pool_used + (size_t)replan_pending(hm.replan) * per_entry + 64u);
   if (dbg_per && getenv("TS_DEBUG_REPLAN")) fprintf(stderr, "[replan] pool used %zu cap %zu -> logical cap %llu\n", e->pool_used, e->pool_cap, d.pool_cap_words);
   // Order every class list by expected cost (largest first: the longest search of a tick bounds it) and, among equals, in
   // space (Morton order of 32 x 32-cell blocks of the vehicles' positions): the searches that run at the same time then
@@ -236,7 +232,7 @@ int run_replans(E* e) {   // e->hm->replan_n = the queue as k_decide_main left i
   static const bool spatial = !getenv("TS_NO_SPATIAL_QUEUE");
   const bool sharded = e->dist_world > 1;      // (then the order must be total and the same on every rank: 64-bit keys, every list)
   for (int h = 0; h < 4 && (spatial || sharded); h++)
-    if (hm.replan_n[h] >= (sharded ? 2 : 256)) TRY(sort_replan_list(e, h, hm.replan_n[h], sharded));
+    if (hm.replan.class_n[h] >= (sharded ? 2 : 256)) TRY(sort_replan_list(e, h, hm.replan.class_n[h], sharded));
   // The quad searcher (astar_quad.h; TS_QUAD=0 switches it off): a big
   // queue (a replanning wave of TS_QUAD_MIN entries or more) sends the classes in TS_QUAD_CLASSES to k_replan_quad (sixteen
   // searches per wave, on its own stream) while k_replan runs beside it on the most expensive class and on every vehicle
@@ -244,23 +240,24 @@ int run_replans(E* e) {   // e->hm->replan_n = the queue as k_decide_main left i
   // Smaller queues are bounded by their longest search, and that one is faster alone on a wave.
   // (a queue is the quads' when it is long against what k_replan can have in flight: 262 144 entries on the 5 751 slots a 4096^2
   // map leaves it, in proportion fewer where its node tables are bigger and its slots fewer - 1 534 at 8192^2)
-  const int quad_min = getenv("TS_QUAD_MIN") ? atoi(getenv("TS_QUAD_MIN"))
-                                             : (int)std::min<long long>(262144, std::max<long long>(16384, 46ll * e->slots.n_slots));
+  const int quad_min = env_int("TS_QUAD_MIN", (int)std::min<long long>(262144, std::max<long long>(16384, 46ll * e->slots.n_slots)));
   bool split_done = false;      // (the queue is split between the ranks once; what is queued again - pool-full entries, hand-backs - is this rank's own)
   // (in the sharded multi-GPU mode the threshold applies to this rank's share: every world-th entry of the queue)
-  const bool quad_queue = replan_pending(hm.replan_n) / std::max(e->dist_world, 1) >= std::max(quad_min, 1);
+  const bool quad_queue = replan_pending(hm.replan) / std::max(e->dist_world, 1) >= std::max(quad_min, 1);
   // (set up with the first replans of a population that will fill such a queue - its first replanning wave - rather than inside that wave)
   const bool quad_soon = e->n_active / std::max(e->dist_world, 1) >= std::max(quad_min, 1);
   if (e->quad_on && (quad_queue || quad_soon)) TRY(ensure_qslots(e));
   if (e->quad_on && e->qslots_ready && quad_queue) {
-    TRY(run_quad_pass(e, rl));
+    TRY(run_quad_pass(e));
     split_done = true;
   }
-  while (replan_pending(hm.replan_n) > 0) {
-    const int n = replan_pending(hm.replan_n);
+  while (replan_pending(hm.replan) > 0) {
+    const int n = replan_pending(hm.replan);
     const int grid = std::min(n, e->slots.n_slots);
     if (grid > e->side_slots && e->quad_on) TRY(arena_to_waves(e));
-    const int w_rank = split_done ? 0 : e->dist_rank, w_world = split_done ? 1 : e->dist_world;
+    const RQueueArgs qa = {.lists = e->class_list, .class_mask = 15, .retry_list = e->retry_list, .handback_list = nullptr,
+                           .rank = split_done ? 0 : e->dist_rank, .world = split_done ? 1 : e->dist_world,
+                           .owned_list = e->dist_world > 1 ? e->owned_list : nullptr, .fb_waves = 0};
     split_done = true;
 #ifdef TS_TRACE_REPLAN
     static int4* tr_buf = nullptr;
@@ -270,13 +267,11 @@ int run_replans(E* e) {   // e->hm->replan_n = the queue as k_decide_main left i
       HIPOK(hipMemcpyToSymbol(HIP_SYMBOL(g_rtrace), &tr_buf, sizeof(tr_buf)));
       HIPOK(hipMemcpyToSymbol(HIP_SYMBOL(g_rtrace_cap), &tr_cap, sizeof(tr_cap)));
     }
-    HIPOK(hipMemsetAsync(tr_buf, 0, (size_t)std::min(n, tr_cap) * sizeof(int4), st));
+    HIPOK(hipMemsetAsync(tr_buf, 0, (size_t)std::min(n, tr_cap) * sizeof(int4), e->stream));
 #endif
-    LAUNCH(e, PK_REPLAN, n, k_replan, dim3(grid), dim3(64), d, P, e->slots, rl, e->replan_list[4], w_rank, w_world,
-           e->dist_world > 1 ? e->owned_list : nullptr, 15, (int32_t*)nullptr, 0, 0);
+    LAUNCH(e, PK_REPLAN, n, k_replan, dim3(grid), dim3(64), d, P, e->slots, qa);
     const double tl = now_ms();
-    HIPOK(hipMemcpyAsync(hm.replan_n, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
-    TRY(read_back(e, &hm.error, &d.cnt->error, sizeof(int)));
+    const int rc = replan_pass_done(e);
 #ifdef TS_TRACE_REPLAN
     if (n >= 1000) {
       std::vector<int4> h((size_t)std::min(n, tr_cap));
@@ -288,16 +283,16 @@ int run_replans(E* e) {   // e->hm->replan_n = the queue as k_decide_main left i
     }
 #endif
     if (getenv("TS_DEBUG_REPLAN")) {
-      int dbg[8];
-      HIPOK(hipMemcpy(dbg, d.cnt->dbg, sizeof(dbg), hipMemcpyDeviceToHost));
+      DevCnt c;
+      HIPOK(hipMemcpy(&c, d.cnt, sizeof(DevCnt), hipMemcpyDeviceToHost));
       fprintf(stderr, "[replan] deepest heap so far %d, longest search so far %d expansions, %lld expansions so far with part of the heap in HBM\n",
-              dbg[4], dbg[5], (long long)(((unsigned long long)(unsigned)dbg[7] << 32) | (unsigned)dbg[6]));
+              c.max_heap, c.max_search_exp, c.spill_exp);
     }
-    if (hm.error == TS_E_CAPACITY) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
-    const int retry = hm.replan_n[4];
+    TRY(rc);
+    const int retry = hm.replan.retry_n;
     if (getenv("TS_DEBUG_REPLAN"))
       fprintf(stderr, "[replan] tick %lld: %d entries (classes %d/%d/%d/%d) on %d searchers, retry=%d, %.2f ms\n", (long long)e->C.step_count,
-              n, hm.replan_n[0], hm.replan_n[1], hm.replan_n[2], hm.replan_n[3], grid, retry, now_ms() - tl);
+              n, hm.replan.class_n[0], hm.replan.class_n[1], hm.replan.class_n[2], hm.replan.class_n[3], grid, retry, now_ms() - tl);
     if (retry == 0) break;
     // the path pool filled up: make room (GC, then growth) and run the entries that could not commit again
     TRY(requeue_in_list0(e, nullptr, 0, retry));
@@ -332,7 +327,7 @@ inline size_t payload_bytes(const XHeader& h) {
 int export_replans(E* e, const DevCnt& before, XHeader& hd, DevCnt& after) {
   Dev& d = e->d;
   hipStream_t st = e->stream;
-  const int n_owned = e->hm->replan_n[6];
+  const int n_owned = e->hm->replan.owned_n;
   TRY(grow(e, &e->d_recs, e->cap_recs, (size_t)std::max(n_owned, 1), (size_t)n_owned * 2 + 1024));
   if (!e->d_xwords_n) HIPOK(dalloc(e, &e->d_xwords_n, 1));
   // the words this rank's replans rewrote, counted first (the pool's growth over the phase is no bound: pool_make_room may
@@ -664,7 +659,7 @@ int prefetch_next_tick(E* e, Roll rl, int nA) {
 
 // The searches the decide phase queued: sharded, this rank's share and the exchange; all of them otherwise
 int dispatch_replans(E* e) {
-  const int n_all = replan_pending(e->hm->replan_n);
+  const int n_all = replan_pending(e->hm->replan);
   if (e->dist_world <= 1) return n_all > 0 ? run_replans(e) : TS_OK;
   // every rank sees the same work lists (as sets): plan this rank's share, then trade results - also when this
   // rank has nothing to plan, the exchange is collective
@@ -682,10 +677,9 @@ int decide_range(E* e, const int lo, const int hi, const int nA) {
   Dev& d = e->d;
   const TsParams& P = e->P;
   hipStream_t st = e->stream;
-  HIPOK(hipMemsetAsync(d.cnt->replan_n, 0, sizeof(int) * 8, st));
+  HIPOK(hipMemsetAsync(&d.cnt->replan, 0, sizeof(ReplanCtl), st));
   const Roll rl = roll_of(P);
   MTPipe& r = e->rng_global;
-  const RLists rlists = replan_lists(e);
   // vehicles per pass (bounds the look-ahead into the word ring); TS_DEBUG_SEG shrinks it so that tests can walk
   // the multi-pass path on small worlds
   static const int SEG = getenv("TS_DEBUG_SEG") ? std::max(64, atoi(getenv("TS_DEBUG_SEG"))) : SEG_VEHICLES;
@@ -717,8 +711,8 @@ int decide_range(E* e, const int lo, const int hi, const int nA) {
       prof_end(e, tok);
     }
     if (seg_end == hi) {  // k_decide_main returns at once if a draw fired (the fix-up below re-runs it)
-      LAUNCH(e, PK_DECIDE_MAIN, hi - lo, k_decide_main, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi, rlists);
-      HIPOK(hipMemcpyAsync(e->hm->replan_n, d.cnt->replan_n, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
+      LAUNCH(e, PK_DECIDE_MAIN, hi - lo, k_decide_main, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi, e->class_list);
+      HIPOK(hipMemcpyAsync(&e->hm->replan, &d.cnt->replan, sizeof(ReplanCtl), hipMemcpyDeviceToHost, st));
     }
     HIPOK(hipMemcpyAsync(&e->hm->rng_event, &d.cnt->rng_event, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     const double t_w3 = now_ms();
@@ -735,8 +729,8 @@ int decide_range(E* e, const int lo, const int hi, const int nA) {
   }
   if (!main_done) {  // the last pass ended with an event at the very last vehicle (or there was no pass left)
     HIPOK(hipMemsetAsync(&d.cnt->rng_event, 0xFF, sizeof(unsigned int), st));
-    LAUNCH(e, PK_DECIDE_MAIN, hi - lo, k_decide_main, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi, rlists);
-    TRY(read_back(e, e->hm->replan_n, d.cnt->replan_n, sizeof(int) * 8));
+    LAUNCH(e, PK_DECIDE_MAIN, hi - lo, k_decide_main, dim3(nblk(hi - lo)), dim3(BLK), d, P, lo, hi, e->class_list);
+    TRY(read_back(e, &e->hm->replan, &d.cnt->replan, sizeof(ReplanCtl)));
   }
   if (hi == nA) TRY(prefetch_next_tick(e, rl, nA));
   return dispatch_replans(e);
@@ -2090,7 +2084,11 @@ int ts_set_replan_sharding_device(ts_handle e, int32_t rank, int32_t world, ts_e
 int ts_debug_read(ts_handle e, int32_t* out8) {
   if (!e || !out8) return TS_E_INVALID;
   HIPOK(hipStreamSynchronize(e->stream));
-  HIPOK(hipMemcpy(out8, e->d.cnt->dbg, sizeof(int) * 8, hipMemcpyDeviceToHost));
+  DevCnt c;
+  HIPOK(hipMemcpy(&c, e->d.cnt, sizeof(DevCnt), hipMemcpyDeviceToHost));
+  // words 0-1 / 2-3: the last ts_astar's cycles / 100 MHz ticks; 4: deepest heap; 5: longest search; 6-7: spilled expansions
+  const long long w64[4] = {c.probe_cycles, c.probe_wall, ((long long)c.max_search_exp << 32) | (unsigned)c.max_heap, c.spill_exp};
+  memcpy(out8, w64, sizeof(w64));
   if (getenv("TS_KPROF")) {
     long long pr[8];
     HIPOK(hipMemcpy(pr, e->d.cnt->prof, sizeof(pr), hipMemcpyDeviceToHost));
