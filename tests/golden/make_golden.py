@@ -177,6 +177,9 @@ SCENARIOS = {
                                       "TOTAL_SERVICE_VEHICLES_FOOD": 150, "TOTAL_SERVICE_VEHICLES_WASTE": 150,
                                       "INTERNAL_POPULATION_TRAFFIC_PER_DAY": 8000, "PASSING_POPULATION_TRAFFIC_PER_DAY": 3000},
                             model_kwargs=dict(carve_subblock_roads=True)),
+    # a ragged grid: neither side a multiple of the device's 8-cell tile (100 = 12 tiles + 4 cells, 75 = 9 tiles + 3 cells),
+    # closed population under the default replanning policy (the shape of full_96_s8)
+    "ragged_100x75_s33": dict(size=100, height=75, seed=33, vehicles=220, ticks=70, defaults={**CLOSED}),
     # constructor variants of the world under a live run (every subsystem on): full-width intersections, a highway ring,
     # no ring road, forward light ranges feeding the neighbour-pressure controller's "out" lanes
     "unopt_96_s21": dict(size=96, seed=21, vehicles=60, ticks=200, defaults={"TRAFFIC_LIGHT_AGENT_ALGORITHM": "NEIGHBOR_GREEN_WAVE"},

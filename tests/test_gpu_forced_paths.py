@@ -51,7 +51,7 @@ def test_smallheap_astar_cost_kats(hip_small, golden_dir, name, tag):
     P.K.run_astar_cost_kats(hip_small, golden_dir, name, tag)
 
 
-@pytest.mark.parametrize("name", ["full_96_s8", "default_200_s20", "costs_int_96_s31", "costs_frac_96_s32"])
+@pytest.mark.parametrize("name", ["full_96_s8", "default_200_s20", "costs_int_96_s31", "costs_frac_96_s32", "ragged_100x75_s33"])
 def test_smallheap_reproduces_reference_trace(hip_small, name):
     P.test_hip_reproduces_reference_trace(hip_small, name)
 

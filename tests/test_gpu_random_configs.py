@@ -64,9 +64,11 @@ def random_case(case: int):
     return size, vehicles, d, with_manager, int(rng.integers(1, 10 ** 6))
 
 
-def run_case(case, make_engines, ticks=45):
+def run_case(case, make_engines, ticks=45, shape=None):
+    """shape: (W, H) of the world in place of the case's own square one; every other draw of the case stays what it is."""
     size, vehicles, d, with_manager, seed = random_case(case)
-    tb = dict(citygen.generate(size, size, seed=seed % 97 + 1))
+    W, H = shape if shape is not None else (size, size)
+    tb = dict(citygen.generate(W, H, seed=seed % 97 + 1))
     if with_manager:   # RainManager scheduled behind the clock agent (city_model.py:198-204 order: manager, then DTA)
         kinds = list(np.asarray(tb["schedule_kinds0"]))
         tb["schedule_kinds0"] = np.asarray(kinds[:-1] + [2] + kinds[-1:], dtype=np.int8)
@@ -92,7 +94,7 @@ def run_case(case, make_engines, ticks=45):
             e.add_vehicles_dirs(sg_cells, sg_cells, np.full(n_sg, capi.POP["through"], np.int32), np.zeros(n_sg + 1, np.int64),
                                 np.zeros(0, np.uint8))
     a, b = apis
-    ctx0 = f"case {case} ({size}x{size}, {len(s)} vehicles, {d['TRAFFIC_LIGHT_AGENT_ALGORITHM']})"
+    ctx0 = f"case {case} ({W}x{H}, {len(s)} vehicles, {d['TRAFFIC_LIGHT_AGENT_ALGORITHM']})"
     for t in range(ticks):
         if n_sg and t == 12:
             for e in apis:

@@ -25,6 +25,9 @@ DTA_TRACES = ["dta_64_s12", "dta_96_s13"]
 RAIN_TRACES = ["rain_96_s14"]
 SERVICE_TRACES = ["service_64_s15", "service_heavy_96_s16", "config1_64_s11", "config5_96_s17"]
 RECT_TRACES = ["rect_96x64_s18", "rect_64x112_s19"]   # non-square grids, every subsystem on
+# neither side a multiple of the 8-cell tile of the device's A* snapshot and tables (100 = 12 tiles + 4, 75 = 9 tiles + 3):
+# closed population under the default replanning policy
+RAGGED_TRACES = ["ragged_100x75_s33"]
 # constructor variants under a live run
 VARIANT_TRACES = ["unopt_96_s21", "ring_r1_112_s22", "noring_96_s23", "fwdrange_96_s24"]
 # VEHICLE_STUCK_DESPAWN_ENABLED with low thresholds (_despawn_check fires); VEHICLE_RESPECT_AWARENESS (field-of-view masking
