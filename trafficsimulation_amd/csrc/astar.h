@@ -62,16 +62,25 @@ struct __attribute__((aligned(8))) TEnt { int32_t dist; uint32_t meta; };   // m
 constexpr uint32_t T_STAMP_SHIFT = 14, T_STEPS_MASK = 0xFFF, T_STAMP_MAX = TS_DEBUG_STAMP_MAX;
 constexpr int A_STEPS_MAX = (int)T_STEPS_MASK - 1;   // largest binding step limit a search can carry (a limit >= N never binds)
 
-__shared__ unsigned long long g_lq[LDS_HEAP];   // packed HQ: f in the low word, cell in the high word
-__shared__ int8_t g_ld[LDS_HEAP];
+// (slot LDS_HEAP of both arrays is a spare no search reads: a lane-predicated store sends its idle lanes there instead of
+// switching them off, which would cost an exec-mask bracket - two scalar instructions and a branch - per store)
+__shared__ unsigned long long g_lq[LDS_HEAP + 1];   // packed HQ: f in the low word, cell (y << 16 | x) in the high word
+__shared__ int8_t g_ld[LDS_HEAP + 1];
 __shared__ int g_job;   // the work-queue entry the wave is on (wave_pop)
+// a workgroup's LDS, rounded up to 1 280-byte allocation granules: twenty-four searchers must fit the 160 KB of a CU
+// (astar_quad.h checks the mix of a replanning wave: the quads' waves with two side waves of k_replan beside them)
+constexpr size_t REPLAN_LDS_BYTES = ((LDS_HEAP + 1) * (sizeof(unsigned long long) + 1) + sizeof(int) + 16 + 1279) / 1280 * 1280;
+static_assert(REPLAN_LDS_BYTES * 4 * TS_REPLAN_WAVES <= 160 * 1024, "the LDS heaps of TS_REPLAN_WAVES searchers per SIMD must fit a CU");
+// heap entries carry the cell as packed coordinates: 16 bits each (ts_create refuses wider / taller maps)
+constexpr int A_XY_MAX = 0xFFFF;
+__device__ __forceinline__ int xy_pack(int x, int y) { return (int)(((uint32_t)y << 16) | (uint32_t)x); }
 
 // One searcher's scratch: LDS heap (above) + its slot of the HBM arena.
 struct AScratch {
   HQ* gq;        // heap slots [LDS_HEAP, heap_cap), indexed by slot - LDS_HEAP
   int8_t* gd;    // dir_arr for the same slots: indexed by heap SLOT and deliberately not moved by the sift routines
   int heap_cap;
-  TEnt* tab;     // one record per search node (Dev::n_nodes), nodes numbered in tiled order
+  TEnt* tab;     // one record per search node (Dev::n_nodes), nodes numbered in tiled order, and one spare behind them
   uint32_t epoch;
   int32_t *A, *P, *T, *PO, *PD;  // cap cells each: A* result, current new path, splice target, staged pre-paths
   int32_t *BYP, *OV, *DV;        // MAXB cells each: bypass result, staged overtake / detour paths
@@ -90,7 +99,7 @@ struct RLists { int32_t* l[4]; };       // the replanning queue's class lists (R
 
 struct ASlots {
   int n_slots, heap_cap, cap, use_reach;
-  size_t tab_entries;    // per slot
+  size_t tab_entries;    // per slot: max(n_nodes, 1) + 1 (the last one is the spare that idle lanes' stores go to)
   TEnt* tab;
   HQ* gq;
   int8_t* gd;
@@ -193,11 +202,27 @@ template <bool SPILL> __device__ __forceinline__ void hd_put(gi8p gd, int k, int
   if constexpr (SPILL) { if (k < LDS_HEAP) g_ld[k] = (int8_t)v; else gd[k - LDS_HEAP] = (int8_t)v; }
   else g_ld[k] = (int8_t)v;
 }
+// the same for the lanes with `p` only, without switching the others off: every lane stores to LDS, an idle lane (and, in
+// the spill form, one whose slot lies in HBM) to the spare slot; only the HBM part of the spill form keeps its branch
+template <bool SPILL> __device__ __forceinline__ void hq_put_if(gu64p gq, bool p, int k, u64 v) {
+  if constexpr (SPILL) {
+    const bool lo = p & (k < LDS_HEAP);
+    g_lq[lo ? k : LDS_HEAP] = v;
+    if (p & !lo) gq[k - LDS_HEAP] = v;
+  } else g_lq[p ? k : LDS_HEAP] = v;
+}
+template <bool SPILL> __device__ __forceinline__ void hd_put_if(gi8p gd, bool p, int k, int v) {
+  if constexpr (SPILL) {
+    const bool lo = p & (k < LDS_HEAP);
+    g_ld[lo ? k : LDS_HEAP] = (int8_t)v;
+    if (p & !lo) gd[k - LDS_HEAP] = (int8_t)v;
+  } else g_ld[p ? k : LDS_HEAP] = (int8_t)v;
+}
 
 // a fresh epoch for the searcher's table (cleared by the wave when the 18-bit stamp wraps)
 __device__ __forceinline__ uint32_t next_epoch(const Dev& d, AScratch& S) {
   if (S.epoch >= T_STAMP_MAX) {
-    const size_t n = (size_t)max(d.n_nodes, 1);
+    const size_t n = (size_t)max(d.n_nodes, 1);     // (the spare record behind them is never read)
     for (size_t q = lane_id(); q < n; q += 64) S.tab[q] = TEnt{0, 0u};
     S.epoch = 0;
     __syncthreads();
@@ -236,13 +261,17 @@ struct ACtx {
   const TS_GLOBAL float* density;
   gi32p outg;
   int heap_cap, out_cap, start_idx, goal_idx, gx, gy, maximum_steps, sx, sy, aw;
+  int goal_xy;            // the goal as a heap entry carries it (xy_pack)
+  uint32_t tab_spare;     // the table record no search reads
   bool fov;
   uint32_t epoch;
   bool soft, ignore_flow, limited, turn_on, rt_on, dens_on;
   double turn_pen, contra_pen, veh_pen, stop_pen, dyn_scale, rt1, rt2, rt3;
   int turn2, contra2, veh2, stop2, rt2_1, rt2_2, rt2_3;     // the same in half units (valid when `half`)
   bool half;
-  long long n_exp, n_relax, n_exp_spill;   // n_exp_spill: expansions made while part of the heap sat in HBM
+  // per search, 32 bits (n_exp <= n_relax + 1: every pop but the first was pushed by a relaxation; the loop gives up with
+  // AL_OVERFLOW before n_relax can wrap); n_exp_spill: expansions made while part of the heap sat in HBM
+  int n_exp, n_relax, n_exp_spill;
   int max_heap;
   long long prof[8], pt;
   __device__ __forceinline__ void xy_of(int cell, int& x, int& y) const {
@@ -288,7 +317,8 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
   const gi8p gd = C.gd;
   const gu64p tab = C.tab;
   const uint32_t epoch = C.epoch, stamp = C.epoch << T_STAMP_SHIFT;
-  const int gx = C.gx, gy = C.gy;
+  const int gx = C.gx, gy = C.gy, goal_xy = C.goal_xy;
+  const uint32_t tab_spare = C.tab_spare;
   // window geometry of this lane (lanes 2..63 = the 62 entries of five levels below a hole that sits on "lane 1")
   const int wlvl = 31 - __builtin_clz((unsigned)max(lane, 1));   // 1 for lanes 2-3, ... 5 for 32-63
   const int woff = lane - (1 << wlvl);
@@ -304,7 +334,11 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
   }
   const int dd_l = lane & 3;
   const int dx_l = lane < 4 ? (dd_l == 1) - (dd_l == 3) : 0, dy_l = lane < 4 ? (dd_l == 0) - (dd_l == 2) : 0;
+  const int dxy_l = dx_l + dy_l * 65536;                           // the same step on packed coordinates
   const unsigned below_l = (1u << lane) - 1u;                      // (lanes 0-3 use it)
+  // One back edge: a stale pop runs the evaluation with every neighbour killed (a few per cent of the pops: cheaper than a
+  // second path to the loop's head with its copies of the loop-carried state), and a turn without relaxations skips
+  // the commit block only.
   while (heap_size > 0) {
     if (!SPILL && heap_size > LDS_HEAP - 4) return AL_SWITCH;        // this turn's pushes might not fit LDS
     if (SPILL && heap_size < LDS_HEAP - 96) return AL_SWITCH;      // (heaps breathe by a few entries per turn: a band of ~90 keeps the switches rare)
@@ -315,20 +349,19 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
     const int prev_dir = uni((int)g_ld[0]);
     const u64 x = uni64(hq_get<SPILL>(gq, heap_size - 1));            // the last entry: it takes the root's place
     const int xd = uni(hd_get<SPILL>(gd, heap_size - 1));
-    const int f_top = uni(hq_f(w0)), cur = uni(hq_i(w0));     // (readfirstlane: lane 0's word, the root)
+    const int f_top = uni(hq_f(w0)), cur = uni(hq_i(w0));     // (readfirstlane: lane 0's word, the root; cur = y << 16 | x)
     heap_size--;
     KP(0);
-    int cx, cy;
-    C.xy_of(cur, cx, cy);
+    const int cx = cur & A_XY_MAX, cy = (int)((unsigned)cur >> 16);
     const int nx_l = cx + dx_l, ny_l = cy + dy_l;
     const bool inb_l = (unsigned)nx_l < (unsigned)W && (unsigned)ny_l < (unsigned)H;
-    const int nidx_l = inb_l ? ny_l * W + nx_l : cur;
-    const uint32_t t_l = inb_l ? C.tile_ix(nx_l, ny_l) : C.tile_ix(cx, cy);
+    const int nidx_l = inb_l ? (int)((uint32_t)cur + (uint32_t)dxy_l) : cur;
+    const uint32_t t_l = C.tile_ix(inb_l ? nx_l : cx, inb_l ? ny_l : cy);    // (the coordinates are selected, not the results: no branch)
     // round 1: the map entries (flags + search-node number); round 2, issued half-way through the sift-down: the table
     // records of those nodes
     const u64 am_l = ld8(C.amap, t_l);
     float dens_l = 0.0f;      // (HALF searches find the cell's vehicle penalty in the map entry itself)
-    if constexpr (!HALF) dens_l = C.density[nidx_l];      // (read whether or not the search is soft: no branch around a load)
+    if constexpr (!HALF) dens_l = C.density[inb_l ? ny_l * W + nx_l : cy * W + cx];      // (read whether or not the search is soft: no branch around a load)
     u64 fr_l = 0;
     if constexpr (FOV) fr_l = ld8(C.fovrun, t_l);
     u64 e_l = 0;
@@ -337,7 +370,7 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
     if (heap_size > 0) {
       const int xf = hq_f(x);
       wave_mem_sync();                     // every lane has read slot 0 before it is overwritten
-      if (lane == 0) g_ld[0] = (int8_t)xd;
+      g_ld[lane == 0 ? 0 : LDS_HEAP] = (int8_t)xd;
       int idx = 0;                         // the hole; x keeps sinking
       for (;;) {
         const int abs_l = ((idx + 1) << wlvl) + woff - 1;
@@ -359,10 +392,12 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
         const unsigned long long pmask = ballot(onp);
         const int k = __builtin_popcountll(pmask);
         const int L = 63 - __builtin_clzll(pmask | 2ull);             // deepest lane on the path; the hole itself (1) if none
-        if (onp) hq_put<SPILL>(gq, (abs_l - 1) >> 1, mine);          // the entries on the path move up one level
         const int abs_end = uni(((idx + 1) << k) + (L - (1 << k)) - 1);
         const bool done = k < 5;
-        if (done & (lane == 0)) hq_put<SPILL>(gq, abs_end, x);
+        // the entries on the path move up one level, and x settles where the hole ends up: one store (lane 0 holds no
+        // entry and is never on the path - it carries x)
+        const bool put_x = done & (lane == 0);
+        hq_put_if<SPILL>(gq, onp | put_x, put_x ? abs_end : (abs_l - 1) >> 1, put_x ? x : mine);
         if (!e_loaded) {                   // the first window is done: the map entries have had time to arrive
           const uint32_t r_l = (uint32_t)(am_l >> 32);
           e_l = ld8(tab, r_l != 0xFFFFFFFFu ? r_l : 0u);
@@ -377,12 +412,12 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
     const uint32_t a_l = (uint32_t)am_l, r_l = (uint32_t)(am_l >> 32);
     const bool node_l = r_l != 0xFFFFFFFFu;
     if (!e_loaded) e_l = ld8(tab, node_l ? r_l : 0u);     // (the heap held a single entry: no sift-down happened)
-    if (cur == C.goal_idx) {
+    if (cur == goal_xy) {
       // walk came_from back to the start, filling the output from its far end, then slide it to the front
       const gi32p outg = C.outg;
       const int out_cap = C.out_cap;
       int len = 0, px = cx, py = cy;
-      for (int c = cur; c != C.start_idx;) {
+      for (int c = cy * W + cx; c != C.start_idx;) {
         if (len >= out_cap) return AL_OVERFLOW;
         if (lane == 0) outg[out_cap - 1 - len] = c;
         len++;
@@ -406,13 +441,10 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
     const u64 e_c = rl(e_l, 4);
     const bool node_c = rl((int)node_l, 4) != 0;     // (only a start cell can be off the node set: dist 0, no steps)
     const uint32_t m_c = node_c ? (uint32_t)(e_c >> 32) : (epoch << T_STAMP_SHIFT);
-    {
-      const int dist_c = !node_c ? 0 : (m_c >> T_STAMP_SHIFT) == epoch ? (int)(uint32_t)e_c : A_INF;
-      if (g > dist_c) continue;
-    }
+    const int dist_c = !node_c ? 0 : (m_c >> T_STAMP_SHIFT) == epoch ? (int)(uint32_t)e_c : A_INF;
+    const bool fresh = g <= dist_c;      // (a stale pop relaxes nothing)
     KP(3);
-    C.n_exp++;
-    if constexpr (SPILL) C.n_exp_spill++;
+    C.n_exp += fresh ? 1 : 0;
     const int steps = C.limited ? (int)((m_c >> 2) & T_STEPS_MASK) : 0;
     const uint32_t bits = (uint32_t)rl((int)a_l, 4) & 15u;
     // ---- lane dd < 4 evaluates neighbour dd from what was fetched before the sift-down -------------------------
@@ -449,7 +481,7 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
         const int occ2 = (int)(a_l >> AMAP_PEN_SHIFT);     // k_amap_build: veh2, or the density-dependent penalty of this cell
         n2 += n_occ ? occ2 : 0;
         n2 += n_stop ? C.stop2 : 0;
-        const int rtp = rt == 1u ? C.rt2_1 : rt == 2u ? C.rt2_2 : rt == 3u ? C.rt2_3 : 0;
+        const int rtp = (rt == 1u ? C.rt2_1 : 0) | (rt == 2u ? C.rt2_2 : 0) | (rt == 3u ? C.rt2_3 : 0);   // (a chain of ?: becomes nested branches)
         n2 += (C.rt_on & n_road) ? rtp : 0;
         ng2_l = n2;
         cheaper = n2 < 2 * dist_l;
@@ -460,46 +492,48 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
         const double occ_pen = C.dens_on ? occ_penalty_dyn(C.veh_pen, C.dyn_scale, dens_l) : C.veh_pen;
         ng_l += n_occ ? occ_pen : 0.0;
         ng_l += n_stop ? C.stop_pen : 0.0;
-        ng_l += (C.rt_on & n_road) ? (rt == 1u ? C.rt1 : rt == 2u ? C.rt2 : rt == 3u ? C.rt3 : 0.0) : 0.0;
+        ng_l += (C.rt_on & n_road) ? ((rt == 1u ? C.rt1 : 0.0) + (rt == 2u ? C.rt2 : 0.0) + (rt == 3u ? C.rt3 : 0.0)) : 0.0;   // (one term at most is not + 0.0: exact)
         cheaper = ng_l < (double)dist_l;
       }
-      ok_l = (lane < 4) & inb_l & node_l & (steps + 1 <= C.maximum_steps) & (flow | (C.ignore_flow & n_road)) & (C.soft | !(n_occ | n_stop)) & cheaper;
+      ok_l = fresh & (lane < 4) & inb_l & node_l & (steps + 1 <= C.maximum_steps) & (flow | (C.ignore_flow & n_road)) & (C.soft | !(n_occ | n_stop)) & cheaper;
     }
     // ---- commit.  The four neighbours are distinct cells, so no relaxation changes another one's test: the table
     // records and the dir bytes of all of them go out with one masked store each; only the heap pushes are made one
     // after the other, in the reference's order N, E, S, W.
     unsigned relax = (unsigned)(ballot(ok_l) & 15ull);
     KP(4);
-    if (relax == 0u) continue;
+    // (the counters move on both paths alike - nothing to copy where they join; heap_size + 0 never exceeds the deepest heap)
     const int n_new = __builtin_popcount(relax);
     C.n_relax += n_new;
-    if (heap_size + n_new > C.heap_cap) return AL_OVERFLOW;
     C.max_heap = max(C.max_heap, heap_size + n_new);
-    const int h_l = abs(nx_l - gx) + abs(ny_l - gy);
-    const int ngi_l = HALF ? (ng2_l >> 1) : (int)ng_l;
-    const u64 ent_l = hq_pack(HALF ? ngi_l + h_l : (int)(ng_l + (double)h_l), nidx_l);
-    if (ok_l) {
-      st8(tab, r_l, (u64)(uint32_t)ngi_l | ((u64)(stamp | (C.limited ? (uint32_t)(steps + 1) << 2 : 0u) | (uint32_t)dd_l) << 32));
-      hd_put<SPILL>(gd, heap_size + __builtin_popcount(relax & below_l), dd_l);
-    }
-    KP(5);
-    while (relax) {
-      const int dd = __builtin_ctz(relax);
-      relax &= relax - 1;
-      const u64 nx64 = rl(ent_l, dd);
-      const int nf = hq_f(nx64);
-      const int i = heap_size;
-      // ancestors of slot i: a_k = ((i + 1) >> k) - 1, k = 1 .. depth; lane k - 1 fetches a_k
-      const int depth = 31 - __builtin_clz((unsigned)(i + 1));
-      const bool has = lane < depth;                                  // depth <= 31: lanes beyond it fetch nothing
-      const int a_mine = (int)(((unsigned)(i + 1) >> ((lane + 1) & 31)) - 1u) & (has ? -1 : 0);
-      const u64 anc = hq_get<SPILL>(gq, a_mine);
-      const unsigned long long rises = ballot(has & (nf < hq_f(anc)));
-      const int r = __builtin_ctzll(~rises);                          // leading ancestors the entry passes (lanes >= 31 never rise)
-      if (lane < r) hq_put<SPILL>(gq, (int)((unsigned)(i + 1) >> (lane & 31)) - 1, anc);   // ancestor k moves to where k - 1 was
-      if (lane == 0) hq_put<SPILL>(gq, ((i + 1) >> r) - 1, nx64);
-      heap_size++;
-      wave_mem_sync();
+    if (relax != 0u) {
+      if ((heap_size + n_new > C.heap_cap) | (C.n_relax > 0x7FFFFFF0)) return AL_OVERFLOW;
+      const int h_l = abs(nx_l - gx) + abs(ny_l - gy);
+      const int ngi_l = HALF ? (ng2_l >> 1) : (int)ng_l;
+      const u64 ent_l = hq_pack(HALF ? ngi_l + h_l : (int)(ng_l + (double)h_l), nidx_l);
+      // (every lane stores: the idle ones to the table's spare record and the spare dir byte)
+      st8(tab, ok_l ? r_l : tab_spare, (u64)(uint32_t)ngi_l | ((u64)(stamp | (C.limited ? (uint32_t)(steps + 1) << 2 : 0u) | (uint32_t)dd_l) << 32));
+      hd_put_if<SPILL>(gd, ok_l, heap_size + __builtin_popcount(relax & below_l), dd_l);
+      KP(5);
+      do {
+        const int dd = __builtin_ctz(relax);
+        relax &= relax - 1;
+        const u64 nx64 = rl(ent_l, dd);
+        const int nf = hq_f(nx64);
+        const int i = heap_size;
+        // ancestors of slot i: a_k = ((i + 1) >> k) - 1, k = 1 .. depth; lane k - 1 fetches a_k
+        const int depth = 31 - __builtin_clz((unsigned)(i + 1));
+        const bool has = lane < depth;                                  // depth <= 31: lanes beyond it fetch nothing
+        const int a_mine = (int)(((unsigned)(i + 1) >> ((lane + 1) & 31)) - 1u) & (has ? -1 : 0);
+        const u64 anc = hq_get<SPILL>(gq, a_mine);
+        const unsigned long long rises = ballot(has & (nf < hq_f(anc)));
+        const int r = __builtin_ctzll(~rises);                          // leading ancestors the entry passes (lanes >= 31 never rise: r <= depth)
+        // ancestor k moves to where k - 1 was (lanes < r), the new entry to where ancestor r was (lane r): slot
+        // ((i + 1) >> lane) - 1 for both - one store
+        hq_put_if<SPILL>(gq, lane <= r, (int)((unsigned)(i + 1) >> (lane & 31)) - 1, lane == r ? nx64 : anc);
+        heap_size++;
+        wave_mem_sync();
+      } while (relax);
     }
     KP(6);
   }
@@ -542,6 +576,7 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
     C.rt2_1 = (int)(C.rt1 * 2.0); C.rt2_2 = (int)(C.rt2 * 2.0); C.rt2_3 = (int)(C.rt3 * 2.0);
   }
   C.n_exp = 0; C.n_relax = 0; C.n_exp_spill = 0; C.max_heap = 0;
+  C.tab_spare = (uint32_t)uni(max(d.n_nodes, 1));
   for (int k = 0; k < 8; k++) C.prof[k] = 0;
   C.pt = clock64();
   // the chain of relaxations behind a heap entry never revisits a cell (dist strictly falls), so it is shorter than
@@ -549,11 +584,12 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
   C.limited = C.maximum_steps < C.N;
   C.xy_of(C.goal_idx, C.gx, C.gy);
   C.xy_of(C.start_idx, C.sx, C.sy);
+  C.goal_xy = xy_pack(C.gx, C.gy);
   const int sx = C.sx, sy = C.sy;
   if (C.lane == 0) {
     const uint32_t sr = (uint32_t)(C.amap[C.tile_ix(sx, sy)] >> 32);
     if (sr != 0xFFFFFFFFu) C.tab[sr] = (u64)0u | ((u64)(C.epoch << T_STAMP_SHIFT) << 32);    // dist 0, steps 0
-    g_lq[0] = hq_pack(abs(sx - C.gx) + abs(sy - C.gy), C.start_idx);
+    g_lq[0] = hq_pack(abs(sx - C.gx) + abs(sy - C.gy), xy_pack(sx, sy));
     g_ld[0] = -1;
   }
   int heap_size = 1;
@@ -566,7 +602,9 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
     for (;;) {
       int q = astar_loop<false, HF, FV>(C, heap_size);
       if (q != AL_SWITCH) return q;
+      const int exp0 = C.n_exp;
       q = astar_loop<true, HF, FV>(C, heap_size);
+      C.n_exp_spill += C.n_exp - exp0;
       if (q != AL_SWITCH) return q;
     }
   };
@@ -575,7 +613,7 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
   S.expansions += C.n_exp; S.relaxations += C.n_relax;
   if (C.lane == 0) {   // profiling aid: deepest heap / longest search any searcher has seen (ts_debug_read words 4, 5)
     atomicMax(&d.cnt->max_heap, C.max_heap);
-    atomicMax(&d.cnt->max_search_exp, (int)min(C.n_exp, (long long)0x7FFFFFFF));
+    atomicMax(&d.cnt->max_search_exp, C.n_exp);
     if (C.n_exp_spill) atomicAdd((unsigned long long*)&d.cnt->spill_exp, (unsigned long long)C.n_exp_spill);
 #ifdef TS_KPROF
     for (int k = 0; k < 8; k++) d.cnt->prof[k] = C.prof[k];

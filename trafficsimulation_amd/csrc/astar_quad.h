@@ -49,6 +49,8 @@ constexpr int QL = TS_QUAD_LCAP;            // heap slots per search in LDS (and
 // (bank spread: the 8-byte slots of the eight quads of a half-wave at the same heap index must fall into different banks)
 static_assert(QL % 8 == 4, "TS_QUAD_LCAP must be 4 mod 8 (LDS bank spread between the quads of a wave)");
 static_assert(((size_t)16 * QL + 64) * 8 * TS_QUAD_WAVES_PER_CU <= 160 * 1024 - 512, "the LDS heaps of TS_QUAD_WAVES_PER_CU waves must fit a CU");
+static_assert(((size_t)16 * QL + 64) * 8 * TS_QUAD_WAVES_PER_CU + 2 * REPLAN_LDS_BYTES <= 160 * 1024,
+              "two side waves of k_replan must fit a CU beside the quads' waves");
 #ifndef TS_QUAD_WINDOW
 #define TS_QUAD_WINDOW 1152
 #endif

@@ -1191,6 +1191,7 @@ int ts_create(const TsWorld* w, const TsParams* params, ts_handle* out) {
         q.rain_speed_reduction < 0 || q.pathfinding_cooldown < 0)
       return TS_E_INVALID;
     if (q.max_contraflow_overtake_steps > MAXB || q.max_contraflow_stuck_detour_steps > MAXB) return TS_E_UNSUPPORTED;
+    if (w->width > A_XY_MAX || w->height > A_XY_MAX) return TS_E_UNSUPPORTED;   // (heap entries carry a cell as 16 + 16 bits)
   }
   E* e = new E();
   memset(&e->d, 0, sizeof(e->d));
