@@ -130,6 +130,52 @@ def test_spawns_between_ticks_with_planner_cache_and_capacity_growth():
     h.close(), c.close()
 
 
+def test_planned_spawn_behind_a_stranded_blocker_commits_its_overtake_paths():
+    """VehicleAgent(...) without a path directly behind a stranded vehicle: the spawn-time planner's phase 3 fires (contraflow
+    overtake: new path = bypass + rest, overtake_path and pre_overtake_path staged) and commits the staged aux paths with the
+    path.  With VEHICLE_STUCK_RECOMPUTE_THRESHOLD = 0 the vehicle's first step_decide replans at once and phase 0 re-merges with
+    the pre_overtake_path the spawn left in the pool.  Blockers: every second vehicle malfunctions per tick (chance 0.5, for
+    good); the spawn points are the route cells behind those that did."""
+    tb = citygen.generate(64, 64, seed=4)
+    s, g, off, dirs = citygen.make_routes(tb, 40, seed=5, min_len=12, max_len=30)
+    rxy = citygen.dirs_to_xy(s, off, dirs)
+    pol = {"RAIN_ENABLED": False, "VEHICLE_MALFUNCTION_CHANCE": 0.5, "VEHICLE_MALFUNCTION_DURATION": 10 ** 6,
+           "VEHICLE_SIDESWIPE_COLLISION_CHANCE": 0.0, "VEHICLE_CONTRAFLOW_OVERTAKE_ACTIVE": True,
+           "VEHICLE_STUCK_RECOMPUTE_THRESHOLD": 0, "VEHICLE_STUCK_RECOMPUTE_THRESHOLD_INTERSECTION": 0}
+    def mk(e):
+        build_engine(e, tb, defaults=pol, global_seed=5, sched_seed=6)
+        e.add_vehicles_dirs(s, g, np.full(len(s), capi.POP["through"], np.int32), off, dirs)
+    h, c = both(mk)
+    h.step(2), c.step(2)
+    same_state(h, c, "blockers")
+    X, Y, F, SI = (capi.V_FIELDS.index(k) for k in ("x", "y", "flags", "spawn_idx"))
+    starts, goals = [], []
+    for row in c.vehicles():
+        if not (row[F] & capi.F_MALFUNCTION):
+            continue
+        i = int(row[SI])
+        cells = np.vstack([np.asarray(s[i]).reshape(1, 2), rxy[off[i]:off[i + 1]]])
+        k = np.where((cells == [row[X], row[Y]]).all(axis=1))[0]
+        if len(k) and 0 < k[0] < len(cells) - 3:      # a stranded blocker with road behind it and ahead of it
+            starts.append(cells[k[0] - 1]); goals.append(cells[-1])
+    assert len(starts) >= 4
+    before = c.counters().overtaking
+    for e in (h, c):
+        e.add_vehicles(np.asarray(starts, np.int32), np.asarray(goals, np.int32), np.full(len(starts), capi.POP["through"], np.int32))
+    assert c.counters().overtaking - before >= 4, "the scenario no longer makes the spawn-time planner overtake"
+    def same_plans(ctx):
+        same_state(h, c, ctx)
+        hc, cc = h.counters(), c.counters()
+        assert (hc.overtaking, hc.astar_calls) == (cc.overtaking, cc.astar_calls), f"{ctx}: {hc.overtaking, hc.astar_calls} vs {cc.overtaking, cc.astar_calls}"
+        for k in range(h.num_vehicles()):
+            assert np.array_equal(h.path(k), c.path(k)), f"{ctx}: path of active vehicle {k}"
+    same_plans("spawn")
+    for t in range(10):
+        h.step(1), c.step(1)
+        same_plans(f"tick {t}")
+    h.close(), c.close()
+
+
 def test_host_writes_between_ticks_and_rain():
     """UI handlers write stop_map directly (cell.py:241-251) and RainManager writes rain_map (rain.py:156-184)."""
     tb = world()

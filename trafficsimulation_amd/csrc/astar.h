@@ -1,4 +1,7 @@
-// astar.h - GPU A* (one search per wavefront, heap in LDS) and the replanning policy of VehicleAgent.
+// astar.h - GPU A* (one search per wavefront, heap in LDS): the wave searcher, astar_wave.  The policy that calls it is
+// decide.h (decide_vehicle), the work queue that feeds it replan.h (k_replan).
+// Also here, because every kernel that runs a searcher wave uses them without the queue (k_astar_single below, k_astar_batch in
+// astar_batch.h): wave_pop, a wave's draw from a work cursor through g_job, and searcher_account, a search's counters into the model's.
 //
 // astar_wave restates astar_numba.py:87-239 verbatim, quirks included:
 //   * binary heap keyed on f only, strict '<' in both sift routines (52-85);
@@ -20,11 +23,6 @@
 //   * everything an expansion needs from HBM (5 map entries, 5 table records, 4 densities) is requested as soon as
 //     the popped cell is known and travels while the sift-down works in LDS: one memory round trip per expansion.
 //
-// decide_vehicle restates step_decide (vehicle_base.py:616-663) with _recompute_path_on_stuck 506-517,
-// _recompute_path_on_obstacle 454-504, _compute_path 143-167 and _compute_path_internal 199-420
-// (phases 0-4).  It is a pure function of the tick-start state until its final commit, so the same code
-// runs in k_decide_main (one vehicle per lane, no scratch: bails out as soon as a search is needed) and in
-// k_replan (one vehicle per wave, every lane executing the same code on the same values).
 #pragma once
 #include <type_traits>
 #include "dev.h"
@@ -33,11 +31,6 @@ namespace {
 
 constexpr int A_INF = 0x3F3F3F3F;
 constexpr int MAXB = 64;  // longest contraflow bypass (VEHICLE_MAX_CONTRAFLOW_*_STEPS <= 64)
-enum { DV_DONE = 0, DV_DEFER = 1, DV_OVERFLOW = 2, DV_POOL_FULL = 3, DV_SUSPEND = 4, DV_BAIL = 5 };
-// Who runs a vehicle's step_decide: one lane without scratch (k_decide_main: bails out as soon as a search is needed), one
-// wavefront (k_replan: every lane the same code on the same values, searches spread over the wave), or one quad of four
-// lanes (k_replan_quad, astar_quad.h: sixteen vehicles per wave, their searches advancing in lockstep)
-enum { DM_LANE = 0, DM_WAVE = 1, DM_QUAD = 2 };
 
 // heap slots (and dir bytes) a searcher keeps in LDS: 6.2 KB, twenty-four searchers per CU (736 entries already cost occupancy) (the deepest heap seen on
 // 1024^2 - 4096^2 runs is ~2100 entries; what does not fit spills to the searcher's HBM scratch)
@@ -74,6 +67,7 @@ static_assert(REPLAN_LDS_BYTES * 4 * TS_REPLAN_WAVES <= 160 * 1024, "the LDS hea
 // heap entries carry the cell as packed coordinates: 16 bits each (ts_create refuses wider / taller maps)
 constexpr int A_XY_MAX = 0xFFFF;
 __device__ __forceinline__ int xy_pack(int x, int y) { return (int)(((uint32_t)y << 16) | (uint32_t)x); }
+__device__ __forceinline__ void xy_unpack(uint32_t xy, int& x, int& y) { x = (int)(xy & 0xFFFFu); y = (int)(xy >> 16); }
 
 // One searcher's scratch: LDS heap (above) + its slot of the HBM arena.
 struct AScratch {
@@ -95,7 +89,6 @@ struct AScratch {
   int q_start, q_goal, q_soft, q_cap;      // the search the policy is waiting for
   int32_t* q_out;
 };
-struct RLists { int32_t* l[4]; };       // the replanning queue's class lists (RQueue)
 
 struct ASlots {
   int n_slots, heap_cap, cap, use_reach;
@@ -121,21 +114,6 @@ __device__ __forceinline__ void scratch_bind(const ASlots& t, int slot, AScratch
   S.calls = 0; S.expansions = 0; S.relaxations = 0;
   S.q_status = 0; S.q_replay = 0; S.q_done = 0; S.q_log = nullptr; S.q_start = 0; S.q_goal = 0; S.q_soft = 0; S.q_cap = 0; S.q_out = nullptr;
 }
-// Work-queue order of the replans (largest first).  Per vehicle the bit length of the expansions its last replan took is
-// kept (Dev::tier_hint); the four classes are ranges of it (< 2 048, < 32 768, < 262 144 expansions, more), and inside a
-// class the queue is sorted by it again (run_replans), so that the longest search of a tick starts first.
-__device__ __forceinline__ int cost_bits(long long expansions) {
-  return 64 - __builtin_clzll((unsigned long long)max(expansions, 0ll) | 1ull);
-}
-__device__ __forceinline__ int cost_class_of_bits(int b) { return b < 12 ? 0 : b < 16 ? 1 : b < 19 ? 2 : 3; }
-// ... and for a vehicle without history, from the distance to its target: the searches are Dijkstra-like (the heuristic is
-// far below the penalties), so they touch on the order of md^2 / 2 cells
-__device__ __forceinline__ int cost_bits_of_distance(int md) { return md < 60 ? 8 : md < 240 ? 13 : md < 680 ? 17 : 19; }
-__device__ __forceinline__ int replan_cost_bits(const Dev& d, int vid) {
-  int x0, y0, x1, y1;
-  cell_xy(d, d.pos[vid], x0, y0); cell_xy(d, d.target[vid], x1, y1);
-  return max((int)d.tier_hint[vid], cost_bits_of_distance(abs(x0 - x1) + abs(y0 - y1)));
-}
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 __device__ __forceinline__ void wave_mem_sync() { __builtin_amdgcn_wave_barrier(); }
@@ -151,6 +129,18 @@ __device__ __forceinline__ double rl(double v, int lane) {
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), lane);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
+// quad_perm DPP: lane j of every quad reads lane P[j] of its quad
+template <int CTRL> __device__ __forceinline__ int qperm(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true); }
+constexpr int QP_SWAP1 = 0xB1;   // [1,0,3,2]
+constexpr int QP_SWAP2 = 0x4E;   // [2,3,0,1]
+constexpr int QP_B0 = 0x00, QP_B1 = 0x55, QP_B2 = 0xAA, QP_B3 = 0xFF;   // broadcasts of lane 0 .. 3
+__device__ __forceinline__ int quad_or(int v) {   // OR over the four lanes of the quad, in every lane
+  v |= qperm<QP_SWAP1>(v);
+  v |= qperm<QP_SWAP2>(v);
+  return v;
+}
+// (quad_perm [0,0,0,0]: every lane of a quad reads its lane 0)
+__device__ __forceinline__ int quad_first(int v) { return qperm<QP_B0>(v); }
 
 // Heap entries and table records travel as packed 64-bit words (HQ: f low, cell high; TEnt: dist low, meta high), and
 // the searcher's HBM arrays are addressed through global-address-space pointers: pointers that reach a function inside
@@ -274,14 +264,8 @@ struct ACtx {
   int n_exp, n_relax, n_exp_spill;
   int max_heap;
   long long prof[8], pt;
-  __device__ __forceinline__ void xy_of(int cell, int& x, int& y) const {
-    if (w_magic) { y = (int)(((u64)(unsigned)cell * w_magic) >> 40); x = cell - y * W; }
-    else { y = cell / W; x = cell - y * W; }
-  }
-  __device__ __forceinline__ uint32_t tile_ix(int x, int y) const {
-    // (tile rows and tiles per row are far below 2^24: the full-rate 24-bit multiply)
-    return (((__umul24((uint32_t)(y >> 3), (uint32_t)W8) + (uint32_t)(x >> 3)) << 6) | (uint32_t)((y & 7) << 3) | (uint32_t)(x & 7));
-  }
+  __device__ __forceinline__ void xy_of(int cell, int& x, int& y) const { cell_xy(W, w_magic, cell, x, y); }
+  __device__ __forceinline__ uint32_t tile_ix(int x, int y) const { return tix(W8, x, y); }
 };
 #ifdef TS_KPROF
 #define KP(k) do { const long long _t = clock64(); C.prof[k] += _t - C.pt; C.pt = _t; } while (0)
@@ -638,18 +622,11 @@ __device__ int reach_strict_wave(const Dev& d, AScratch& S, int start, int goal)
   const TS_GLOBAL u64* amap = (const TS_GLOBAL u64*)(uintptr_t)uni64((u64)(uintptr_t)d.amap);
   const unsigned qcap = (unsigned)uni(S.heap_cap - LDS_HEAP) * 2u;
   if (qcap < 256u) return 0;
-  auto xy_of = [&](int cell, int& x, int& y) {
-    if (w_magic) { y = (int)(((u64)(unsigned)cell * w_magic) >> 40); x = cell - y * W; }
-    else { y = cell / W; x = cell - y * W; }
-  };
-  auto tile_ix = [&](int x, int y) -> uint32_t {
-    return ((((uint32_t)(y >> 3) * (uint32_t)W8 + (uint32_t)(x >> 3)) << 6) | (uint32_t)((y & 7) << 3) | (uint32_t)(x & 7));
-  };
   if (lane == 0) {
     int sx, sy;
-    xy_of(start, sx, sy);
+    cell_xy(W, w_magic, start, sx, sy);
     ring[0] = start;
-    const uint32_t sr = (uint32_t)(amap[tile_ix(sx, sy)] >> 32);
+    const uint32_t sr = (uint32_t)(amap[tix(W8, sx, sy)] >> 32);
     if (sr != 0xFFFFFFFFu) tabw[2 * (size_t)sr + 1] = stamp;
   }
   __syncthreads();
@@ -660,14 +637,14 @@ __device__ int reach_strict_wave(const Dev& d, AScratch& S, int start, int goal)
     const int c = idx < tail ? ring[idx % qcap] : -1;
     head = min(tail, head + 64u);
     int cx = 0, cy = 0;
-    if (c >= 0) xy_of(c, cx, cy);
-    const uint32_t bits = c >= 0 ? (uint32_t)amap[tile_ix(cx, cy)] & 15u : 0u;
+    if (c >= 0) cell_xy(W, w_magic, c, cx, cy);
+    const uint32_t bits = c >= 0 ? (uint32_t)amap[tix(W8, cx, cy)] & 15u : 0u;
     for (int dd = 0; dd < 4; dd++) {
       int n = -1;
       if (bits & (1u << dd)) {
         const int nx = cx + (dd == 1) - (dd == 3), ny = cy + (dd == 0) - (dd == 2);
         if (nx >= 0 && nx < W && ny >= 0 && ny < H) {
-          const u64 an = amap[tile_ix(nx, ny)];
+          const u64 an = amap[tix(W8, nx, ny)];
           const uint32_t rn = (uint32_t)(an >> 32);
           if (((uint32_t)an & 0x300u) == 0u && rn != 0xFFFFFFFFu &&
               __hip_atomic_exchange(&tabw[2 * (size_t)rn + 1], stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != stamp)
@@ -686,562 +663,6 @@ __device__ int reach_strict_wave(const Dev& d, AScratch& S, int start, int goal)
   return found ? 1 : 2;
 }
 
-// ---------------------------------------------------------------------------------------------
-// vehicle working state for one step_decide
-// ---------------------------------------------------------------------------------------------
-struct VW {
-  int vid, i, pos, target;
-  uint16_t f;
-  int base, cur, cooldown, over_dur, det_dur, stuck_ticks;
-  // current path: pool-resident direction string, or cells in S.P
-  bool newpath;
-  int plen, pcur;
-  uint32_t off;
-  // aux paths k: 0 overtake_path, 1 pre_overtake_path, 2 stuck_detour_path, 3 pre_stuck_detour_path
-  bool ax_staged[4];
-  int ax_len[4];  // -1 = None
-  int d_overtaking, d_detour;
-  bool reach_known;  // a replan inside the decide phase: phase 1 asks reach_strict_wave first
-};
-
-__device__ __forceinline__ int32_t* ax_buf(const AScratch& S, int k) { return k == 0 ? S.OV : k == 1 ? S.PO : k == 2 ? S.DV : S.PD; }
-
-// sequential reader over an aux path (staged cells or pool-resident directions)
-struct AxReader {
-  const int32_t* cells;
-  const uint32_t* pool;
-  uint32_t off;
-  int cell, idx, W;
-  __device__ void init(const Dev& d, const AScratch& S, const VW& v, int k) {
-    idx = 0; W = d.W; pool = d.pool;
-    if (v.ax_staged[k]) { cells = ax_buf(S, k); }
-    else { cells = nullptr; off = d.ax_off[k][v.vid]; cell = d.ax_start[k][v.vid]; }
-  }
-  __device__ __forceinline__ int next() {
-    if (cells) return cells[idx++];
-    cell = step_cell(cell, path_dir(pool, off, idx++), W);
-    return cell;
-  }
-};
-
-__device__ __forceinline__ int vw_path_cell(const Dev& d, const AScratch* S, const VW& v, int k, int& walk) {
-  // k-th remaining cell; `walk` carries the running cell for pool-resident paths (call with k ascending)
-  if (v.newpath) return S->P[k];
-  walk = step_cell(walk, path_dir(d.pool, v.off, v.pcur + k), d.W);
-  return walk;
-}
-
-// _scan_ahead_for_obstacles (vehicle_base.py:422-452).  The cells are decoded first and their records loaded
-// together (independent loads, one memory round trip); the reference's early exit at index 0 only shortens the
-// evaluation.
-constexpr int SCAN_MAX = 16;
-__device__ void scan_ahead_dev(const Dev& d, const TsParams& P, const AScratch* S, const VW& v, int& idx_stop,
-                               int& idx_veh, int& first_cell) {
-  idx_stop = -1; idx_veh = -1; first_cell = -1;
-  const int look = min(P.vehicle_awareness_range, v.plen);
-  int walk = v.pos;
-  if (look <= SCAN_MAX && !v.newpath) {
-    int cells[SCAN_MAX];
-    uint32_t dyn[SCAN_MAX];   // the dword holding occ / stop / stuck / stat
-    // the next 16 steps are at most 32 bits of the direction string: two pool words, decoded in registers
-    const uint32_t wi = (uint32_t)v.pcur >> 4, nwords = ((uint32_t)(v.pcur + v.plen) + 15u) >> 4;
-    uint64_t bits = d.pool[v.off + wi];
-    if (wi + 1 < nwords) bits |= (uint64_t)d.pool[v.off + wi + 1] << 32;
-    bits >>= (v.pcur & 15) * 2;
-    {
-      int c = v.pos;
-#pragma unroll
-      for (int k = 0; k < SCAN_MAX; k++) {
-        if (k < look) c = step_cell(c, (int)((bits >> (2 * k)) & 3), d.W);
-        cells[k] = c;
-      }
-    }
-    if (look > 0) first_cell = cells[0];
-    // an obstacle at index 0 ends the scan (the reference's break can only fire there) - and in dense traffic that
-    // is the common case, so the first record is fetched alone and the other nine only if it is clear
-    dyn[0] = look > 0 ? *reinterpret_cast<const uint32_t*>(&d.cell[cells[0]].occ) : 0u;
-    if (look > 0 && (int8_t)((dyn[0] >> 8) & 0xFF) == 1) idx_stop = 0;
-    if (look > 0 && (int8_t)(dyn[0] & 0xFF) == 1) idx_veh = 0;
-    if (idx_stop == 0 || idx_veh == 0) return;
-#pragma unroll
-    for (int k = 1; k < SCAN_MAX; k++) dyn[k] = k < look ? *reinterpret_cast<const uint32_t*>(&d.cell[cells[k]].occ) : 0u;
-#pragma unroll
-    for (int k = 1; k < SCAN_MAX; k++) {
-      const bool in = k < look;
-      const int occ = (int8_t)(dyn[k] & 0xFF), stop = (int8_t)((dyn[k] >> 8) & 0xFF);
-      if (in && idx_stop < 0 && stop == 1) idx_stop = k;
-      if (in && idx_veh < 0 && occ == 1) idx_veh = k;
-    }
-    return;
-  }
-  for (int k = 0; k < look; k++) {
-    int c = vw_path_cell(d, S, v, k, walk);
-    if (k == 0) first_cell = c;
-    const Cell cc = d.cell[c];
-    if (idx_stop < 0 && cc.stop == 1) idx_stop = k;
-    if (idx_veh < 0 && cc.occ == 1) idx_veh = k;
-    if (idx_stop == 0 || idx_veh == 0) break;
-  }
-}
-
-__device__ __forceinline__ void swap_ptr(int32_t*& a, int32_t*& b) { int32_t* t = a; a = b; b = t; }
-
-// _compute_path_internal (vehicle_base.py:199-420).  On success the result is in S.P[0..*out_len) (possibly
-// empty).  Returns false on tier overflow.
-// DM_WAVE: the caller runs with all 64 lanes of its wave executing the same code on the same values (one vehicle per
-// wave); plain stores are then harmless duplicates, atomics are issued by lane 0 only, and the searches use
-// astar_wave.  DM_QUAD: the same with the four lanes of a quad.  DM_LANE: one vehicle per lane (k_decide_main), nothing is shared.
-constexpr int QLOG = 8;   // searches one step_decide can make in quad mode (beyond that the vehicle goes to k_replan)
-template <int MODE>
-__device__ __forceinline__ int astar_any(const Dev& d, const TsParams& P, AScratch& S, int start_idx, int goal_idx, bool soft,
-                                         bool ignore_flow, int maximum_steps, int32_t* out, int out_cap) {
-  if constexpr (MODE == DM_WAVE) return astar_wave(d, P, S, start_idx, goal_idx, soft, ignore_flow, maximum_steps, out, out_cap);
-  else if constexpr (MODE == DM_QUAD) {
-    const int k = S.q_replay++;
-    if (k < S.q_done) {   // finished in an earlier pass: its path already sits in `out`
-      S.calls++; S.expansions += S.q_log[3 * k + 1]; S.relaxations += S.q_log[3 * k + 2];
-      return S.q_log[3 * k];
-    }
-    // the quad searcher carries neither step limits nor contraflow (bypass searches are rare and small): such a vehicle is
-    // handed to k_replan, as is one that searches more often than the log is long
-    if (maximum_steps < d.N || ignore_flow || k >= QLOG) { S.q_status = DV_BAIL; return -1; }
-    S.q_start = start_idx; S.q_goal = goal_idx; S.q_soft = soft ? 1 : 0; S.q_out = out; S.q_cap = out_cap;
-    S.q_status = DV_SUSPEND;
-    return -1;
-  }
-  else return -1;   // (one vehicle per lane never searches: decide_vehicle<DM_LANE> defers before it gets here)
-}
-template <int MODE>
-__device__ bool compute_path_internal_dev(const Dev& d, const TsParams& P, AScratch& S, VW& v, int& out_len) {
-  // ---- phase 0: re-merge with the saved original path (219-277) ----
-  for (int which = 0; which < 2; which++) {
-    const int kb = which == 0 ? 0 : 2, kp = kb + 1;  // bypass slot, pre-path slot
-    const bool active = which == 0 ? (v.f & VF_OVER) != 0 : (v.f & VF_DETOUR) != 0;
-    if (!active || v.ax_len[kp] <= 0) continue;
-    AxReader r;
-    r.init(d, S, v, kp);
-    int merge_idx = -1, b = -1;
-    for (int q = 0; q < v.ax_len[kp]; q++) {
-      int c = r.next();
-      if (d.cell[c].occ == 0) { merge_idx = q; b = c; break; }
-    }
-    if (merge_idx < 0) continue;
-    int bl = astar_any<MODE>(d, P, S, v.pos, b, false, true, P.max_contraflow_overtake_steps, S.BYP, MAXB);
-    if (bl < 0) return false;
-    if (bl > 0 && S.BYP[bl - 1] == b) {
-      int n = 0;
-      for (int q = 0; q < bl; q++) S.T[n++] = S.BYP[q];
-      int rest = v.ax_len[kp] - (merge_idx + 1);
-      if (n + rest > S.cap) return false;
-      for (int q = 0; q < rest; q++) S.T[n++] = r.next();
-      int32_t* dst = ax_buf(S, kb);
-      for (int q = 0; q < bl; q++) dst[q] = S.BYP[q];
-      v.ax_staged[kb] = true; v.ax_len[kb] = bl;
-      swap_ptr(S.P, S.T);
-      out_len = n;
-      return true;
-    }
-  }
-  // ---- phase 1: strict; phase 2: soft obstacles (280-306) ----
-  const int sx_goal = v.target;
-  int la;
-  bool unreachable = false;
-  if constexpr (MODE == DM_WAVE) unreachable = v.reach_known && reach_strict_wave(d, S, v.pos, sx_goal) == 2;
-  if (unreachable) {
-    // the frontier BFS proved the target unreachable under the strict rules: the search would flood its whole
-    // component and return [] (astar_numba.py:239).  Same result, without the flood.
-    S.calls++;
-    la = 0;
-  } else {
-    la = astar_any<MODE>(d, P, S, v.pos, sx_goal, false, false, 0x7FFFFFFF, S.A, S.cap);
-    if (la < 0) return false;
-  }
-  if (la == 0) {
-    la = astar_any<MODE>(d, P, S, v.pos, sx_goal, true, false, 0x7FFFFFFF, S.A, S.cap);
-    if (la < 0) return false;
-  }
-  // ---- phase 3: contraflow overtake of a stranded / parked blocker (309-366) ----
-  if (P.contraflow_overtake_active && la > 0) {
-    int idx_stop = -1, idx_veh = -1;
-    int look = min(P.vehicle_awareness_range, la);
-    for (int q = 0; q < look; q++) {
-      if (idx_stop < 0 && d.cell[S.A[q]].stop == 1) idx_stop = q;
-      if (idx_veh < 0 && d.cell[S.A[q]].occ == 1) idx_veh = q;
-      if (idx_stop >= 0 && idx_veh >= 0) break;
-    }
-    if (idx_veh == 0) {
-      int bk = d.cell[S.A[0]].veh;
-      if (bk >= 0 && (seen_stranded(d, bk, v.i) || seen_parked(d, bk, v.i))) {
-        int bt = -1, idx_bp = -1;
-        for (int q = 0; q < la; q++) if (d.cell[S.A[q]].occ == 0) { bt = S.A[q]; idx_bp = q; break; }
-        if (bt >= 0) {
-          int bl = astar_any<MODE>(d, P, S, v.pos, bt, false, true, P.max_contraflow_overtake_steps, S.BYP, MAXB);
-          if (bl < 0) return false;
-          if (bl > 1 && S.BYP[bl - 1] == bt) {
-            // idx_bp = first index of bt in path = the index found above (first free cell)
-            int n = 0;
-            for (int q = 0; q < bl; q++) S.T[n++] = S.BYP[q];
-            if (n + (la - idx_bp - 1) > S.cap) return false;
-            for (int q = idx_bp + 1; q < la; q++) S.T[n++] = S.A[q];
-            for (int q = 0; q < la; q++) S.PO[q] = S.A[q];      // pre_overtake_path = path
-            v.ax_staged[1] = true; v.ax_len[1] = la;
-            for (int q = 0; q < bl; q++) S.OV[q] = S.BYP[q];    // overtake_path = bypass
-            v.ax_staged[0] = true; v.ax_len[0] = bl;
-            v.f |= VF_OVER;
-            v.d_overtaking++;
-            v.over_dur = 0;
-            swap_ptr(S.P, S.T);
-            out_len = n;
-            return true;
-          }
-        }
-      }
-    }
-  }
-  // ---- phase 4: stuck detour (369-418) ----
-  if (P.stuck_contraflow_enabled && la > 0) {
-    int threshold = st_inter(d.cell[v.pos].stat) == 1 ? P.stuck_contraflow_threshold_intersection : P.stuck_contraflow_threshold;
-    if (v.stuck_ticks >= threshold) {
-      int bt = -1, merge_idx = -1;
-      for (int q = 0; q < la; q++) if (d.cell[S.A[q]].occ == 0) { bt = S.A[q]; merge_idx = q; break; }
-      if (bt >= 0) {
-        int bl = astar_any<MODE>(d, P, S, v.pos, bt, true, true, P.max_contraflow_stuck_detour_steps, S.BYP, MAXB);
-        if (bl < 0) return false;
-        if (bl > 1 && S.BYP[bl - 1] == bt) {
-          int n = 0;
-          for (int q = 0; q < bl; q++) S.T[n++] = S.BYP[q];
-          if (n + (la - merge_idx - 1) > S.cap) return false;
-          for (int q = merge_idx + 1; q < la; q++) S.T[n++] = S.A[q];
-          for (int q = 0; q < la; q++) S.PD[q] = S.A[q];        // pre_stuck_detour_path = path.copy()
-          v.ax_staged[3] = true; v.ax_len[3] = la;
-          for (int q = 0; q < bl; q++) S.DV[q] = S.BYP[q];      // stuck_detour_path = bypass
-          v.ax_staged[2] = true; v.ax_len[2] = bl;
-          v.d_detour++;
-          v.f |= VF_DETOUR;
-          v.det_dur = 0;
-          swap_ptr(S.P, S.T);
-          out_len = n;
-          return true;
-        }
-      }
-    }
-  }
-  swap_ptr(S.P, S.A);
-  out_len = la;
-  return true;
-}
-
-// `pos not in aux path k`
-__device__ bool ax_contains(const Dev& d, const AScratch* S, const VW& v, int k, int cell) {
-  if (v.ax_len[k] <= 0) return false;
-  if (!S) {  // no scratch: only pool-resident paths can exist
-    int c = d.ax_start[k][v.vid];
-    uint32_t off = d.ax_off[k][v.vid];
-    for (int q = 0; q < v.ax_len[k]; q++) { c = step_cell(c, path_dir(d.pool, off, q), d.W); if (c == cell) return true; }
-    return false;
-  }
-  AxReader r;
-  r.init(d, *S, v, k);
-  for (int q = 0; q < v.ax_len[k]; q++) if (r.next() == cell) return true;
-  return false;
-}
-
-// device-side bump allocation in the path pool; returns false when the pool is exhausted
-// (quad_perm [0,0,0,0]: every lane of a quad reads its lane 0)
-__device__ __forceinline__ int quad_first(int v) { return __builtin_amdgcn_mov_dpp(v, 0x00, 0xF, 0xF, true); }
-template <int MODE>
-__device__ __forceinline__ bool pool_alloc(const Dev& d, int words, uint32_t& off) {
-  unsigned long long o = 0;
-  const bool one = MODE == DM_LANE || (MODE == DM_WAVE ? lane_id() == 0 : (lane_id() & 3) == 0);
-  if (one) o = atomicAdd((unsigned long long*)&d.cnt->pool_used, (unsigned long long)words);
-  if (MODE == DM_WAVE) o = ((unsigned long long)(unsigned)__shfl((int)(o >> 32), 0) << 32) | (unsigned)__shfl((int)(unsigned)o, 0);
-  if (MODE == DM_QUAD) o = ((unsigned long long)(unsigned)quad_first((int)(o >> 32)) << 32) | (unsigned)quad_first((int)(unsigned)o);
-  if (o + (unsigned long long)words > (unsigned long long)d.pool_cap_words) return false;
-  off = (uint32_t)o;
-  return true;
-}
-__device__ void encode_cells(const Dev& d, uint32_t off, int start_cell, const int32_t* cells, int len) {
-  int prev = start_cell;
-  uint32_t word = 0;
-  for (int k = 0; k < len; k++) {
-    int c = cells[k];
-    int delta = c - prev;
-    int dir = delta == d.W ? 0 : delta == 1 ? 1 : delta == -d.W ? 2 : 3;
-    word |= (uint32_t)dir << ((k & 15) * 2);
-    if ((k & 15) == 15) { d.pool[off + (k >> 4)] = word; word = 0; }
-    prev = c;
-  }
-  if (len & 15) d.pool[off + (len >> 4)] = word;
-}
-
-// step_decide for vehicle number i of active_vehicle_agents.  S == nullptr: run until a search is needed
-// (returns DV_DEFER without side effects).  Otherwise completes, unless the tier overflows or the pool is full.
-template <int MODE>
-__device__ int decide_vehicle(const Dev& d, const TsParams& P, int i, AScratch* S) {
-  const bool one = MODE == DM_LANE || (MODE == DM_WAVE ? lane_id() == 0 : (lane_id() & 3) == 0);   // the lane that issues this vehicle's atomics
-  const int vid = d.active[i];
-  if (vid < 0) return DV_DONE;
-  VW v;
-  v.vid = vid; v.i = i; v.pos = d.pos[vid]; v.target = d.target[vid];
-  v.reach_known = S != nullptr && S->use_reach;
-  v.f = d.flags[vid] & ~VF_EARLY;
-  const uint8_t ev = d.ev[vid];
-  v.base = d.base_speed[vid]; v.cur = d.cur_speed[vid];
-  bool early = false;
-  int stranded_left = d.stranded_left[vid];
-  bool write_stranded = false;
-  int dc_coll = 0, dc_malf = 0;
-  if (ev == 1) {  // became stranded at its own decide point: state already written by k_apply_event
-    v.base = 0; v.cur = 0; early = true;
-  } else {
-    if (ev != 2 && (v.f & (VF_COLL | VF_MALF))) {  // _tick_stranded (552-565)
-      stranded_left -= 1;
-      if (stranded_left <= 0) {
-        if (v.f & VF_COLL) dc_coll--;
-        if (v.f & VF_MALF) dc_malf--;
-        v.f &= ~(VF_COLL | VF_MALF);
-        stranded_left = 0;
-      }
-      write_stranded = true;
-      if (v.f & (VF_COLL | VF_MALF)) { v.base = 0; v.cur = 0; early = true; }
-    }
-    if (!early && !P.malfunction_active) {  // `not ACTIVE or ...` (609): malfunction without a draw
-      v.f = (v.f | VF_MALF) & ~VF_COLL;
-      stranded_left = P.malfunction_duration; write_stranded = true;
-      dc_malf++;
-      v.base = 0; v.cur = 0; early = true;
-    }
-    if (!early && d.cell[v.pos].stop == 1) { v.base = 0; v.cur = 0; early = true; }
-  }
-  int max_steps = d.max_steps[vid];
-  bool path_changed = false, reached_body = false, arrived = false;
-  v.newpath = false;
-  v.d_overtaking = 0; v.d_detour = 0;
-  for (int k = 0; k < 4; k++) { v.ax_staged[k] = false; v.ax_len[k] = 0; }
-  bool ax_none_set[2] = {false, false};
-  if (!early) {
-    if (v.base == 0) v.base = d.R[i];  // _choose_new_speed: rolled by the host scan
-    int speed = v.base;
-    if (P.rain_enabled && d.rain[v.pos] == 1) speed = max(1, speed - P.rain_speed_reduction);
-    v.cur = speed;
-    v.off = d.path_off[vid]; v.pcur = d.path_cur[vid]; v.plen = d.path_len[vid] - v.pcur;
-    v.cooldown = d.cooldown[vid]; v.over_dur = d.over_dur[vid]; v.det_dur = d.det_dur[vid];
-    v.stuck_ticks = d.stuck_ticks[vid];
-    for (int k = 0; k < 4; k++) { v.ax_staged[k] = false; v.ax_len[k] = d.ax_len[k][vid]; }
-    // _recompute_path_on_stuck (506-517): self.path = self._compute_path(use_cache=False)
-    const int thresh = st_inter(d.cell[v.pos].stat) == 1 ? P.stuck_recompute_threshold_intersection : P.stuck_recompute_threshold;
-    if (v.stuck_ticks >= thresh) {
-      if (!S) return DV_DEFER;
-      v.cooldown = P.pathfinding_cooldown;
-      int len;
-      if (!compute_path_internal_dev<MODE>(d, P, *S, v, len)) return MODE == DM_QUAD ? S->q_status : DV_OVERFLOW;
-      v.newpath = true; v.plen = len; path_changed = true;
-    }
-    // _recompute_path_on_obstacle (454-504)
-    if ((v.f & VF_OVER) && (v.ax_len[0] <= 0 || !ax_contains(d, S, v, 0, v.pos))) {
-      v.ax_len[0] = -1; v.ax_staged[0] = false; ax_none_set[0] = true; v.f &= ~VF_OVER;
-    }
-    if ((v.f & VF_DETOUR) && (v.ax_len[2] <= 0 || !ax_contains(d, S, v, 2, v.pos))) {
-      v.ax_len[2] = -1; v.ax_staged[2] = false; ax_none_set[1] = true; v.f &= ~VF_DETOUR;
-    }
-    int idx_stop, idx_veh, first_cell;
-    scan_ahead_dev(d, P, S, v, idx_stop, idx_veh, first_cell);
-    bool done_obst = false;
-    if (v.f & VF_OVER) {
-      v.over_dur += 1;
-      if (v.over_dur <= P.contraflow_overtake_duration) done_obst = true;
-    }
-    if (!done_obst && (v.f & VF_DETOUR)) {
-      v.det_dur += 1;
-      if (v.det_dur <= P.contraflow_stuck_detour_duration) done_obst = true;
-    }
-    if (!done_obst && v.cooldown > 0) {
-      if (idx_veh == 0) {
-        int b = d.cell[first_cell].veh;
-        if (b >= 0 && (seen_stranded(d, b, i) || seen_parked(d, b, i))) {
-          // immediate pathfinding
-        } else { v.cooldown -= 1; done_obst = true; }
-      } else { v.cooldown -= 1; done_obst = true; }
-    }
-    if (!done_obst && (idx_stop >= 0 || idx_veh >= 0)) {
-      if (!S) return DV_DEFER;
-      // path = self._compute_path(use_cache=False); adopted only when non-empty (498-502).  The planner
-      // never writes through S->P, it only swaps buffer pointers at the end, so a previous result of this
-      // tick (stuck replan) survives an empty answer and is swapped back.
-      v.cooldown = P.pathfinding_cooldown;
-      const bool keep_new = v.newpath;
-      int len;
-      if (!compute_path_internal_dev<MODE>(d, P, *S, v, len)) return MODE == DM_QUAD ? S->q_status : DV_OVERFLOW;
-      if (len > 0) {
-        v.newpath = true; v.plen = len; path_changed = true;
-        scan_ahead_dev(d, P, S, v, idx_stop, idx_veh, first_cell);
-      } else if (keep_new) {
-        swap_ptr(S->P, S->A);  // undo the final swap of the empty result
-      }
-    }
-    // _determine_max_steps (719-731)
-    int ms = min(v.cur, v.plen);
-    bool blocked = false;
-    if (idx_stop >= 0) ms = min(ms, idx_stop);
-    if (idx_veh >= 0) { if (idx_veh == 0) blocked = true; ms = min(ms, idx_veh); }
-    max_steps = ms;
-    v.f = blocked ? (v.f | VF_BLOCKED) : (v.f & ~VF_BLOCKED);
-    if (ms <= 0) {
-      v.base = 0;
-      if (v.pos == v.target) arrived = true;   // on_target_reached() inside step_decide (657-661)
-      early = true;
-    }
-    reached_body = true;
-  }
-  if (ev == 2) { v.base = 0; v.cur = 0; }  // collision inflicted after this vehicle had decided
-  // ---------------- commit (first the allocation that can fail, then everything else) ----------------
-  if (reached_body && S) {
-    int words = path_changed ? (v.plen + 15) / 16 : 0;
-    for (int k = 0; k < 4; k++) if (v.ax_staged[k]) words += (v.ax_len[k] + 15) / 16;
-    uint32_t off = 0;
-    if (words > 0 && !pool_alloc<MODE>(d, words, off)) return DV_POOL_FULL;
-    uint8_t chg = 0;
-    if (path_changed) {
-      encode_cells(d, off, v.pos, S->P, v.plen);
-      d.path_off[vid] = off; d.path_len[vid] = v.plen; d.path_cur[vid] = 0;
-      off += (v.plen + 15) / 16;
-      chg |= 1;
-    }
-    for (int k = 0; k < 4; k++) {
-      if (!v.ax_staged[k]) continue;
-      encode_cells(d, off, v.pos, ax_buf(*S, k), v.ax_len[k]);
-      d.ax_start[k][vid] = v.pos; d.ax_off[k][vid] = off; d.ax_len[k][vid] = v.ax_len[k];
-      off += (v.ax_len[k] + 15) / 16;
-      chg |= (uint8_t)(2 << k);
-    }
-    if (chg) d.chg[vid] = chg;
-  }
-  if (reached_body) {
-    if (ax_none_set[0] && !v.ax_staged[0]) d.ax_len[0][vid] = -1;
-    if (ax_none_set[1] && !v.ax_staged[2]) d.ax_len[2][vid] = -1;
-    d.cooldown[vid] = v.cooldown; d.over_dur[vid] = v.over_dur; d.det_dur[vid] = v.det_dur;
-    if (one && v.d_overtaking) atomicAdd((unsigned long long*)&d.cnt->overtaking, (unsigned long long)v.d_overtaking);
-    if (one && v.d_detour) atomicAdd((unsigned long long*)&d.cnt->in_stuck_detour, (unsigned long long)v.d_detour);
-  }
-  if (write_stranded) d.stranded_left[vid] = stranded_left;
-  if (one && dc_coll) atomicAdd((unsigned long long*)&d.cnt->collisions, (unsigned long long)(long long)dc_coll);
-  if (one && dc_malf) atomicAdd((unsigned long long*)&d.cnt->malfunctions, (unsigned long long)(long long)dc_malf);
-  d.max_steps[vid] = (int8_t)max_steps;
-  d.base_speed[vid] = (int8_t)v.base;
-  d.cur_speed[vid] = (int8_t)v.cur;
-  d.flags[vid] = early ? (v.f | VF_EARLY) : v.f;
-  if (arrived && one) {
-    if (!(v.f & VF_KEEP)) {   // a trip that ends where it starts: _despawn inside step_decide.  The host ends the stretch of
-      // the decide order at such a vehicle and takes it off the maps once everybody before it is through (tick())
-      if (d.dec_expect == i + 1) atomicExch(&d.cnt->dec_arrived, i + 1);
-      else atomicExch(&d.cnt->error, TS_E_DEVICE);
-    }
-    else if (v.f & VF_TOBLOCK) svc_record(d, i, vid, AR_DECIDE);        // ServiceVehicleAgent._start_service
-    else {   // base on_target_reached of a vehicle that stays: trip statistics once more, then _park()
-      if (P.enable_traffic && d.pop[vid] == TS_POP_THROUGH) {
-        atomicAdd(&d.cnt->dur_through, d.elapsed - d.depart[vid]);
-        atomicAdd((unsigned long long*)&d.cnt->dist_through, (unsigned long long)d.steps[vid]);
-        atomicAdd((unsigned long long*)&d.cnt->completed_through, 1ULL);
-      } else if (P.enable_traffic && d.pop[vid] == TS_POP_INTERNAL) {
-        atomicAdd(&d.cnt->dur_internal, d.elapsed - d.depart[vid]);
-        atomicAdd((unsigned long long*)&d.cnt->dist_internal, (unsigned long long)d.steps[vid]);
-        atomicAdd((unsigned long long*)&d.cnt->completed_internal, 1ULL);
-      }
-      if (!(v.f & VF_PARKED)) svc_record(d, i, vid, AR_DECIDE);
-    }
-  }
-  return DV_DONE;
-}
-
-// every live vehicle: the part of step_decide that needs no search; the others go to the replan list
-__global__ void k_decide_main(Dev d, TsParams P, int lo, int n_active, RLists lists) {
-  int i = lo + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_active) return;
-  if (d.cnt->rng_event != 0xFFFFFFFFu) return;  // a malfunction / sideswipe fired: the host re-runs this after the fix-up
-  if (decide_vehicle<DM_LANE>(d, P, i, nullptr) == DV_DEFER) {
-    // work-queue class (largest first): what the vehicle's last replan cost, or what a search over this distance is
-    // likely to cost
-    const int h = cost_class_of_bits(replan_cost_bits(d, d.active[i]));
-    lists.l[h][atomicAdd(&d.cnt->replan.class_n[h], 1)] = i;
-  }
-}
-
-// sort key of a replanning entry (run_replans): expected cost, largest first (bit length of the expansions, see cost_bits),
-// then the Morton index of the 32 x 32-cell block its vehicle stands in
-constexpr int REPLAN_KEY_BITS = 21;
-__device__ __forceinline__ uint32_t morton_block_key(int x, int y) {
-  const uint32_t bx = (uint32_t)x >> 5, by = (uint32_t)y >> 5;
-  uint32_t k = 0;
-  for (int b = 0; b < 8; b++) k |= ((bx >> b) & 1u) << (2 * b) | ((by >> b) & 1u) << (2 * b + 1);
-  return k;
-}
-__device__ __forceinline__ uint32_t replan_key(const Dev& d, int i) {
-  const int vid = d.active[i];
-  int x = 0, y = 0, bits = 0;
-  if (vid >= 0) { cell_xy(d, d.pos[vid], x, y); bits = min(replan_cost_bits(d, vid), 31); }
-  // (only the long searches are ordered by cost - 65 536 expansions and more, bit by bit; the bulk stays in plain spatial order)
-  return ((uint32_t)(31 - max(bits, 16)) << 16) | morton_block_key(x, y);
-}
-// The same with the entry itself (its decide-order index) below the key: a total order, the same on every rank of a sharded
-// run whatever order k_decide_main's atomics left the list in, so that ranks can split the queue by POSITION (entry j of
-// the sorted queue belongs to rank j % world: every rank gets every world-th search of every cost class and every
-// neighbourhood - the longest searches are dealt out one by one instead of falling where index % world puts them).
-__global__ void k_replan_keys64(Dev d, const int32_t* list, int n, unsigned long long* keys) {
-  int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  keys[j] = ((unsigned long long)replan_key(d, list[j]) << 32) | (unsigned long long)(uint32_t)list[j];
-}
-__global__ void k_replan_unkey64(const unsigned long long* keys, int n, int32_t* list) {
-  int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n) list[j] = (int32_t)(uint32_t)keys[j];
-}
-__global__ void k_replan_keys(Dev d, const int32_t* list, int n, uint32_t* keys) {
-  int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  keys[j] = replan_key(d, list[j]);
-}
-
-// ---- the replanning work queue ---------------------------------------------------------------------------------------
-// Vehicles whose step_decide needs a search wait in four class lists, by expected cost (k_decide_main files them, run_replans
-// sorts each).  The queue is classes 3, 2, 1, 0 in turn: a tick's replanning time is bounded below by its longest search, so
-// those start first and the short ones fill in behind.  Its counters are DevCnt::replan and the four words after it.  k_replan
-// (one wave per search) and k_replan_quad (astar_quad.h, sixteen per wave) serve it, each the classes of its `class_mask` with
-// a cursor of its own; pool-full entries go to retry_list for the host to run again.
-// Ownership by position (`world` > 1, the replicated-state multi-GPU mode): the queue is in the same total order on every
-// rank (run_replans sorts by (key, index)) and the entry at position pos of the WHOLE queue - every class counted, whichever
-// kernel serves it - is rank pos % world's.  What a rank plans goes to owned_list for ts_replan_export / ts_replan_import.
-// Hand-backs: a vehicle the quads cannot carry goes to handback_list - counted in handback_n, then stored (-1 = not yet
-// written).  k_replan's waves beside the quads (fb_waves = the quads' grid, 0 = none) serve that list once their own classes
-// are done: a ticket from handback_claimed, never beyond handback_n, so what is left when they stop is a suffix the host can
-// queue again; hand-backs of this rank's quads are this rank's.  They give up when all fb_waves quad waves have counted
-// themselves out in quad_waves_done and nothing more was produced, or when no counter has moved for about three seconds
-// (the kernels were not run side by side - a profiler or debugger serialising launches; k_replan_quad is then yet to run).
-// The host's part, one kernel argument.  fb_waves: k_replan only, the quads' grid (0: no quads beside it).
-struct RQueueArgs { RLists lists; int class_mask; int32_t *retry_list, *handback_list; int rank, world; int32_t* owned_list /* nullptr unless sharded */; int fb_waves; };
-struct RQueue {         // what a turn at the queue reads: the host's part + what rqueue_open fills on the device
-  RLists lists;
-  int n[4], pos0[4];    // class list lengths (0: not served by this launch); position of each class' first entry in the whole queue
-  int32_t *retry_list, *handback_list, *owned_list; int rank, world;
-};
-// k_replan's: + the quads beside it.  Apart from RQueue for the compiler's sake only: the queue goes to the turn functions through the stack, and fb_waves inside RQueue (or as a parameter) changes k_replan_quad's (k_replan's) scratch size
-struct RQueueFb : RQueue { int fb_waves; };
-__device__ __forceinline__ RQueue rqueue_open(const Dev& d, const RQueueArgs& a) {
-  RQueue q; const int* cn = d.cnt->replan.class_n;
-  q.lists = a.lists;
-  for (int c = 0; c < 4; c++) q.n[c] = ((a.class_mask >> c) & 1) ? cn[c] : 0;
-  q.pos0[3] = 0; q.pos0[2] = cn[3]; q.pos0[1] = cn[3] + cn[2]; q.pos0[0] = cn[3] + cn[2] + cn[1];
-  q.retry_list = a.retry_list; q.handback_list = a.handback_list; q.owned_list = a.owned_list; q.rank = a.rank; q.world = a.world;
-  return q;
-}
-// cursor value j (below the launch's total) -> the entry i and its position in the whole queue; false: another rank's
-__device__ __forceinline__ bool rqueue_entry(const RQueue& q, int j, int& i, int& pos) {
-  const int n3 = q.n[3], n2 = q.n[2], n1 = q.n[1];
-  if (j < n3) { i = q.lists.l[3][j]; pos = q.pos0[3] + j; }
-  else if (j < n3 + n2) { i = q.lists.l[2][j - n3]; pos = q.pos0[2] + j - n3; }
-  else if (j < n3 + n2 + n1) { i = q.lists.l[1][j - n3 - n2]; pos = q.pos0[1] + j - n3 - n2; }
-  else { i = q.lists.l[0][j - n3 - n2 - n1]; pos = q.pos0[0] + j - n3 - n2 - n1; }
-  return q.world <= 1 || (pos % q.world) == q.rank;
-}
 // lane 0 draws the next value of a queue cursor for the whole wave
 __device__ __forceinline__ int wave_pop(int* cursor) {
   if (threadIdx.x == 0) g_job = atomicAdd(cursor, 1);
@@ -1254,182 +675,6 @@ __device__ __forceinline__ void searcher_account(const Dev& d, long long calls, 
   atomicAdd((unsigned long long*)&d.cnt->astar_calls, (unsigned long long)calls);
   atomicAdd((unsigned long long*)&d.cnt->astar_exp, (unsigned long long)exp);
   atomicAdd((unsigned long long*)&d.cnt->astar_relax, (unsigned long long)relax);
-}
-
-// One turn of a searcher wave at the replanning work queue: take the next entry, run the vehicle's step_decide with
-// all 64 lanes, account for it.  Returns 0 once the queue is empty.  Kept out of line on purpose: inlined into
-// k_replan's loop, hipcc 7.2 threaded the lane-0-only parts (queue pop, accounting) of consecutive turns together and
-// let lane 0 run the loop on a path of its own, apart from the other 63 lanes - wrong for code whose lanes cooperate
-// through readlane / ballot.  A call boundary is a point where the wave is whole again.
-#ifdef TS_TRACE_REPLAN
-// profiling builds (profiles/replan_trace.py): per queue entry (start, end: low words of the 100 MHz clock; expansions;
-// predicted cost bits | searcher slot << 8)
-__device__ int4* g_rtrace = nullptr;
-__device__ int g_rtrace_cap = 0;
-#endif
-__device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParams& P, AScratch* S, const RQueueFb& q) {
-  const int n3 = uni(q.n[3]), n2 = uni(q.n[2]), n1 = uni(q.n[1]), n0 = uni(q.n[0]);
-  const int j = wave_pop(&d.cnt->replan.cursor);
-  int i, pos = j;
-  bool mine = true;
-  if (j >= n3 + n2 + n1 + n0) {
-    if (q.fb_waves == 0) return 0;
-    // this launch's own lists are done: serve the hand-back list (the protocol and its give-up rule: see RQueue)
-    if (threadIdx.x == 0) {
-      int job = -1;
-      long long t_last = wall_clock64();
-      int seen = -1;
-      for (;;) {
-        const int produced = __hip_atomic_load(&d.cnt->handback_n, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        int claimed = __hip_atomic_load(&d.cnt->handback_claimed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (claimed < produced) {
-          if (__hip_atomic_compare_exchange_strong(&d.cnt->handback_claimed, &claimed, claimed + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            // (the producer stores the entry right after counting it: a running wave, a few hundred cycles at most)
-            do job = __hip_atomic_load(&q.handback_list[claimed], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); while (job < 0);
-            break;
-          }
-          continue;
-        }
-        const int done = __hip_atomic_load(&d.cnt->quad_waves_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        if (done >= q.fb_waves) {
-          if (__hip_atomic_load(&d.cnt->handback_n, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == produced) break;   // nothing more can come
-          continue;
-        }
-        const int mark = produced + done + __hip_atomic_load(&d.cnt->quad_cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const long long now = wall_clock64();
-        if (mark != seen) { seen = mark; t_last = now; }
-        else if (now - t_last > 300000000ll) break;          // 3 s of the 100 MHz clock
-        __builtin_amdgcn_s_sleep(64);
-      }
-      g_job = job;
-    }
-    __syncthreads();
-    i = uni(g_job);
-    __syncthreads();
-    if (i < 0) return 0;
-  }
-  else mine = rqueue_entry(q, j, i, pos);
-  i = uni(i);
-  if (!mine) return 1;
-  // the most expensive classes are a tick's critical path (its longest search bounds it): their waves take the issue slots
-  // of their SIMD first, the five waves beside them fill in behind (`s_setprio`; TS_NO_PRIO: a build without it)
-#ifndef TS_NO_PRIO
-  if (j < n3) __builtin_amdgcn_s_setprio(3);
-  else if (j < n3 + n2) __builtin_amdgcn_s_setprio(2);
-  else __builtin_amdgcn_s_setprio(0);
-#endif
-  const long long c0 = S->calls, e0 = S->expansions, r0 = S->relaxations;
-#ifdef TS_TRACE_REPLAN
-  const long long tr0 = wall_clock64();
-  const int tr_bits = replan_cost_bits(d, max(d.active[i], 0));
-#endif
-  const int r = uni(decide_vehicle<DM_WAVE>(d, P, i, S));
-#ifdef TS_TRACE_REPLAN
-  if (threadIdx.x == 0 && g_rtrace && j < g_rtrace_cap && j < n3 + n2 + n1 + n0)
-    g_rtrace[j] = make_int4((int)(unsigned)tr0, (int)(unsigned)wall_clock64(), (int)(S->expansions - e0), tr_bits | ((int)blockIdx.x << 8));
-#endif
-  if (threadIdx.x == 0) {
-    if (r == DV_DONE) {  // work of attempts that are re-run after pool growth is not counted twice
-      const int vid = d.active[i];
-      if (S->calls > c0) d.tier_hint[vid] = (uint8_t)cost_bits(S->expansions - e0);
-      searcher_account(d, S->calls - c0, S->expansions - e0, S->relaxations - r0);
-      if (q.owned_list) q.owned_list[atomicAdd(&d.cnt->replan.owned_n, 1)] = i;
-    } else if (r == DV_OVERFLOW) atomicExch(&d.cnt->error, TS_E_CAPACITY);
-    else if (r == DV_POOL_FULL) q.retry_list[atomicAdd(&d.cnt->replan.retry_n, 1)] = i;
-  }
-  return 1;
-}
-
-// Replanning vehicles, one wave per searcher slot: every wave takes the next entry of the queue (RQueue) until it is empty;
-// all 64 lanes run the vehicle's step_decide together and share the work inside the searches.
-TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_replan(Dev d, TsParams P, ASlots sl, RQueueArgs qa) {
-  AScratch S;
-  scratch_bind(sl, blockIdx.x, S);
-  const RQueueFb q = {rqueue_open(d, qa), qa.fb_waves};
-  while (uni(replan_turn(d, P, &S, q))) {}
-  if (threadIdx.x == 0) sl.slot_epoch[blockIdx.x] = S.epoch;
-}
-
-// ---- replicated-state multi-GPU mode (ts_set_replan_sharding) ------------------------------------------------------
-// What step_decide changed about a vehicle this rank planned, for the ranks that did not: one fixed record plus the
-// 2-bit direction words of whatever paths the replan rewrote.
-struct ReplanRec {
-  int32_t i, vid, flags, base, cur, max_steps, cooldown, over_dur, det_dur, stranded_left, hint;
-  int32_t path_len, path_woff;          // path_woff < 0: the path was left as it is
-  int32_t ax_len[4], ax_start[4], ax_woff[4];
-  int32_t pad_[3];
-};
-static_assert(sizeof(ReplanRec) == 112, "ReplanRec is exchanged as 28 ints");
-// `count_only`: add up the words the export will need and touch nothing else (the host sizes the word buffer with it: the
-// pool's growth over the phase is no bound once a garbage collection ran inside it).
-__global__ void k_replan_export(Dev d, const int32_t* owned, int n, ReplanRec* recs, uint32_t* words, unsigned long long* words_n,
-                                int count_only) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int i = owned[t];
-  const int vid = d.active[i];
-  if (count_only) {
-    if (vid < 0) return;
-    const uint8_t chg = d.chg[vid];
-    unsigned long long nw = (chg & 1) ? (unsigned long long)((d.path_len[vid] + 15) >> 4) : 0ull;
-    for (int k = 0; k < 4; k++) if ((chg >> (1 + k)) & 1) nw += (unsigned long long)((d.ax_len[k][vid] + 15) >> 4);
-    if (nw) atomicAdd(words_n, nw);
-    return;
-  }
-  ReplanRec r;
-  r.i = i; r.vid = vid;
-  r.pad_[0] = r.pad_[1] = r.pad_[2] = 0;
-  if (vid < 0) { recs[t] = r; return; }
-  r.flags = d.flags[vid]; r.base = d.base_speed[vid]; r.cur = d.cur_speed[vid]; r.max_steps = d.max_steps[vid];
-  r.cooldown = d.cooldown[vid]; r.over_dur = d.over_dur[vid]; r.det_dur = d.det_dur[vid];
-  r.stranded_left = d.stranded_left[vid]; r.hint = d.tier_hint[vid];
-  const uint8_t chg = d.chg[vid];
-  d.chg[vid] = 0;
-  r.path_len = d.path_len[vid]; r.path_woff = -1;
-  if (chg & 1) {
-    const int nw = (r.path_len + 15) >> 4;
-    const unsigned long long w = atomicAdd(words_n, (unsigned long long)nw);
-    const uint32_t src = d.path_off[vid];
-    for (int q = 0; q < nw; q++) words[w + q] = d.pool[src + q];
-    r.path_woff = (int32_t)w;
-  }
-  for (int k = 0; k < 4; k++) {
-    r.ax_len[k] = d.ax_len[k][vid]; r.ax_start[k] = d.ax_start[k][vid]; r.ax_woff[k] = -1;
-    if ((chg >> (1 + k)) & 1) {
-      const int nw = (r.ax_len[k] + 15) >> 4;
-      const unsigned long long w = atomicAdd(words_n, (unsigned long long)nw);
-      const uint32_t src = d.ax_off[k][vid];
-      for (int q = 0; q < nw; q++) words[w + q] = d.pool[src + q];
-      r.ax_woff[k] = (int32_t)w;
-    }
-  }
-  recs[t] = r;
-}
-// the same in the other direction: records of vehicles another rank planned (pool capacity ensured by the host)
-__global__ void k_replan_import(Dev d, const ReplanRec* __restrict__ recs, int n, const uint32_t* __restrict__ words) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const ReplanRec r = recs[t];
-  const int vid = r.vid;
-  if (vid < 0) return;
-  d.flags[vid] = (uint16_t)r.flags; d.base_speed[vid] = (int8_t)r.base; d.cur_speed[vid] = (int8_t)r.cur;
-  d.max_steps[vid] = (int8_t)r.max_steps; d.cooldown[vid] = r.cooldown; d.over_dur[vid] = r.over_dur; d.det_dur[vid] = r.det_dur;
-  d.stranded_left[vid] = r.stranded_left; d.tier_hint[vid] = (uint8_t)r.hint;
-  if (r.path_woff >= 0) {
-    const int nw = (r.path_len + 15) >> 4;
-    const uint32_t o = (uint32_t)atomicAdd((unsigned long long*)&d.cnt->pool_used, (unsigned long long)nw);
-    for (int q = 0; q < nw; q++) d.pool[o + q] = words[r.path_woff + q];
-    d.path_off[vid] = o; d.path_len[vid] = r.path_len; d.path_cur[vid] = 0;
-  }
-  for (int k = 0; k < 4; k++) {
-    d.ax_len[k][vid] = r.ax_len[k];
-    if (r.ax_woff[k] >= 0) {
-      const int nw = (r.ax_len[k] + 15) >> 4;
-      const uint32_t o = (uint32_t)atomicAdd((unsigned long long*)&d.cnt->pool_used, (unsigned long long)nw);
-      for (int q = 0; q < nw; q++) d.pool[o + q] = words[r.ax_woff[k] + q];
-      d.ax_start[k][vid] = r.ax_start[k]; d.ax_off[k][vid] = o;
-    }
-  }
 }
 
 // one search on the current maps (the `astar(...)` operator seam, ts_astar) - searcher slot 0
@@ -1448,70 +693,6 @@ TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_astar_single(Dev d, TsPara
   sl.slot_epoch[0] = S.epoch;
   if (len >= 0) searcher_account(d, S.calls, S.expansions, S.relaxations);
   *out_len = len;  // -1 = heap / output capacity exceeded; the path cells are in the slot's A buffer
-}
-
-// VehicleAgent.__init__ -> self.path = self._compute_path() on a cache miss (vehicle_base.py:80-81, 143-167):
-// the phase 0-4 planner for a freshly placed vehicle.  status: path length, or -1 overflow / -2 pool full.
-TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_spawn_plan(Dev d, TsParams P, ASlots sl, int vid, int32_t* status) {
-  if (blockIdx.x) return;
-  const bool one = threadIdx.x == 0;
-  AScratch S;
-  scratch_bind(sl, 0, S);
-  VW v;
-  v.vid = vid; v.i = LAST_IDX; v.pos = d.pos[vid]; v.target = d.target[vid];
-  v.f = d.flags[vid]; v.base = 0; v.cur = 0; v.cooldown = P.pathfinding_cooldown;
-  v.over_dur = d.over_dur[vid]; v.det_dur = d.det_dur[vid]; v.stuck_ticks = d.stuck_ticks[vid];
-  v.newpath = false; v.plen = 0; v.pcur = 0; v.off = 0; v.d_overtaking = 0; v.d_detour = 0;
-  v.reach_known = false;
-  for (int k = 0; k < 4; k++) { v.ax_staged[k] = false; v.ax_len[k] = d.ax_len[k][vid]; }
-  int len;
-  bool ok = compute_path_internal_dev<DM_WAVE>(d, P, S, v, len);
-  if (one) sl.slot_epoch[0] = S.epoch;
-  if (!ok) { if (one) *status = -1; return; }
-  int words = (len + 15) / 16;
-  for (int k = 0; k < 4; k++) if (v.ax_staged[k]) words += (v.ax_len[k] + 15) / 16;
-  uint32_t off = 0;
-  if (words > 0 && !pool_alloc<DM_WAVE>(d, words, off)) { if (one) *status = -2; return; }
-  if (one) searcher_account(d, S.calls, S.expansions, S.relaxations);
-  encode_cells(d, off, v.pos, S.P, len);
-  d.path_off[vid] = off; d.path_len[vid] = len; d.path_cur[vid] = 0;
-  off += (len + 15) / 16;
-  for (int k = 0; k < 4; k++) {
-    if (!v.ax_staged[k]) continue;
-    encode_cells(d, off, v.pos, ax_buf(S, k), v.ax_len[k]);
-    d.ax_start[k][vid] = v.pos; d.ax_off[k][vid] = off; d.ax_len[k][vid] = v.ax_len[k];
-    off += (v.ax_len[k] + 15) / 16;
-  }
-  d.flags[vid] = v.f; d.over_dur[vid] = v.over_dur; d.det_dur[vid] = v.det_dur;
-  if (one && v.d_overtaking) atomicAdd((unsigned long long*)&d.cnt->overtaking, (unsigned long long)v.d_overtaking);
-  if (one && v.d_detour) atomicAdd((unsigned long long*)&d.cnt->in_stuck_detour, (unsigned long long)v.d_detour);
-  if (one) *status = len;
-}
-
-// path-pool garbage collection: every live vehicle copies the words it still needs into a fresh pool
-__global__ void k_pool_gc(Dev d, int n_active, uint32_t* new_pool, unsigned long long* new_used) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_active) return;
-  int vid = d.active[i];
-  if (vid < 0) return;
-  {
-    int cur = d.path_cur[vid], len = d.path_len[vid];
-    int w0 = cur >> 4, w1 = (len + 15) >> 4;
-    int words = w1 - w0;
-    uint32_t src = d.path_off[vid] + w0;
-    uint32_t dst = words > 0 ? (uint32_t)atomicAdd(new_used, (unsigned long long)words) : 0u;
-    for (int q = 0; q < words; q++) new_pool[dst + q] = d.pool[src + q];
-    d.path_off[vid] = dst; d.path_cur[vid] = cur & 15; d.path_len[vid] = len - (w0 << 4);
-  }
-  for (int k = 0; k < 4; k++) {
-    int len = d.ax_len[k][vid];
-    if (len <= 0) continue;
-    int words = (len + 15) >> 4;
-    uint32_t src = d.ax_off[k][vid];
-    uint32_t dst = (uint32_t)atomicAdd(new_used, (unsigned long long)words);
-    for (int q = 0; q < words; q++) new_pool[dst + q] = d.pool[src + q];
-    d.ax_off[k][vid] = dst;
-  }
 }
 
 }  // namespace

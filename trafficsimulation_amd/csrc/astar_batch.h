@@ -5,7 +5,7 @@
 // a scan of the lengths then gives the CSR offsets and k_batch_gather writes the (x, y) pairs in query order.  Nothing of
 // the result depends on the order of service.  The host side is astar_batch_api.h.
 #pragma once
-#include "astar.h"
+#include "astar.h"   // (the order helpers - cost classes, morton_block_key - are dev.h's: no policy, no replanning queue here)
 
 namespace {
 

@@ -1,6 +1,6 @@
 // astar_quad.h - the replanning searches, sixteen to a wavefront (k_replan_quad).
 //
-// k_replan (astar.h) spreads ONE search over the 64 lanes of a wave: 138 vector + 151 scalar instructions per expansion,
+// k_replan (replan.h) spreads ONE search over the 64 lanes of a wave: 138 vector + 151 scalar instructions per expansion,
 // issued for one expansion's worth of work (profiles/r03_sq_replan_4096.json).  Here a search owns a QUAD of four lanes -
 // lane j of the quad is direction j of astar_numba.py's neighbour loop (N, E, S, W) - and the sixteen quads of a wave run
 // sixteen independent searches through one branch-light loop in lockstep: every instruction issued serves sixteen
@@ -35,7 +35,7 @@
 // 25-30 % on a replanning wave, and slower than k_replan on a queue that is bounded by its longest search - run_replans
 // (engine.hip) sends them queues of TS_QUAD_MIN = 262 144 entries and more.
 #pragma once
-#include "astar.h"
+#include "replan.h"
 
 namespace {
 
@@ -93,17 +93,6 @@ constexpr int Q_HEAP_MAX = (QL + Q_SPILL) < (32 * QL - 2) ? (QL + Q_SPILL) : (32
 
 __shared__ unsigned long long q_lds[16 * QL + 64];     // (the last 64 entries: one scratch slot per lane, see q_lput_if)
 
-// quad_perm DPP: lane j of every quad reads lane P[j] of its quad
-template <int CTRL> __device__ __forceinline__ int qperm(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true); }
-constexpr int QP_SWAP1 = 0xB1;   // [1,0,3,2]
-constexpr int QP_SWAP2 = 0x4E;   // [2,3,0,1]
-constexpr int QP_B0 = 0x00, QP_B1 = 0x55, QP_B2 = 0xAA, QP_B3 = 0xFF;   // broadcasts of lane 0 .. 3
-__device__ __forceinline__ int quad_or(int v) {   // OR over the four lanes of the quad, in every lane
-  v |= qperm<QP_SWAP1>(v);
-  v |= qperm<QP_SWAP2>(v);
-  return v;
-}
-
 // what a quad keeps about its search while the lockstep loop runs (every lane of the quad holds the same values)
 struct QState {
   int hs;                   // heap_size
@@ -143,13 +132,8 @@ struct QConst {   // per quad, fixed for the kernel's lifetime
 
 // the table record of cell (x, y): the window's origin (ox, oy) is the search's start minus half a window when the map is
 // larger than the window, (0, 0) otherwise
-__device__ __forceinline__ uint32_t q_tix(const QConst& K, int ox, int oy, int x, int y) {
-  const uint32_t xm = (uint32_t)(x - ox), ym = (uint32_t)(y - oy);
-  return ((__umul24(ym >> 3, (uint32_t)K.tw8) + (xm >> 3)) << 6) | ((ym & 7u) << 3) | (xm & 7u);
-}
-__device__ __forceinline__ uint32_t q_aix(const QConst& K, int x, int y) {
-  return (((__umul24((uint32_t)(y >> 3), (uint32_t)K.W8) + (uint32_t)(x >> 3)) << 6) | (uint32_t)((y & 7) << 3) | (uint32_t)(x & 7));
-}
+__device__ __forceinline__ uint32_t q_tix(const QConst& K, int ox, int oy, int x, int y) { return tix(K.tw8, x - ox, y - oy); }
+__device__ __forceinline__ uint32_t q_aix(const QConst& K, int x, int y) { return tix(K.W8, x, y); }
 // heap slot k of the quad's search: LDS below QL, the search's HBM spill above.  The turn's hot path uses the LDS forms
 // only (no branch around a memory operation, no wait for the expansion's loads in flight); slots that may lie beyond QL
 // are touched in blocks of their own, which only run for quads whose heap has outgrown LDS.
@@ -275,7 +259,7 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
   const int last_i = s.hs - 1;
   const int f_top = hq_f(root);
   const uint32_t cxy = (uint32_t)hq_i(root);
-  const int cx = (int)(cxy & 0xFFFFu), cy = (int)(cxy >> 16);
+  int cx, cy; xy_unpack(cxy, cx, cy);
   const int prev_dir = s.dir0;
   const int xd = (int)((s.dwin >> (2 * ((last_i - s.wb) & 31))) & 3ull);
   s.hs = last_i;
@@ -345,7 +329,7 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
   const bool bad = (ok & (ngi > (int)Q_DIST_MASK)) | (cand & !inw);
   int relax = quad_or((ok ? (1 << j) : 0) | (bad ? 16 : 0));
   const int nf_l = ngi + abs(nx - s.gx) + abs(ny - s.gy);
-  const int nxy_l = (int)((uint32_t)nx | ((uint32_t)ny << 16));
+  const int nxy_l = xy_pack(nx, ny);
   QP(3);
   // ---- the sift-down finishes beyond LDS.  (Every path takes delivery of the two entries here, before the turn's stores
   // leave: a load still pending on some path would be waited for behind them - stores included - where its register is
@@ -477,18 +461,13 @@ __device__ __attribute__((noinline)) int quad_policy(const Dev& d, const TsParam
   if (r == DV_SUSPEND) {
     req.start = S.q_start; req.goal = S.q_goal; req.soft = S.q_soft; req.cap = S.q_cap; req.out = S.q_out;
   } else if (one) {
-    if (r == DV_DONE) {
-      const int vid = d.active[i];
-      if (S.calls > 0) d.tier_hint[vid] = (uint8_t)cost_bits(S.expansions);
-      searcher_account(d, S.calls, S.expansions, S.relaxations);
-      if (q.owned_list) q.owned_list[atomicAdd(&d.cnt->replan.owned_n, 1)] = i;
-    } else if (r == DV_POOL_FULL) q.retry_list[atomicAdd(&d.cnt->replan.retry_n, 1)] = i;
+    if (r == DV_DONE || r == DV_POOL_FULL) replan_settle(d, q, i, r, S.calls, S.expansions, S.relaxations);
     else { atomicAdd(&qs.stats[r == DV_BAIL ? QST_BAIL : QST_OVERFLOW], 1ull); __hip_atomic_store(&q.handback_list[atomicAdd(&d.cnt->handback_n, 1)], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }     // DV_BAIL, DV_OVERFLOW: k_replan takes the vehicle
   }
   return r;
 }
 
-// Replanning vehicles, sixteen per wave: every quad takes the next entry of the queue (RQueue, astar.h) until it is empty;
+// Replanning vehicles, sixteen per wave: every quad takes the next entry of the queue (RQueue, replan.h) until it is empty;
 // vehicles this searcher cannot carry are handed back to k_replan.
 __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs, RQueueArgs qa) {
   const int lane = (int)threadIdx.x, j = lane & 3;
@@ -533,7 +512,7 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
         if (st == QS_FOUND) {
           const TS_GLOBAL uint32_t* tab = K.tab;
           gi32p outg = (gi32p)(uintptr_t)req.out;
-          int px = (int)(s.goal_xy & 0xFFFFu), py = (int)(s.goal_xy >> 16);
+          int px, py; xy_unpack(s.goal_xy, px, py);
           while (px != s.sx || py != s.sy) {
             if (len >= req.cap) { len = -1; break; }
             outg[req.cap - 1 - len] = py * K.W + px;
@@ -591,14 +570,14 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
         cell_xy(d, req.goal, gxx, gyy); cell_xy(d, req.start, sxx, syy);
         s.gx = gxx; s.gy = gyy; s.sx = sxx; s.sy = syy;
         s.ox = K.chk_x ? sxx - (K.tw >> 1) : 0; s.oy = K.chk_y ? syy - (K.th >> 1) : 0;
-        s.goal_xy = (uint32_t)gxx | ((uint32_t)gyy << 16);
+        s.goal_xy = (uint32_t)xy_pack(gxx, gyy);
         s.stamp = epoch << Q_STAMP_SHIFT;
         s.soft = req.soft;
         s.n_exp = 0; s.n_relax = 0;
         s.dir0 = -1; s.wb = 0; s.dwin = 0;
         if (one) {
           K.tab[q_tix(K, s.ox, s.oy, sxx, syy)] = s.stamp;    // dist 0
-          q_lds[K.lbase] = hq_pack(abs(sxx - gxx) + abs(syy - gyy), (int)((uint32_t)sxx | ((uint32_t)syy << 16)));
+          q_lds[K.lbase] = hq_pack(abs(sxx - gxx) + abs(syy - gyy), xy_pack(sxx, syy));
         }
         s.hs = 1;
         wave_mem_sync();

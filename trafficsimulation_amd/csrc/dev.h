@@ -33,7 +33,7 @@ constexpr uint32_t NO_RANK = 0xFFFFFFFFu;
 constexpr uint8_t F_DRAW_MALF = 1, F_DRAW_SWIPE = 2, F_DRAW_SPEED = 4;
 constexpr uint32_t WORDS_MASK = (1u << 23) - 1;  // = MTPipe::TW_CAP - 1
 
-struct ReplanCtl {  // the counters of the replanning work queue (RQueue, astar.h): DevCnt::replan, mirrored in HostMirror::replan
+struct ReplanCtl {  // the counters of the replanning work queue (RQueue, replan.h): DevCnt::replan, mirrored in HostMirror::replan
   int class_n[4];  // class list lengths: k_decide_main counts, the replanning kernels read, requeue_in_list0 rewrites
   int retry_n;     // entries that found the path pool full (retry_list): the replanning kernels count, the host reads
   int cursor;      // k_replan's queue cursor: replan_turn pops, the host zeroes it with the whole struct
@@ -47,8 +47,8 @@ struct DevCnt {
   int deaths;      // vehicles removed this tick
   int arr_n;       // service records written this tick (Dev::arr)
   int error;       // sticky device-side error
-  ReplanCtl replan;      // the replanning work queue (RQueue, astar.h); the host mirrors it whole (HostMirror::replan)
-  int handback_n;        // the hand-back protocol (RQueue, astar.h; zeroed before a quad pass): produced - the quads count, replan_turn and the host read
+  ReplanCtl replan;      // the replanning work queue (RQueue, replan.h); the host mirrors it whole (HostMirror::replan)
+  int handback_n;        // the hand-back protocol (RQueue, replan.h; zeroed before a quad pass): produced - the quads count, replan_turn and the host read
   int quad_cursor;       // the quads' queue cursor: the quads pop, replan_turn reads it as a sign of progress
   int handback_claimed;  // hand-backs claimed: replan_turn's tickets, the host reads how many were served
   int quad_waves_done;   // quad waves that have counted themselves out: k_replan_quad's last act, replan_turn waits on it
@@ -113,7 +113,7 @@ struct Dev {
   int32_t* ax_start[4];
   uint32_t* ax_off[4];
   int32_t* ax_len[4];
-  uint8_t* tier_hint;  // per vehicle: bit length of the expansions its last replan took (astar.h: cost_bits), orders the replanning work queue
+  uint8_t* tier_hint;  // per vehicle: bit length of the expansions its last replan took (cost_bits, below), orders the replanning work queue
   uint8_t* chg;        // per vehicle: what its replan of this tick rewrote (bit 0 path, bits 1-4 aux paths) - read and cleared by
                        // k_replan_export in the multi-GPU mode
   // what a search reads about a cell, as of the last tick start (or the last ensure_amap), in tiled order: low word =
@@ -167,19 +167,42 @@ struct Dev {
 __device__ __forceinline__ int path_dir(const uint32_t* pool, uint32_t off, int k) {
   return (pool[off + ((uint32_t)k >> 4)] >> ((k & 15) * 2)) & 3;
 }
+// pool words of a direction string of `len` steps (sixteen 2-bit directions per word)
+__device__ __forceinline__ int path_words(int len) { return (len + 15) >> 4; }
 __device__ __forceinline__ int step_cell(int cell, int dir, int W) {
   return dir == 0 ? cell + W : dir == 1 ? cell + 1 : dir == 2 ? cell - W : cell - 1;
 }
 __device__ __forceinline__ void set_occ(const Dev& d, int c, int8_t v) { d.cell[c].occ = v; d.occ[c] = v; }
 __device__ __forceinline__ void set_stop(const Dev& d, int c, int8_t v) { d.cell[c].stop = v; d.stop[c] = v; }
 // cell -> (x, y) without an integer division (falls back to one when the map is beyond the magic number's range)
-__device__ __forceinline__ void cell_xy(const Dev& d, int cell, int& x, int& y) {
-  if (d.w_magic) { y = (int)(((unsigned long long)(unsigned)cell * d.w_magic) >> 40); x = cell - y * d.W; }
-  else { y = cell / d.W; x = cell - y * d.W; }
+__device__ __forceinline__ void cell_xy(int W, unsigned long long w_magic, int cell, int& x, int& y) {
+  if (w_magic) { y = (int)(((unsigned long long)(unsigned)cell * w_magic) >> 40); x = cell - y * W; }
+  else { y = cell / W; x = cell - y * W; }
 }
-// position of cell (x, y) in the 8 x 8-tiled order
-__device__ __forceinline__ uint32_t tix(const Dev& d, int x, int y) {
-  return ((((uint32_t)(y >> 3) * (uint32_t)d.W8 + (uint32_t)(x >> 3)) << 6) | (uint32_t)((y & 7) << 3) | (uint32_t)(x & 7));
+__device__ __forceinline__ void cell_xy(const Dev& d, int cell, int& x, int& y) { cell_xy(d.W, d.w_magic, cell, x, y); }
+// position of cell (x, y) in the 8 x 8-tiled order of a map (or a table window) `tiles` tiles wide
+__device__ __forceinline__ uint32_t tix(int tiles, int x, int y) {
+  // (tile rows and tiles per row are far below 2^24: the full-rate 24-bit multiply)
+  return (((__umul24((uint32_t)(y >> 3), (uint32_t)tiles) + (uint32_t)(x >> 3)) << 6) | (uint32_t)((y & 7) << 3) | (uint32_t)(x & 7));
+}
+__device__ __forceinline__ uint32_t tix(const Dev& d, int x, int y) { return tix(d.W8, x, y); }
+// Work-queue order of the replans (largest first).  Per vehicle the bit length of the expansions its last replan took is
+// kept (Dev::tier_hint); the four classes are ranges of it (< 2 048, < 32 768, < 262 144 expansions, more), and inside a
+// class the queue is sorted by it again (run_replans), so that the longest search of a tick starts first.
+// (Here and not in replan.h: ts_astar_batch orders its queries by the same classes and blocks, astar_batch.h.)
+__device__ __forceinline__ int cost_bits(long long expansions) {
+  return 64 - __builtin_clzll((unsigned long long)max(expansions, 0ll) | 1ull);
+}
+__device__ __forceinline__ int cost_class_of_bits(int b) { return b < 12 ? 0 : b < 16 ? 1 : b < 19 ? 2 : 3; }
+// ... and for a vehicle without history, from the distance to its target: the searches are Dijkstra-like (the heuristic is
+// far below the penalties), so they touch on the order of md^2 / 2 cells
+__device__ __forceinline__ int cost_bits_of_distance(int md) { return md < 60 ? 8 : md < 240 ? 13 : md < 680 ? 17 : 19; }
+// ... and inside a class in space: the Morton index of the 32 x 32-cell block of (x, y)
+__device__ __forceinline__ uint32_t morton_block_key(int x, int y) {
+  const uint32_t bx = (uint32_t)x >> 5, by = (uint32_t)y >> 5;
+  uint32_t k = 0;
+  for (int b = 0; b < 8; b++) k |= ((bx >> b) & 1u) << (2 * b) | ((by >> b) & 1u) << (2 * b + 1);
+  return k;
 }
 __device__ __forceinline__ uint32_t claim_rank(uint32_t v, uint32_t prefix) {
   return (v >> RANK_BITS) == prefix ? (v & RANK_MASK) : NO_RANK;

@@ -37,6 +37,8 @@
 
 #include "dev.h"
 #include "astar.h"
+#include "decide.h"
+#include "replan.h"
 #include "astar_quad.h"
 #include "astar_batch.h"
 #include "observe.h"
@@ -65,7 +67,7 @@ int read_back(E* e, void* dst, const void* src, size_t bytes) {
   return TS_OK;
 }
 
-// entries in the replanning work queue (RQueue, astar.h) as k_decide_main or the last pass left it
+// entries in the replanning work queue (RQueue, replan.h) as k_decide_main or the last pass left it
 inline int replan_pending(const ReplanCtl& r) { return r.class_n[0] + r.class_n[1] + r.class_n[2] + r.class_n[3]; }
 inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 
@@ -130,7 +132,7 @@ int replan_pass_done(E* e) {
 }
 
 // The quad pass of a big queue (see run_replans): the classes in TS_QUAD_CLASSES go to k_replan_quad while k_replan serves the
-// others and the quads' hand-backs beside it (RQueue, astar.h).  What neither got to is queued again in list 0.
+// others and the quads' hand-backs beside it (RQueue, replan.h).  What neither got to is queued again in list 0.
 int run_quad_pass(E* e) {
   Dev& d = e->d;
   const TsParams& P = e->P;

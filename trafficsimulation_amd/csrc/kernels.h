@@ -1,4 +1,4 @@
-// kernels.h - the per-tick device kernels other than the A* family (astar.h): decide front, move rounds, compaction, events.
+// kernels.h - the per-tick device kernels other than the A* family (astar.h, decide.h, replan.h): decide front, move rounds, compaction, events.
 // Part of the single translation unit engine.hip (included from there, in order).
 #pragma once
 
