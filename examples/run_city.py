@@ -15,11 +15,11 @@ TRAFFIC = dict(P_int=10000, P_thr=2400, dt=6, start_offset=6 * 3600, service_foo
                max_load_food=50.0, max_load_waste=250.0, load_time=20, gradual=True, food_capacity_per_cell=2.0,
                waste_capacity_per_cell=1.5, food_consumption_ticks=50, waste_production_ticks=100)
 
-def run(size, seed, ticks, every=50, engine=None, traffic=None, defaults=None, out=print, observe=False, **world_kwargs):
+def run(size, seed, ticks, every=50, engine=None, traffic=None, defaults=None, out=print, observe=False, trip_log=None, **world_kwargs):
     from trafficsimulation_amd.mesa_api import CityModel
     t0 = time.time()
     m = CityModel(size, size, seed=seed, defaults=defaults or {}, traffic=dict(TRAFFIC, **(traffic or {})), engine=engine,
-                  **world_kwargs)
+                  trip_log=trip_log, **world_kwargs)
     out(f"city {m.width}x{m.height} seed {seed}: {len(m.intersection_light_groups)} light groups, {len(m.city_blocks)} blocks, "
         f"{len(m.get_start_blocks())} entries, built in {time.time() - t0:.1f} s")
     if observe:
@@ -43,10 +43,20 @@ if __name__ == "__main__":
     ap.add_argument("--every", type=int, default=50)
     ap.add_argument("--carve", action="store_true", help="carve_subblock_roads=True (BASELINE config 5 style)")
     ap.add_argument("--heatmap", metavar="OUT.npy", default=None, help="write the run's flow (cells entered), pooled 8 x 8, to this file")
+    ap.add_argument("--trips", metavar="OUT.npy", default=None, help="write one record per finished trip (capi.TRIP_DTYPE) to this file")
+    ap.add_argument("--trip-capacity", type=int, default=1 << 20, help="records the trip log holds (later ones are dropped and counted)")
     a = ap.parse_args()
     kw = dict(carve_subblock_roads=True) if a.carve else {}
-    m = run(a.size, a.seed, a.ticks, a.every, observe=bool(a.heatmap), **kw)
+    m = run(a.size, a.seed, a.ticks, a.every, observe=bool(a.heatmap), trip_log=a.trip_capacity if a.trips else None, **kw)
     if a.heatmap:
         import numpy as np
         from trafficsimulation_amd import _capi as capi
         np.save(a.heatmap, sum(m.engine.observe_pooled(n, 8) for n in capi.OBS_ENTER))
+    if a.trips:
+        import numpy as np
+        rec, info = m.trips(), m.engine.triplog_info()
+        np.save(a.trips, rec)
+        od = m.od_matrix()
+        o, d = divmod(int(od["count"].argmax()), len(od["zones"]))
+        print(f"{len(rec)} trips logged ({info['dropped']} dropped), {int(od['count'].sum())} arrived between known zones; "
+              f"busiest pair: {od['zones'][o]} -> {od['zones'][d]} ({int(od['count'][o, d])} trips)")

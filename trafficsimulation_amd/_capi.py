@@ -95,6 +95,20 @@ class TsObserveInfo(C.Structure):
                 ("device_bytes", C.c_uint64)]
 
 
+# include/trafficsim_triplog.h: TsTripRecord as a numpy record, the TS_TRIP_END_* codes, TsTripLogInfo
+TRIP_DTYPE = np.dtype([(n, np.int32) for n in (
+    "spawn_idx", "population", "vehicle_type", "end_reason", "origin_x", "origin_y", "dest_x", "dest_y", "end_x", "end_y",
+    "spawn_step", "end_step", "distance", "stuck_ticks")] + [("depart_elapsed", np.float64), ("end_elapsed", np.float64)])
+assert TRIP_DTYPE.itemsize == 72
+TRIP_END = {"arrived": 0, "despawned": 1, "removed": 2}
+TRIPLOG_MAX_ZONES = 1024
+
+
+class TsTripLogInfo(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("count", C.c_int64), ("dropped", C.c_int64), ("groups", C.c_int64),
+                ("device_bytes", C.c_uint64)]
+
+
 class TsCounters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "stuck", "collisions", "malfunctions", "overtaking", "in_stuck_detour", "parked", "live_internal",
@@ -849,6 +863,124 @@ class CApi:
             raise RuntimeError("observe_device: torch cannot reach the engine's device - import torch before the engine "
                                "library is loaded, or download with observe_plane") from ex
         return t.view(torch.int32).view(self.H, self.W)
+
+    # ---- trip log (include/trafficsim_triplog.h) ----------------------------------------------------
+    def _tl_fn(self, name: str):
+        """The trip-log entries, bound on first use: the CPU oracle shares this class and has none of them."""
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no trip log")
+        fn.restype = C.c_int64 if name == "triplog_read" else C.c_int
+        fn.argtypes = {"triplog_start": [C.c_void_p, C.c_int64],
+                       "triplog_stop": [C.c_void_p],
+                       "triplog_clear": [C.c_void_p],
+                       "triplog_info": [C.c_void_p, C.POINTER(TsTripLogInfo)],
+                       "triplog_read": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+                       "triplog_device": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)],
+                       "triplog_set_zones": [C.c_void_p, C.c_void_p, C.c_int32],
+                       "triplog_od": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]}[name]
+        return fn
+
+    @property
+    def has_triplog(self) -> bool:
+        return self.prefix == "ts_" and hasattr(self.lib, "ts_triplog_start")
+
+    def triplog_start(self, capacity: int):
+        """Allocate a log of `capacity` records and log every vehicle that leaves from now on.  Starting again frees the old
+        log: the new one is empty."""
+        self._chk(self._tl_fn("triplog_start")(self.h, max(min(int(capacity), 2 ** 63 - 1), -1)))
+        self._tl_zones = 0
+
+    def triplog_stop(self):
+        self._chk(self._tl_fn("triplog_stop")(self.h))
+        self._tl_zones = 0
+
+    def triplog_clear(self):
+        """Empty the log; capacity and zone plane stay."""
+        self._chk(self._tl_fn("triplog_clear")(self.h))
+
+    def triplog_info(self) -> dict:
+        """{"capacity", "count", "dropped", "groups", "device_bytes"}; all zero when the log is off."""
+        info = TsTripLogInfo()
+        self._chk(self._tl_fn("triplog_info")(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in TsTripLogInfo._fields_}
+
+    def trips(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Records [first, first + n) of the log (default: all from `first` on) as a TRIP_DTYPE array, in log order."""
+        fn = self._tl_fn("triplog_read")
+        if n is None:
+            n = max(self.triplog_info()["count"] - int(first), 0)
+        out = np.zeros(max(int(n), 1), dtype=TRIP_DTYPE)
+        got = self._chk(fn(self.h, int(first), int(n), out.ctypes.data))
+        return out[:got]
+
+    def triplog_device(self, device=None):
+        """The kept records as a (count, 18) int32 torch tensor over the engine's own device memory (no copy; a record is 18
+        words: the 14 int32 fields, then the two doubles as word pairs; valid until triplog_stop, the next triplog_start or
+        close).  torch must have been imported before the engine library was loaded, as for observe_device."""
+        fn = self._tl_fn("triplog_device")
+        try:
+            import torch
+        except ImportError as ex:
+            raise RuntimeError("triplog_device needs torch (use trips for a host array)") from ex
+        ptr, count = C.c_void_p(), C.c_int64()
+        self._chk(fn(self.h, C.byref(ptr), C.byref(count)))
+        from .dist import ShardedReplans
+        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        if count.value == 0:
+            return torch.zeros((0, 18), dtype=torch.int32, device=device)
+        try:
+            t = ShardedReplans._wrap_device(ptr.value, count.value * TRIP_DTYPE.itemsize, device)
+        except RuntimeError as ex:
+            raise RuntimeError("triplog_device: torch cannot reach the engine's device - import torch before the engine "
+                               "library is loaded, or download with trips") from ex
+        return t.view(torch.int32).view(-1, 18)
+
+    def triplog_set_zones(self, zone_of_cell, n_zones: int):
+        """One (H, W) int32 plane: the zone 0 .. n_zones - 1 of every cell, -1 = none.  n_zones = 0 drops the plane."""
+        fn = self._tl_fn("triplog_set_zones")
+        z = None
+        if zone_of_cell is not None:
+            z = np.ascontiguousarray(zone_of_cell, dtype=np.int32)
+            if z.shape != (self.H, self.W):
+                raise ValueError(f"the zone plane must be ({self.H}, {self.W}), got {z.shape}")
+        self._chk(fn(self.h, z.ctypes.data if z is not None else None, max(min(int(n_zones), 0x7FFFFFFF), -1)))
+        self._tl_zones = int(n_zones)
+
+    @staticmethod
+    def _tl_mask(reasons) -> int:
+        if reasons is None:
+            return sum(1 << k for k in TRIP_END.values())
+        if isinstance(reasons, (int, np.integer)):
+            return int(reasons)
+        mask = 0
+        for r in ([reasons] if isinstance(reasons, str) else reasons):
+            if r not in TRIP_END:
+                raise ValueError(f"unknown end reason {r!r} (one of {', '.join(TRIP_END)})")
+            mask |= 1 << TRIP_END[r]
+        return mask
+
+    def triplog_od(self, reasons=None, count=True, duration=True, distance=True) -> dict:
+        """Origin / destination sums over the records whose end reason is in `reasons` (names, a bit mask, default all),
+        reduced on the device: {"count" uint64, "duration" float64, "distance" uint64} as (n_zones, n_zones) arrays indexed
+        [zone(origin), zone(dest)] (a matrix switched off is left out), and "unzoned"."""
+        fn = self._tl_fn("triplog_od")
+        nz = getattr(self, "_tl_zones", 0)
+        out = {}
+        if count:
+            out["count"] = np.zeros((nz, nz), dtype=np.uint64)
+        if duration:
+            out["duration"] = np.zeros((nz, nz), dtype=np.float64)
+        if distance:
+            out["distance"] = np.zeros((nz, nz), dtype=np.uint64)
+        unz = C.c_uint64()
+        ptr = {k: (v.ctypes.data if v.size else None) for k, v in out.items()}
+        mask = self._tl_mask(reasons)
+        if not 0 <= mask <= 0xFFFFFFFF:
+            raise ValueError(f"reason mask {mask} does not fit 32 bits")
+        self._chk(fn(self.h, mask, ptr.get("count"), ptr.get("duration"), ptr.get("distance"), C.byref(unz)))
+        out["unzoned"] = int(unz.value)
+        return out
 
     BATCH_INFO = ("slots", "side_slots", "arena_shared", "arena_quad", "last_waves", "last_usable", "last_arena_quad",
                   "last_passes", "device")

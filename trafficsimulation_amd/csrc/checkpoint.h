@@ -591,6 +591,9 @@ int ts_checkpoint_load(ts_handle e, const void* src, uint64_t n) {
   e->roll_guess = 0; e->take_guess = 0; e->take_n = 0;
   e->quad_last_fb = -1;
   e->prof_pending.clear(); e->ev_used = 0;
+  // the trip log keeps its records; it did not see any of these vehicles being placed
+  e->tl_pending = 0;
+  if (e->tl_on) TRY(tl_forget_origins(e));
   return TS_OK;
 }
 

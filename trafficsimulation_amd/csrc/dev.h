@@ -4,6 +4,7 @@
 #include <cstdint>
 #include "../../include/trafficsim.h"
 #include "../../include/trafficsim_observe.h"
+#include "../../include/trafficsim_triplog.h"
 
 #define BLK 256
 
@@ -84,6 +85,8 @@ __host__ __device__ __forceinline__ int st_is_road(uint8_t s) { return (s >> 4) 
 __host__ __device__ __forceinline__ int st_inter(uint8_t s) { return (s >> 5) & 1; }
 __host__ __device__ __forceinline__ int st_road_type(uint8_t s) { return (s >> 6) & 3; }
 
+struct TripLog;   // triplog.h
+
 struct Dev {
   int W, H, N;
   int W8, H8;                   // the map in 8 x 8 tiles (tiled order of the A* snapshot and tables, see tix)
@@ -135,10 +138,13 @@ struct Dev {
   int32_t* bslot;     // schedule slot of every CityBlock, kept by compaction
   int32_t* arr;       // service records, 3 ints each (see AR_*)
   int arr_cap;
+  int tl_step;        // the trip log (triplog.h): TsCounters::step_count as its hooks record it - the host sets it before every
+                      // tick and every entry that places or removes vehicles (here: the padding behind arr_cap)
   uint32_t* rank;     // per schedule slot
   uint8_t* resolved;  // per schedule slot, this move phase
-  // light groups (CSR tables + state)
-  int G;
+  // light groups (CSR tables + state); gc_n: see gc_cell below (the two ints share one 8-byte slot: Dev is copied into
+  // the scratch of the A* kernels, its size is part of their resource budget)
+  int G, gc_n;
   int32_t *g_light_off, *light_cell, *light_ctrl_off, *light_ctrl, *g_ns_off, *g_ns, *g_ew_off, *g_ew, *g_icell_off,
       *g_icell, *g_nsin_off, *g_nsin, *g_nsout_off, *g_nsout, *g_ewin_off, *g_ewin, *g_ewout_off, *g_ewout, *g_nb,
       *g_nb_ctor, *g_slot;
@@ -146,7 +152,6 @@ struct Dev {
   // round of a move phase claims them with one thread per pair instead of one thread walking a whole group
   int32_t *gc_cell, *gc_group;
   uint8_t* gc_plane;
-  int gc_n;
   int32_t *gs_cur, *gs_pend, *gs_trans, *gs_clear, *gs_ftphase, *gs_fttimer, *gs_qtimer, *gs_gap, *gs_last, *gs_nsp,
       *gs_ewp, *gs_repop;
   // per-cell min-rank claims for the move phase live in Cell::claim (epoch-tagged so they never need clearing)
@@ -162,7 +167,10 @@ struct Dev {
   // any of the four ENTER planes that is held (nullptr: none) - the one test the move kernel makes.
   uint32_t* obs[TS_OBS_NPLANES];
   uint32_t* obs_enter;
+  // the trip log (triplog.h): its arrays and counters, nullptr = off - the one test k_spawn and remove_vehicle_dev make
+  TripLog* tlog;
 };
+static_assert(sizeof(Dev) == 976, "Dev travels by value and lies in the A* kernels' scratch: new members go into its padding");
 
 __device__ __forceinline__ int path_dir(const uint32_t* pool, uint32_t off, int k) {
   return (pool[off + ((uint32_t)k >> 4)] >> ((k & 15) * 2)) & 3;

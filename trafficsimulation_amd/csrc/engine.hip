@@ -42,6 +42,7 @@
 #include "astar_quad.h"
 #include "astar_batch.h"
 #include "observe.h"
+#include "triplog.h"
 #include "kernels.h"
 #include "host_state.h"
 #include "host_shuffle.h"
@@ -818,6 +819,7 @@ int decide_stretches(E* e, TickState& ts, const std::vector<int32_t>& standing) 
       ci++;
     }
   }
+  e->tl_pending += removed;
   if (removed > 0) {   // the schedule is shuffled without them (RandomActivation.step takes the live keys)
     TRY(compact_lists(e, removed));
     ts.nA = e->n_active; ts.nS = e->n_sched;
@@ -1084,6 +1086,7 @@ int move_phase(E* e, TickState& ts) {
     e->prev_discs = ts.discs;
   }
   e->C.agent_steps += sched_vehicles_at_shuffle;
+  e->tl_pending += ts.dev_deaths;
   if (ts.dev_deaths + ts.host_deaths > 0) return compact_lists(e, ts.dev_deaths);   // spawns of this tick are part of the lists by now
   return TS_OK;
 }
@@ -1100,6 +1103,7 @@ int tick(E* e) {
   // vehicle at a time is the reference's own speed limit for this switch; nothing about it is parallel.
   ts.seq = !P.pathfinding_batching;
   d.seq = ts.seq ? 1 : 0;
+  d.tl_step = (int)e->C.step_count;
   if (ts.seq && e->dist_world > 1) return fail(e, TS_E_UNSUPPORTED, "PATHFINDING_BATCHING=False has no sharded form (its decisions are sequential)");
   std::vector<int32_t> standing;
   if (e->standing_possible && ts.nA > 0 && !ts.seq) TRY(find_standing(e, ts.nA, standing));
@@ -1136,6 +1140,9 @@ int tick(E* e) {
   host_prof(e, PH_MOVE_WALL, now_ms() - t_move0, ts.nS);
   if (e->clock_slot >= 0 && !e->gen.armed) e->C.elapsed += P.time_per_step_seconds;  // an armed generator did it in its step
   e->C.step_count++;
+  // the trip log (triplog.h): this tick's removals become one group of records, in ascending vehicle id
+  if (d.tlog && e->tl_pending > 0) TRY(tl_seal(e));
+  e->tl_pending = 0;
   // traffic observation (observe.h): the tick's ENTER increments were made by the move kernel; sample the live vehicles where
   // they stand now (the lists are compacted: exactly the rows ts_download_vehicles would return)
   if (e->obs_mask) {
@@ -1690,6 +1697,7 @@ static int add_vehicles_core(ts_handle e, int n, std::vector<int32_t>& start, st
   if (words) HIPOK(hipMemcpyAsync(e->d.pool + e->pool_used, enc.data(), words * 4, hipMemcpyHostToDevice, st));
   HIPOK(hipMemsetAsync(e->d_total, 0, sizeof(int), st));
   SpawnArgs a{ds, dg, dp, dl, dof, dser};
+  e->d.tl_step = (int)e->C.step_count;
   hipLaunchKernelGGL(k_spawn, dim3(nblk(n)), dim3(BLK), 0, st, e->d, e->P, a, n, e->n_vehicles_total, e->n_active,
                      e->n_sched, e->C.elapsed, e->d_overflow, e->d_total, (e->d.amap && e->amap_valid) ? 1 : 0);
   HIPOK(hipMemcpyAsync(&e->hm->scratch, e->d_total, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1857,7 +1865,9 @@ int ts_remove_vehicle(ts_handle e, int32_t spawn_idx, int32_t population_type) {
   HIPOK(hipMemcpy(&fl, d.flags + spawn_idx, 2, hipMemcpyDeviceToHost));
   if (!(fl & VF_ALIVE)) return fail(e, TS_E_INVALID, "no such live vehicle");
   if (fl & VF_SVC) return fail(e, TS_E_UNSUPPORTED, "service vehicles cannot be removed by the host");
-  hipLaunchKernelGGL(k_remove_one, dim3(1), dim3(64), 0, e->stream, d, spawn_idx, (int)population_type);
+  d.tl_step = (int)e->C.step_count;
+  hipLaunchKernelGGL(k_remove_one, dim3(1), dim3(64), 0, e->stream, d, spawn_idx, (int)population_type, e->C.elapsed);
+  if (d.tlog) { e->tl_pending++; TRY(tl_seal(e)); }   // a host removal is a group of its own
   // the lists close up at once (the reference's list.remove / schedule.remove): the next tick shuffles the live keys
   TRY(compact_lists(e, 1));
   HIPOK(hipMemsetAsync(&d.cnt->deaths, 0, sizeof(int), e->stream));
@@ -2171,3 +2181,4 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
 #include "checkpoint.h"
 #include "astar_batch_api.h"
 #include "observe_api.h"
+#include "triplog_api.h"

@@ -335,6 +335,7 @@ int spawn_service_at(E* e, int origin, int kind, int id) {
   v.load = food ? v.max_load : 0.0;
   v.phase = phase; v.ticks = 0; v.pos = origin; v.target = target;
   e->svc.push_back(v);
+  if (e->tl_on) { const int8_t ty = (int8_t)kind; HIPOK(hipMemcpyAsync(e->tl.vtype + vid, &ty, 1, hipMemcpyHostToDevice, e->stream)); HIPOK(hipStreamSynchronize(e->stream)); }
   if (food) e->C.live_service_food++; else e->C.live_service_waste++;
   return TS_OK;
 }

@@ -197,8 +197,10 @@ __device__ __forceinline__ void cell_append(const Dev& d, int cell, int vid) {
 }
 
 // CityModel.remove_vehicle (city_model.py:1920-1941): off the maps, the cell list, the schedule and the decide order
-// (pop_arg: the population_type argument of CityModel.remove_vehicle; the vehicle's own despawn passes its own, -1 here)
-__device__ __forceinline__ void remove_vehicle_dev(const Dev& d, int vid, int s, int pos, uint16_t& f, int key, int pop_arg = -1) {
+// (pop_arg: the population_type argument of CityModel.remove_vehicle; the vehicle's own despawn passes its own, -1 here;
+// reason / elapsed: the TS_TRIP_END_* code and the clock of this removal, for the trip log)
+__device__ __forceinline__ void remove_vehicle_dev(const Dev& d, int vid, int s, int pos, uint16_t& f, int key, int reason,
+                                                   double elapsed, int pop_arg = -1) {
   set_occ(d, pos, 0); d.cell[pos].stuck = 0;
   cell_unlink(d, pos, vid);
   f &= ~VF_ALIVE;
@@ -209,6 +211,7 @@ __device__ __forceinline__ void remove_vehicle_dev(const Dev& d, int vid, int s,
   else if (pop == TS_POP_THROUGH) atomicAdd((unsigned long long*)&d.cnt->live_through, (unsigned long long)-1LL);
   atomicAdd(&d.cnt->deaths, 1);
   if (f & VF_SVC) svc_record(d, key, vid, AR_DESPAWN);
+  if (d.tlog) tl_remove_dev(d, vid, reason, elapsed);
 }
 
 // on_target_reached (vehicle_base.py:755-775) -> _despawn -> CityModel.remove_vehicle (city_model.py:1920-1941)
@@ -235,7 +238,7 @@ __device__ void on_target_reached_dev(const Dev& d, const TsParams& P, int vid, 
     }
   }
   if (!(f & VF_KEEP)) {
-    remove_vehicle_dev(d, vid, s, pos, f, key);
+    remove_vehicle_dev(d, vid, s, pos, f, key, TS_TRIP_END_ARRIVED, elapsed_now);
   } else if (!(f & VF_PARKED)) {
     f |= VF_PARKED;
     atomicAdd((unsigned long long*)&d.cnt->parked, 1ULL);
@@ -332,7 +335,7 @@ __device__ __forceinline__ void vehicle_step_dev(const Dev& d, const TsParams& P
       if (f & VF_STUCK) { atomicAdd((unsigned long long*)&d.cnt->stuck, (unsigned long long)-1LL); f &= ~VF_STUCK; }
       if (d.pop[vid] == TS_POP_INTERNAL) atomicAdd((unsigned long long*)&d.cnt->errored_internal, 1ULL);
       else atomicAdd((unsigned long long*)&d.cnt->errored_through, 1ULL);
-      remove_vehicle_dev(d, vid, s, pos, f, key);
+      remove_vehicle_dev(d, vid, s, pos, f, key, TS_TRIP_END_DESPAWNED, elapsed_now);
     }
   }
   if (f & VF_SVCNEW) f = (f & ~VF_SVCNEW) | VF_SERVICING;   // (the step() in which _start_service ran inside step_decide is over)
@@ -676,6 +679,7 @@ __global__ void k_spawn(Dev d, TsParams P, SpawnArgs a, int n, int vid0, int act
   d.active[active0 + i] = vid; d.active_idx[vid] = active0 + i;
   d.sched_kind[sched0 + i] = K_VEHICLE; d.sched_ref[sched0 + i] = vid; d.sched_slot[vid] = sched0 + i;
   set_occ(d, pos, 1); d.cell[pos].stuck = 0;  // place_vehicle (city_model.py:1897-1918)
+  if (d.tlog) tl_spawn_dev(d, vid, pos);
   if (a.serial[i] || atomicCAS(&d.cell[pos].veh, -1, vid) != -1) overflow[atomicAdd(n_overflow, 1)] = vid;
 }
 __global__ void k_spawn_serial(Dev d, int* overflow, int n_overflow) {  // cells holding several vehicles: list order = spawn order
@@ -920,10 +924,10 @@ __global__ void k_live_stats(Dev d, int n_active, double elapsed, double* out) {
     if (smax) atomicMax(&oi[7], (unsigned long long)smax);
   }
 }
-__global__ void k_remove_one(Dev d, int vid, int pop_arg) {
+__global__ void k_remove_one(Dev d, int vid, int pop_arg, double elapsed) {
   if (threadIdx.x || blockIdx.x) return;
   uint16_t f = d.flags[vid];
-  remove_vehicle_dev(d, vid, d.sched_slot[vid], d.pos[vid], f, 0, pop_arg);
+  remove_vehicle_dev(d, vid, d.sched_slot[vid], d.pos[vid], f, 0, TS_TRIP_END_REMOVED, elapsed, pop_arg);
   d.flags[vid] = f;
 }
 // (schedule slot, rank) of CityBlocks (which = 0, ids = block index) or vehicles (which = 1, ids = vehicle id)

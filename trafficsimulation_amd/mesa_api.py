@@ -647,7 +647,8 @@ class CityModel:
 
     def __init__(self, width=200, height=200, seed=None, defaults: Optional[dict] = None, tables: Optional[dict] = None,
                  engine: Optional[capi.CApi] = None, global_seed: Optional[int] = None, global_state=None,
-                 sched_state=None, traffic: Optional[dict] = None, world: str = "reference", **world_kwargs):
+                 sched_state=None, traffic: Optional[dict] = None, world: str = "reference", trip_log: Optional[int] = None,
+                 **world_kwargs):
         import random as _random
         self._seed = seed if seed is not None else _random.random()
         if traffic is not None and "gradual_city_block_resources" in world_kwargs:   # ctor kwarg -> CityBlock mode (city_model.py:50, 1735)
@@ -676,6 +677,10 @@ class CityModel:
         # random.setstate()-style states take precedence over integer seeds (exact replays of a reference run)
         build_engine(engine, tables, defaults=defaults or {}, global_seed=gseed, sched_seed=sched_seed,
                      global_state=global_state, sched_state=sched_state)
+        # trip_log=capacity: the trip log (include/trafficsim_triplog.h) is on before the first vehicle is placed, so every
+        # record knows its origin
+        if trip_log is not None:
+            engine.triplog_start(int(trip_log))
         # DynamicTrafficAgent("DTA", self) (city_model.py:203-204): traffic = {"P_int", "P_thr", "start_offset",
         # "service_food", "service_waste", ...} arms the engine's generator; it draws day 0 from the global stream now
         self._service_cfg = dict(traffic or {})
@@ -905,6 +910,51 @@ class CityModel:
             out["mean_speed"] = np.divide(out["speed"].astype(np.float64), present, out=np.full(present.shape, np.nan), where=present > 0)
         out["ticks"] = info["ticks"]
         return out
+
+    # ---- trip log (include/trafficsim_triplog.h) ----------------------------------------------------
+    def trips(self) -> np.ndarray:
+        """One `capi.TRIP_DTYPE` record per vehicle that has left since the model was built with `trip_log=capacity`, in the
+        log's canonical order (tick by tick, ascending spawn index inside a tick).  Like observation the log is not carried by
+        save / load / deepcopy / pickle: the model those give has the log off."""
+        return self.engine.trips()
+
+    def _block_zones(self):
+        """(zone plane (H, W) int32, zone names): one zone per city block, made of the block's entrances, then one for the
+        highway entrances and one for the highway exits."""
+        t = self.tables
+        zone = np.full((self.height, self.width), -1, dtype=np.int32)
+        names = []
+        if "blk_entr_off" in t:
+            eoff, exy = np.asarray(t["blk_entr_off"]), np.asarray(t["blk_entr_xy"]).reshape(-1, 2)
+            ids = np.asarray(t["blk_id"]) if "blk_id" in t else np.arange(1, len(eoff))
+            for b in range(len(eoff) - 1):
+                xy = exy[eoff[b]:eoff[b + 1]]
+                zone[xy[:, 1], xy[:, 0]] = len(names)
+                names.append(f"block_{int(ids[b])}")
+        for key, name in (("highway_entrances_xy", "highway_entrances"), ("highway_exits_xy", "highway_exits")):
+            xy = np.asarray(t.get(key, np.zeros((0, 2))), dtype=np.int64).reshape(-1, 2)
+            zone[xy[:, 1], xy[:, 0]] = len(names)
+            names.append(name)
+        return zone, names
+
+    def od_matrix(self, by: str = "block", reasons=("arrived",)) -> dict:
+        """Origin / destination matrix of the logged trips whose end reason is in `reasons` (`capi.TRIP_END` names), summed
+        on the device: {"zones": names, "count": (Z, Z) uint64 indexed [origin zone, destination zone], "mean_duration" and
+        "mean_distance": (Z, Z) float64, NaN where no trip was counted, "unzoned": trips with an unknown origin or an end
+        outside every zone}.  `by="block"`: one zone per city block (its entrances), one for all highway entrances, one for
+        all highway exits."""
+        if by != "block":
+            raise ValueError(f"od_matrix: unknown zoning {by!r} (only 'block')")
+        zone, names = self._block_zones()
+        if len(names) > capi.TRIPLOG_MAX_ZONES:
+            raise ValueError(f"od_matrix: {len(names)} zones, the engine takes {capi.TRIPLOG_MAX_ZONES}")
+        self.engine.triplog_set_zones(zone, len(names))
+        od = self.engine.triplog_od(reasons)
+        n = od["count"].astype(np.float64)
+        nan = np.full(n.shape, np.nan)
+        return {"zones": names, "count": od["count"], "unzoned": od["unzoned"],
+                "mean_duration": np.divide(od["duration"], n, out=nan.copy(), where=n > 0),
+                "mean_distance": np.divide(od["distance"].astype(np.float64), n, out=nan.copy(), where=n > 0)}
 
     def intersection_report(self) -> List[dict]:
         """Per light group, over the ticks observed: vehicle-ticks waiting on the N-S and on the W-E approaches (and the
