@@ -43,14 +43,17 @@ enum {
   TS_E_CAPACITY = -5     /* a fixed-size device pool overflowed */
 };
 
-/* Defaults.TRAFFIC_LIGHT_AGENT_ALGORITHM (config.py:341-347); RL variants are out of scope. */
+/* Defaults.TRAFFIC_LIGHT_AGENT_ALGORITHM (config.py:341-347).  Of the learning variants only the environment side of
+ * "NEIGHBOR_RL_BATCHED" exists, as TS_LIGHTS_EXTERNAL: the groups decide nothing in their own step() and are driven from
+ * outside through trafficsim_lights_ext.h.  The other RL variants are out of scope. */
 enum {
   TS_LIGHTS_DISABLED = 0,
   TS_LIGHTS_FIXED_TIME = 1,
   TS_LIGHTS_QUEUE_ACTUATED = 2,
   TS_LIGHTS_PRESSURE_CONTROL = 3,
   TS_LIGHTS_NEIGHBOR_PRESSURE_CONTROL = 4,
-  TS_LIGHTS_NEIGHBOR_GREEN_WAVE = 5
+  TS_LIGHTS_NEIGHBOR_GREEN_WAVE = 5,
+  TS_LIGHTS_EXTERNAL = 6
 };
 
 /* The subset of config.py `Defaults` that the hot path reads.  Field names follow the

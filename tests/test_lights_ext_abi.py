@@ -1,0 +1,105 @@
+"""The external-control entries (include/trafficsim_lights_ext.h) without a GPU: the header declares exactly them, the two
+structs have the layout the Python binding declares, the algorithm names map to TS_LIGHTS_EXTERNAL, the HIP library exports
+the entries, and the oracle-backed CApi - which shares the class and has no external control - refuses them cleanly."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from trafficsimulation_amd import _capi as capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ["ts_lights_ext_act", "ts_lights_ext_config", "ts_lights_ext_device", "ts_lights_ext_download", "ts_lights_ext_info",
+           "ts_lights_ext_observe", "ts_lights_ext_request", "ts_lights_ext_set_static"]
+
+
+def header(name):
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+
+
+def test_header_declares_exactly_the_entries():
+    assert sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", header("trafficsim_lights_ext.h")))) == ENTRIES
+
+
+def test_algorithm_names():
+    src = header("trafficsim.h")
+    assert re.search(r"\bTS_LIGHTS_EXTERNAL\s*=\s*6\b", src)
+    assert capi.LIGHT_ALGORITHMS["EXTERNAL"] == capi.LIGHT_ALGORITHMS["NEIGHBOR_RL_BATCHED"] == 6
+    assert sorted(set(capi.LIGHT_ALGORITHMS.values())) == list(range(7))
+    for name in ("NEIGHBOR_RL", "RL_A2C_BATCHED", "GAT_DQN", "GAT_DQN_BATCHED"):      # the other RL names keep their refusal
+        assert name not in capi.LIGHT_ALGORITHMS
+    # nothing else of the extension leaks into the main header
+    assert "lights_ext" not in src.replace("trafficsim_lights_ext.h", "") and "TsLightsExt" not in src
+    ext = header("trafficsim_lights_ext.h")
+    assert re.search(r"#define\s+TS_LIGHTS_EXT_DEFAULT_DIM\s+13\b", ext) and re.search(r"#define\s+TS_LIGHTS_EXT_DEFAULT_MIN_GREEN\s+5\b", ext)
+    assert re.search(rf"#define\s+TS_LIGHTS_EXT_MAX_DIM\s+{max(capi.LIGHTS_EXT_DIMS)}\b", ext)
+
+
+def test_params_accept_the_names_and_refuse_the_other_rl_variants():
+    from oracle import pyoracle
+    api = capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
+    for name in ("EXTERNAL", "NEIGHBOR_RL_BATCHED"):
+        assert api.params_from_defaults({"TRAFFIC_LIGHT_AGENT_ALGORITHM": name}).light_algorithm == 6
+    with pytest.raises(capi.EngineError) as ex:
+        api.params_from_defaults({"TRAFFIC_LIGHT_AGENT_ALGORITHM": "GAT_DQN"})
+    assert ex.value.code == capi.TS_E_UNSUPPORTED
+
+
+def test_struct_layouts(tmp_path):
+    """sizeof and every offsetof of TsLightsExtInfo and TsLightsExtDevice, as a C compiler sees the header."""
+    structs = [("TsLightsExtInfo", capi.TsLightsExtInfo), ("TsLightsExtDevice", capi.TsLightsExtDevice)]
+    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "trafficsim_lights_ext.h"', 'int main(void) {']
+    for cname, cls in structs:
+        prog.append(f'  printf("%zu\\n", sizeof({cname}));')
+        prog += [f'  printf("%zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
+    prog += ['  return 0;', '}']
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(prog))
+    exe = tmp_path / "layout"
+    subprocess.run([os.environ.get("CC", "cc"), "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    k = 0
+    for cname, cls in structs:
+        assert out[k] == ctypes.sizeof(cls), cname
+        assert out[k + 1:k + 1 + len(cls._fields_)] == [getattr(cls, f).offset for f, _ in cls._fields_], cname
+        k += 1 + len(cls._fields_)
+    assert ctypes.sizeof(capi.TsLightsExtInfo) == 32 and ctypes.sizeof(capi.TsLightsExtDevice) == 40
+
+
+def test_hip_library_exports_the_entries():
+    import __graft_entry__ as ge
+    ge.build_hip()
+    from trafficsimulation_amd._lib import LIB_PATH
+    lib = ctypes.CDLL(LIB_PATH)
+    for s in ENTRIES:
+        assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
+
+
+def oracle_api():
+    from oracle import pyoracle
+    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
+
+
+def test_oracle_capi_has_no_external_control():
+    assert oracle_api().has_lights_ext is False
+
+
+@pytest.mark.parametrize("call", ["config", "set_static", "info", "observe", "act", "request", "controller", "device"])
+def test_oracle_external_control_is_unsupported(call):
+    api = oracle_api()
+    api.n_groups = 3
+    z = np.zeros(3, np.int8)
+    calls = {"config": lambda: api.lights_config(13, 5), "set_static": lambda: api.lights_set_static(np.zeros(3), np.zeros(3)),
+             "info": api.lights_info, "observe": api.lights_observe, "act": lambda: api.lights_act(z),
+             "request": lambda: api.lights_request(z), "controller": api.lights_controller, "device": api.lights_device}
+    with pytest.raises(capi.EngineError) as ex:
+        calls[call]()
+    assert ex.value.code == capi.TS_E_UNSUPPORTED
+
+
+def test_approach_penalty_score_is_the_mean_of_the_penalties():
+    got = capi.approach_penalty_score([[4, 2, 2, 0], [0, 0, 0, 0], [3, 0, 0, 3], [5, 1, 0, 0]], (0.5, 5, 50.0))
+    assert np.array_equal(got, [2.75, 0.0, 50.0, 0.1])

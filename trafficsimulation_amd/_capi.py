@@ -18,7 +18,11 @@ TS_OK, TS_E_INVALID, TS_E_STATE, TS_E_DEVICE, TS_E_UNSUPPORTED, TS_E_CAPACITY = 
 LIGHT_ALGORITHMS = {
     "DISABLED": 0, "FIXED_TIME": 1, "QUEUE_ACTUATED": 2, "PRESSURE_CONTROL": 3,
     "NEIGHBOR_PRESSURE_CONTROL": 4, "NEIGHBOR_GREEN_WAVE": 5,
+    # external control (include/trafficsim_lights_ext.h): the groups decide nothing in their own step(); the reference's name
+    # for it is its batched learning controller, whose environment side this is
+    "EXTERNAL": 6, "NEIGHBOR_RL_BATCHED": 6,
 }
+LIGHTS_EXT_DIMS = (7, 11, 13, 17, 19)
 M_FIELDS = ["spawn_idx", "population", "target_x", "target_y", "vehicle_type", "service_phase"]
 TRIP_SERVICE_FOOD, TRIP_SERVICE_WASTE = 3, 4
 AGENT_LIGHT_GROUP, AGENT_NOOP, AGENT_RAIN_MANAGER, AGENT_CLOCK, AGENT_CITY_BLOCK = 0, 1, 2, 3, 6
@@ -107,6 +111,16 @@ TRIPLOG_MAX_ZONES = 1024
 class TsTripLogInfo(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("count", C.c_int64), ("dropped", C.c_int64), ("groups", C.c_int64),
                 ("device_bytes", C.c_uint64)]
+
+
+class TsLightsExtInfo(C.Structure):
+    _fields_ = [("state_dim", C.c_int32), ("min_green", C.c_int32), ("n_groups", C.c_int32), ("observed", C.c_int32),
+                ("calls", C.c_int64), ("device_bytes", C.c_uint64)]
+
+
+class TsLightsExtDevice(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("next_state", C.c_void_p), ("controller", C.c_void_p), ("stored", C.c_void_p),
+                ("n_groups", C.c_int32), ("state_dim", C.c_int32)]
 
 
 class TsCounters(C.Structure):
@@ -237,6 +251,17 @@ def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
 
+def approach_penalty_score(counts, penalties) -> np.ndarray:
+    """IntersectionLightGroup.penalty_score (intersection_light_group.py:156-165) from a (G, 4) table of
+    [blocks, R1 blocks, R2 blocks, R3 blocks] per group and the three road-type penalties: their mean over the blocks.
+    The reference adds the penalties block by block; the counts give the same double whenever every partial sum is exact -
+    penalties that are multiples of a power of two, like config.py's 0.5 / 5 / 50 - and may differ from it in the last bit
+    otherwise (the table does not carry the order of the blocks)."""
+    c = np.asarray(counts, dtype=np.float64).reshape(-1, 4)
+    p1, p2, p3 = (float(p) for p in penalties)
+    return np.where(c[:, 0] > 0, (c[:, 1] * p1 + c[:, 2] * p2 + c[:, 3] * p3) / np.maximum(c[:, 0], 1), 0.0)
+
+
 def path_crc(xy) -> int:
     """crc32 of a path as int32 (x, y) pairs, 0 if empty - the TS_V_PATH_CRC convention."""
     a = _i32(xy).reshape(-1, 2)
@@ -337,6 +362,8 @@ class CApi:
         rc = self._f("create")(C.byref(w), C.byref(params), C.byref(self.h))
         if rc < 0:
             raise EngineError(rc, "create failed")
+        self._light_algorithm = int(params.light_algorithm)
+        self._road_type_penalties = (float(params.road_type_penalty_r1), float(params.road_type_penalty_r2), float(params.road_type_penalty_r3))
         return self
 
     def close(self):
@@ -373,6 +400,10 @@ class CApi:
             setattr(t, k, v.ctypes.data)
         self._chk(self._f("set_lights")(self.h, C.byref(t)))
         self.n_groups = t.n_groups
+        # external control: penalty_score from the cells' own road types where the tables carry them (the road_type plane the
+        # engine falls back to shows an R2 cell of the ring road as R1)
+        if "g_approach_road_types" in tables and self.prefix == "ts_" and getattr(self, "_light_algorithm", None) == LIGHT_ALGORITHMS["EXTERNAL"]:
+            self.lights_set_static(penalty_score=approach_penalty_score(tables["g_approach_road_types"], self._road_type_penalties))
 
     def cached_stats(self) -> Dict[str, object]:
         """DynamicTrafficAgent.cached_stats as the statistics panel reads it (ui_modules/traffic_statistics.py): the
@@ -980,6 +1011,133 @@ class CApi:
             raise ValueError(f"reason mask {mask} does not fit 32 bits")
         self._chk(fn(self.h, mask, ptr.get("count"), ptr.get("duration"), ptr.get("distance"), C.byref(unz)))
         out["unzoned"] = int(unz.value)
+        return out
+
+    # ---- external light control (include/trafficsim_lights_ext.h) ------------------------------------
+    def _le_fn(self, name: str):
+        """The external-control entries, bound on first use: the CPU oracle shares this class and has none of them."""
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no external light control")
+        fn.restype = C.c_int
+        fn.argtypes = {"lights_ext_config": [C.c_void_p, C.c_int32, C.c_int32],
+                       "lights_ext_set_static": [C.c_void_p, C.c_void_p, C.c_void_p],
+                       "lights_ext_observe": [C.c_void_p, C.c_void_p],
+                       "lights_ext_act": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
+                       "lights_ext_request": [C.c_void_p, C.c_void_p, C.c_int32],
+                       "lights_ext_download": [C.c_void_p, C.c_void_p],
+                       "lights_ext_device": [C.c_void_p, C.POINTER(TsLightsExtDevice)],
+                       "lights_ext_info": [C.c_void_p, C.POINTER(TsLightsExtInfo)]}[name]
+        return fn
+
+    @property
+    def has_lights_ext(self) -> bool:
+        return self.prefix == "ts_" and hasattr(self.lib, "ts_lights_ext_observe")
+
+    def lights_config(self, state_dim: int = 13, min_green: int = 5):
+        """SRL_INPUT_DIMENSIONS (7, 11, 13, 17 or 19) and SRL_MIN_GREEN; only before the first control call."""
+        self._chk(self._le_fn("lights_ext_config")(self.h, int(state_dim), int(min_green)))
+
+    def lights_set_static(self, intersection_size=None, penalty_score=None):
+        """The two static features of every group as float64 [G] (None = leave); only before the first control call."""
+        fn = self._le_fn("lights_ext_set_static")
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (intersection_size, penalty_score)]
+        for v in a:
+            if v is not None and v.shape != (self.n_groups,):
+                raise ValueError(f"a static feature must have shape ({self.n_groups},), got {v.shape}")
+        self._chk(fn(self.h, *(v.ctypes.data if v is not None and v.size else None for v in a)))
+
+    def lights_info(self) -> dict:
+        """{"state_dim", "min_green", "n_groups", "observed", "calls", "device_bytes"}"""
+        info = TsLightsExtInfo()
+        self._chk(self._le_fn("lights_ext_info")(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in TsLightsExtInfo._fields_}
+
+    def lights_observe(self, to_host: bool = True):
+        """Phase A: the state vector of every group, (G, state_dim) float32.  A second call before the next lights_act or
+        step returns the same (cached) vector.  to_host=False only runs it (the vector is in lights_device()["state"])."""
+        fn = self._le_fn("lights_ext_observe")
+        if not to_host:
+            self._chk(fn(self.h, None))
+            return None
+        dim = self.lights_info()["state_dim"]
+        out = np.zeros((max(self.n_groups, 1), dim), dtype=np.float32)
+        self._chk(fn(self.h, out.ctypes.data))
+        return out[:self.n_groups]
+
+    def _le_bytes(self, v, what):
+        """An int8 vector of one entry per group as (pointer, on_device, keep-alive): numpy / sequences on the host, a torch
+        tensor on the engine's device as it is."""
+        if type(v).__module__.split(".")[0] == "torch":
+            import torch
+            if v.dtype != torch.int8 or v.dim() != 1 or v.shape[0] != self.n_groups or not v.is_contiguous():
+                raise ValueError(f"{what}: a torch tensor must be contiguous int8 of shape ({self.n_groups},)")
+            if v.is_cuda:
+                dev = self.debug_batch_info()["device"]
+                if v.device.index != dev:
+                    raise ValueError(f"{what}: the tensor is on {v.device}, the engine on cuda:{dev}")
+                torch.cuda.current_stream(v.device).synchronize()   # (the engine reads it on its own stream)
+                return v.data_ptr(), 1, v
+            v = v.numpy()
+        a = np.ascontiguousarray(np.clip(np.asarray(v, dtype=np.int64), -128, 127), dtype=np.int8)
+        if a.shape != (self.n_groups,):
+            raise ValueError(f"{what}: one entry per group ({self.n_groups}), got shape {a.shape}")
+        return a.ctypes.data, 0, a
+
+    def lights_act(self, actions, want_next: bool = True):
+        """Phase B with one action (0 keep, 1 switch) per group - numpy, a sequence, or an int8 torch tensor on the engine's
+        device (read there, no copy).  Runs phase A first if lights_observe has not run since the last step.  Returns the
+        next-state vectors (G, state_dim) float32, or None with want_next=False."""
+        fn = self._le_fn("lights_ext_act")
+        ptr, on_dev, keep = self._le_bytes(actions, "actions")
+        out = None
+        if want_next:
+            out = np.zeros((max(self.n_groups, 1), self.lights_info()["state_dim"]), dtype=np.float32)
+        self._chk(fn(self.h, ptr, on_dev, out.ctypes.data if out is not None else None))
+        del keep
+        return out[:self.n_groups] if out is not None else None
+
+    def lights_request(self, phases):
+        """apply_phase(phase) on every group whose entry is 0 or 1; -1 = no request.  For controllers that do not follow the
+        observe / act protocol; touches none of its state."""
+        fn = self._le_fn("lights_ext_request")
+        ptr, on_dev, keep = self._le_bytes(phases, "phases")
+        self._chk(fn(self.h, ptr, on_dev))
+        del keep
+
+    def lights_controller(self) -> np.ndarray:
+        """(G, 2) int32: _rl_phase, rl_timer of every group."""
+        fn = self._le_fn("lights_ext_download")
+        out = np.zeros((max(self.n_groups, 1), 2), dtype=np.int32)
+        self._chk(fn(self.h, out.ctypes.data))
+        return out[:self.n_groups]
+
+    def lights_device(self, device=None) -> dict:
+        """{"state", "next_state": (G, state_dim) float32, "controller", "stored": (G, 2) int32} as torch tensors over the
+        engine's own device memory (no copy; valid until close; the engine rewrites them in every control call).  torch must
+        have been imported before the engine library was loaded, as for observe_device."""
+        fn = self._le_fn("lights_ext_device")
+        try:
+            import torch
+        except ImportError as ex:
+            raise RuntimeError("lights_device needs torch (use lights_observe / lights_controller for host arrays)") from ex
+        d = TsLightsExtDevice()
+        self._chk(fn(self.h, C.byref(d)))
+        from .dist import ShardedReplans
+        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        G, dim = int(d.n_groups), int(d.state_dim)
+        if G == 0:
+            z = lambda w, t: torch.zeros((0, w), dtype=t, device=device)   # noqa: E731
+            return {"state": z(dim, torch.float32), "next_state": z(dim, torch.float32), "controller": z(2, torch.int32), "stored": z(2, torch.int32)}
+        try:
+            wrap = lambda p, n: ShardedReplans._wrap_device(p, n, device)   # noqa: E731
+            out = {"state": wrap(d.state, G * dim * 4).view(torch.float32).view(G, dim),
+                   "next_state": wrap(d.next_state, G * dim * 4).view(torch.float32).view(G, dim),
+                   "controller": wrap(d.controller, G * 8).view(torch.int32).view(G, 2),
+                   "stored": wrap(d.stored, G * 8).view(torch.int32).view(G, 2)}
+        except RuntimeError as ex:
+            raise RuntimeError("lights_device: torch cannot reach the engine's device - import torch before the engine "
+                               "library is loaded, or use lights_observe") from ex
         return out
 
     BATCH_INFO = ("slots", "side_slots", "arena_shared", "arena_quad", "last_waves", "last_usable", "last_arena_quad",

@@ -189,6 +189,17 @@ std::vector<int32_t**> ck_group_columns(Dev& d) {
           &d.gs_last, &d.gs_nsp, &d.gs_ewp, &d.gs_repop, &d.g_slot};
 }
 
+// The external light control (lights_ext_api.h): a trailing section, written only under TS_LIGHTS_EXTERNAL - blobs of every
+// other algorithm are what they were.  The scalars, then the controller columns [G][2], the stored pressures [G][2] and the
+// cached state vector [G][dim] (meaningful while `observed` is set).
+struct CkLightsExt {
+  uint32_t magic;
+  int32_t dim, min_green, observed;
+  int64_t calls;
+};
+constexpr uint32_t CK_LE_MAGIC = 0x3154584Cu;   // "LXT1"
+static_assert(sizeof(CkLightsExt) == 24, "checkpoint: external light control section");
+
 // what is in flight between two ticks: the shuffle pipeline (idle once tick() returned), the take-ahead table on the copy
 // stream, the permutation copies, the quad searcher's stream and the main stream
 int ck_drain(E* e) {
@@ -313,6 +324,14 @@ int ck_write(E* e, CkSink& s, uint64_t path_words, bool stage) {
   s.dev(d.hslot, (size_t)e->n_host_agents * 4);
   s.dev(d.bslot, (size_t)e->blocks_scheduled * 4);
   for (int32_t** g : ck_group_columns(d)) s.dev(*g, (size_t)d.G * 4);
+  if (e->P.light_algorithm == TS_LIGHTS_EXTERNAL && e->le.ready) {
+    const LightsExt& x = e->le.x;
+    const CkLightsExt L{CK_LE_MAGIC, x.dim, x.min_green, e->le.observed ? 1 : 0, e->le.calls};
+    s.val(L);
+    s.dev(x.ctrl, (size_t)x.G * 8);
+    s.dev(x.stored, (size_t)x.G * 8);
+    s.dev(x.state, (size_t)x.G * x.dim * 4);
+  }
   return TS_OK;
 }
 
@@ -478,6 +497,19 @@ int ts_checkpoint_load(ts_handle e, const void* src, uint64_t n) {
   auto gcols = ck_group_columns(d);
   std::vector<const uint8_t*> g_p;
   for (size_t k = 0; k < gcols.size(); k++) g_p.push_back(r.take((size_t)d.G * 4));
+  const bool le_on = e->P.light_algorithm == TS_LIGHTS_EXTERNAL && e->le.ready;
+  CkLightsExt L{};
+  const uint8_t *le_ctrl_p = nullptr, *le_stored_p = nullptr, *le_state_p = nullptr;
+  if (le_on) {
+    if (!r.val(L) || L.magic != CK_LE_MAGIC) return bad("external light control");
+    if (L.dim != e->le.x.dim || L.min_green != e->le.x.min_green)
+      return fail(e, TS_E_INVALID, "checkpoint: the blob's external light control has dimension " + std::to_string(L.dim) + " and min-green " +
+                  std::to_string(L.min_green) + ", the handle is configured with " + std::to_string(e->le.x.dim) + " and " + std::to_string(e->le.x.min_green));
+    if (L.calls < 0 || (L.observed != 0 && L.observed != 1) || (L.observed && L.calls == 0)) return bad("external light control");
+    le_ctrl_p = r.take((size_t)d.G * 8);
+    le_stored_p = r.take((size_t)d.G * 8);
+    le_state_p = r.take((size_t)d.G * L.dim * 4);
+  }
   if (!r.ok) return bad("device sections truncated");
   if (r.pos != n) return bad("trailing bytes");
   {
@@ -549,6 +581,11 @@ int ts_checkpoint_load(ts_handle e, const void* src, uint64_t n) {
     for (size_t k = 0; k < gcols.size(); k++) HIPOK(hipMemcpyAsync(*gcols[k], g_p[k], (size_t)d.G * 4, hipMemcpyHostToDevice, st));
     HIPOK(hipMemsetAsync(d.gclaim_r, 0xFF, (size_t)d.G * 4, st));
   }
+  if (le_on && d.G) {
+    HIPOK(hipMemcpyAsync(e->le.x.ctrl, le_ctrl_p, (size_t)d.G * 8, hipMemcpyHostToDevice, st));
+    HIPOK(hipMemcpyAsync(e->le.x.stored, le_stored_p, (size_t)d.G * 8, hipMemcpyHostToDevice, st));
+    HIPOK(hipMemcpyAsync(e->le.x.state, le_state_p, (size_t)d.G * L.dim * 4, hipMemcpyHostToDevice, st));
+  }
   // counters: the device block with the bump allocator at the packed pool's end
   S.cnt.pool_used = S.path_words;
   *e->hcnt = S.cnt;
@@ -594,6 +631,7 @@ int ts_checkpoint_load(ts_handle e, const void* src, uint64_t n) {
   // the trip log keeps its records; it did not see any of these vehicles being placed
   e->tl_pending = 0;
   if (e->tl_on) TRY(tl_forget_origins(e));
+  if (le_on) { e->le.calls = L.calls; e->le.observed = L.observed != 0; }
   return TS_OK;
 }
 

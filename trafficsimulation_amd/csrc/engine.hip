@@ -44,6 +44,7 @@
 #include "observe.h"
 #include "triplog.h"
 #include "kernels.h"
+#include "lights_ext.h"
 #include "host_state.h"
 #include "host_shuffle.h"
 #include "host_agents.h"
@@ -1104,6 +1105,7 @@ int tick(E* e) {
   ts.seq = !P.pathfinding_batching;
   d.seq = ts.seq ? 1 : 0;
   d.tl_step = (int)e->C.step_count;
+  e->le.observed = false;   // (lights_ext_api.h: the maps move, a cached state vector ends here)
   if (ts.seq && e->dist_world > 1) return fail(e, TS_E_UNSUPPORTED, "PATHFINDING_BATCHING=False has no sharded form (its decisions are sequential)");
   std::vector<int32_t> standing;
   if (e->standing_possible && ts.nA > 0 && !ts.seq) TRY(find_standing(e, ts.nA, standing));
@@ -1481,6 +1483,7 @@ int ts_set_lights(ts_handle e, const TsLightTables* t) {
   d.G = G;
   e->lights_set = true;
   e->groups_scheduled = 0;
+  if (e->P.light_algorithm == TS_LIGHTS_EXTERNAL) TRY(le_init(e));
   return TS_OK;
 }
 
@@ -2182,3 +2185,4 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
 #include "astar_batch_api.h"
 #include "observe_api.h"
 #include "triplog_api.h"
+#include "lights_ext_api.h"

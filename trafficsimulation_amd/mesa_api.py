@@ -22,8 +22,12 @@ Differences from the reference that a caller can observe:
   * with `traffic={...}` the engine's traffic generator spawns internal / through / service vehicles itself;
     they show up as VehicleAgent / ServiceVehicleAgent views (ids "V_<spawn index>" / "SV_<spawn index>": the
     reference's id strings are not kept on the device), `model.city_blocks` holds CityBlock views.
-  * RL light controllers are out of scope; rain clouds are not exposed as agents (only
-    `model.rain_map`).
+  * learning light controllers are not part of the engine.  Under TRAFFIC_LIGHT_AGENT_ALGORITHM = "EXTERNAL" (or the
+    reference's name "NEIGHBOR_RL_BATCHED") the groups decide nothing themselves and the caller drives them between ticks:
+    `model.light_states()`, `model.control_lights(actions)`, `model.request_phases(phases)`
+    (include/trafficsim_lights_ext.h); the policy and its training are the caller's torch code.  The other RL variants
+    (NEIGHBOR_RL, RL_A2C_BATCHED, GAT_DQN*) are out of scope.
+  * rain clouds are not exposed as agents (only `model.rain_map`).
 """
 from __future__ import annotations
 
@@ -489,6 +493,9 @@ class IntersectionLightGroup:
     fixed_time_timer = property(lambda s: s._f("fixed_time_timer"))
     ns_pressure = property(lambda s: s._f("ns_pressure"))
     ew_pressure = property(lambda s: s._f("ew_pressure"))
+    # external light control only (intersection_light_group.py:91-92)
+    _rl_phase = property(lambda s: int(s.model._light_controller()[s.index, 0]))
+    rl_timer = property(lambda s: int(s.model._light_controller()[s.index, 1]))
 
     # ---- links (intersection_light_group.py:293-307) --------------------------------------------------------------
     def get_opposite_traffic_lights(self):
@@ -661,6 +668,8 @@ class CityModel:
             # engine's global stream continues from where that leaves it, as the reference's agents would
             from . import worldgen
             d = defaults or {}
+            if capi.LIGHT_ALGORITHMS.get(d.get("TRAFFIC_LIGHT_AGENT_ALGORITHM")) == capi.LIGHT_ALGORITHMS["EXTERNAL"]:
+                world_kwargs = dict(world_kwargs, approach_road_types=True)   # (penalty_score of the state vector)
             tables = worldgen.generate_world(width, height, seed=global_seed if global_seed is not None else self._seed,
                                              rain_enabled=bool(d.get("RAIN_ENABLED", True)), enable_traffic=traffic is not None,
                                              block_entrance_road_level=int(d.get("BLOCK_ENTRANCE_ROAD_LEVEL", 0)), **world_kwargs)
@@ -835,6 +844,33 @@ class CityModel:
         if s["groups"] is None:
             s["groups"] = self.engine.groups()
         return s["groups"]
+
+    def _light_controller(self):
+        s = self._snapshot()
+        if s.get("light_ctrl") is None:
+            s["light_ctrl"] = self.engine.lights_controller()
+        return s["light_ctrl"]
+
+    # ---- external light control (include/trafficsim_lights_ext.h), between two step() calls ---------------------------
+    def light_states(self) -> np.ndarray:
+        """The state vector of every light group, (G, SRL_INPUT_DIMENSIONS) float32, as the reference's get_rl_state
+        builds it (rl_simple.py:95-143).  Calling it again before control_lights or step returns the same vectors."""
+        self._flush_host_writes()
+        return self.engine.lights_observe()
+
+    def control_lights(self, actions) -> np.ndarray:
+        """One action per group (0 keep, 1 ask for the other phase; numpy, a sequence or an int8 torch tensor on the
+        engine's device): the reference's action protocol (rl_simple.py:226-236).  Returns the next-state vectors."""
+        self._flush_host_writes()
+        out = self.engine.lights_act(actions)
+        self._invalidate()
+        return out
+
+    def request_phases(self, phases) -> None:
+        """apply_phase(phase) on every group whose entry is 0 or 1 (-1 = none), for controllers of any other kind."""
+        self._flush_host_writes()
+        self.engine.lights_request(phases)
+        self._invalidate()
 
     def _counters(self):
         s = self._snapshot()

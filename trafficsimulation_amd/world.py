@@ -22,6 +22,11 @@ def build_engine(api: capi.CApi, tables, defaults: Optional[dict] = None, params
     api.create(tables["allowed_dirs_map"], tables["is_road_map"], tables["road_type_map"],
                tables["intersection_map"], p)
     api.set_lights(tables)
+    # external light control (include/trafficsim_lights_ext.h): SRL_INPUT_DIMENSIONS / SRL_MIN_GREEN of the same Defaults dict
+    if p.light_algorithm == capi.LIGHT_ALGORITHMS["EXTERNAL"] and getattr(api, "has_lights_ext", False) and defaults:
+        d = json.loads(defaults) if isinstance(defaults, (str, bytes)) else defaults
+        if "SRL_INPUT_DIMENSIONS" in d or "SRL_MIN_GREEN" in d:
+            api.lights_config(int(d.get("SRL_INPUT_DIMENSIONS", 13)), int(d.get("SRL_MIN_GREEN", 5)))
     kinds = np.asarray(tables["schedule_kinds0"]).astype(int)
     # run-length encode consecutive kinds into schedule_add calls (insertion order is preserved)
     i = 0

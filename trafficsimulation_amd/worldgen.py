@@ -923,6 +923,22 @@ class WorldBuilder:
             return []
         return sorted(cand, key=lambda rc: min(abs(rc[0] - ex) + abs(rc[1] - ey) for ex, ey in entrances))
 
+    def approach_road_types(self) -> np.ndarray:
+        """(G, 4) int32 per light group: [blocks, R1, R2, R3] over every light's incoming + outgoing road blocks - the four
+        ns / ew, in / out coordinate lists together - by CellAgent.road_type: what IntersectionLightGroup.penalty_score is a
+        mean of (intersection_light_group.py:156-165).  Not derivable from road_type_map, which shows an R2 cell of the ring
+        road as 1 (city_model.py:2170-2172)."""
+        out = np.zeros((len(self.groups), 4), np.int32)
+        col = {R1: 1, R2: 2, R3: 3}
+        for i, g in enumerate(self.groups):
+            for nm in ("ns_in", "ns_out", "ew_in", "ew_out"):
+                for (x, y) in getattr(g, nm):
+                    out[i, 0] += 1
+                    rt = self.rtype[y * self.W + x]
+                    if rt in col:
+                        out[i, col[rt]] += 1
+        return out
+
     # ------------------------------------------------------------------ output tables
     def tables(self) -> dict:
         """Same keys and layouts as tests/golden/make_golden.py::world_tables."""
@@ -1019,16 +1035,21 @@ class WorldBuilder:
         return out
 
 
-def generate_world(width=200, height=200, seed=None, **options) -> dict:
+def generate_world(width=200, height=200, seed=None, approach_road_types=False, **options) -> dict:
     """`CityModel(width, height, seed=seed, **options)` after `random.seed(seed)`, as world tables.
 
     `options` are the reference constructor's keyword arguments (city_model.py:27-53) plus the `Defaults` switches that
-    reach the tables: `block_entrance_road_level`, `rain_enabled`, `enable_traffic`."""
+    reach the tables: `block_entrance_road_level`, `rain_enabled`, `enable_traffic`.  `approach_road_types` adds the table
+    g_approach_road_types (WorldBuilder.approach_road_types), which the external light control's penalty_score needs."""
     import gc
     was_enabled = gc.isenabled()
     gc.disable()          # millions of small tracked objects and no garbage: the cyclic collector only costs (1.6x at 1024^2)
     try:
-        return WorldBuilder(width, height, seed=seed, **options).build().tables()
+        b = WorldBuilder(width, height, seed=seed, **options).build()
+        out = b.tables()
+        if approach_road_types:
+            out["g_approach_road_types"] = b.approach_road_types()
+        return out
     finally:
         if was_enabled:
             gc.enable()
