@@ -15,7 +15,23 @@ TRAFFIC = dict(P_int=10000, P_thr=2400, dt=6, start_offset=6 * 3600, service_foo
                max_load_food=50.0, max_load_waste=250.0, load_time=20, gradual=True, food_capacity_per_cell=2.0,
                waste_capacity_per_cell=1.5, food_consumption_ticks=50, waste_production_ticks=100)
 
-def run(size, seed, ticks, every=50, engine=None, traffic=None, defaults=None, out=print, observe=False, trip_log=None, **world_kwargs):
+def write_frame(path_stem, frame):
+    """An (h, w, 4) RGBA frame as PNG through PIL where that imports, else as binary PPM (P6, RGB); returns the file's path."""
+    try:
+        from PIL import Image
+    except ImportError:
+        path = path_stem + ".ppm"
+        with open(path, "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (frame.shape[1], frame.shape[0]))
+            f.write(frame[..., :3].tobytes())
+        return path
+    path = path_stem + ".png"
+    Image.fromarray(frame[..., :3], "RGB").save(path)
+    return path
+
+
+def run(size, seed, ticks, every=50, engine=None, traffic=None, defaults=None, out=print, observe=False, trip_log=None,
+        frames=None, frame_every=10, zoom=1, shrink=1, **world_kwargs):
     from trafficsimulation_amd.mesa_api import CityModel
     t0 = time.time()
     m = CityModel(size, size, seed=seed, defaults=defaults or {}, traffic=dict(TRAFFIC, **(traffic or {})), engine=engine,
@@ -25,8 +41,12 @@ def run(size, seed, ticks, every=50, engine=None, traffic=None, defaults=None, o
     if observe:
         m.observe()      # traffic observation planes (include/trafficsim_observe.h), from the first tick on
     t0 = time.time()
+    if frames:
+        os.makedirs(frames, exist_ok=True)
     for t in range(1, ticks + 1):
         m.step()
+        if frames and t % frame_every == 0:      # rendered on the device (include/trafficsim_render.h), one file per frame
+            write_frame(os.path.join(frames, f"frame_{t:06d}"), m.render(zoom=zoom, shrink=shrink))
         if t % every == 0 or t == ticks:
             s = m.dynamic_traffic_generator.cached_stats
             out(f"tick {t:6d}  live {len(m.active_vehicle_agents):6d}  internal {s['live_internal']:5d}  through {s['live_through']:5d}  "
@@ -45,9 +65,14 @@ if __name__ == "__main__":
     ap.add_argument("--heatmap", metavar="OUT.npy", default=None, help="write the run's flow (cells entered), pooled 8 x 8, to this file")
     ap.add_argument("--trips", metavar="OUT.npy", default=None, help="write one record per finished trip (capi.TRIP_DTYPE) to this file")
     ap.add_argument("--trip-capacity", type=int, default=1 << 20, help="records the trip log holds (later ones are dropped and counted)")
+    ap.add_argument("--frames", metavar="DIR", default=None, help="write a frame of the whole city into DIR every --frame-every ticks (PNG with PIL, else PPM)")
+    ap.add_argument("--frame-every", type=int, default=10)
+    ap.add_argument("--zoom", type=int, default=1, help="pixels per cell of the frames (1..64)")
+    ap.add_argument("--shrink", type=int, default=1, help="cells per pixel of the frames (1..64; not together with --zoom)")
     a = ap.parse_args()
     kw = dict(carve_subblock_roads=True) if a.carve else {}
-    m = run(a.size, a.seed, a.ticks, a.every, observe=bool(a.heatmap), trip_log=a.trip_capacity if a.trips else None, **kw)
+    m = run(a.size, a.seed, a.ticks, a.every, observe=bool(a.heatmap), trip_log=a.trip_capacity if a.trips else None,
+            frames=a.frames, frame_every=a.frame_every, zoom=a.zoom, shrink=a.shrink, **kw)
     if a.heatmap:
         import numpy as np
         from trafficsimulation_amd import _capi as capi

@@ -1,0 +1,122 @@
+"""The device renderer through the Mesa-style facade: CityModel.render() on the seed-built default city against the numpy
+statement of the pixel rule, CellAgent.get_portrayal()["Color"] against the pixel of the same cell, save / load / deepcopy /
+pickle, and examples/run_city.py --frames."""
+import copy
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import render_expect as rx
+from tests.test_gpu_render import BG, Scene
+from trafficsimulation_amd import _capi as capi
+from trafficsimulation_amd import render as rn
+from trafficsimulation_amd.mesa_api import CityModel
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+TICKS = 40
+
+
+@pytest.fixture(scope="module")
+def city():
+    """CityModel() as the reference ships it (200 x 200) with a busier day, stepped TICKS ticks with the entering order of
+    the vehicles tracked for the model."""
+    from run_city import TRAFFIC
+    m = CityModel(200, 200, seed=5, traffic=dict(TRAFFIC, P_int=200000, P_thr=60000, service_food=400, service_waste=400),
+                  defaults={"RAIN_SPAWN_CHANCE": 0.3, "RAIN_RADIUS_MIN": 10, "RAIN_RADIUS_MAX": 30})
+    m.observe()
+    plane, names = m.render_type_plane()
+    assert names == rn.RENDER_TYPE_NAMES and (plane >= 18).any() and plane.shape == (200, 200)
+    scene = Scene.wrap(m.engine, m.tables, plane, rn.cell_palette())
+    for _ in range(TICKS):
+        m.step()
+        scene._track()
+    yield m, scene
+    m.close()
+
+
+def model_frame(scene, view, heat="present"):
+    st = scene.state(heat)
+    return rx.render(st, {**view, "layers": capi.render_layer_mask(view.get("layers"))}), st
+
+
+def test_render_equals_the_model(city):
+    m, scene = city
+    assert len(m.active_vehicle_agents) > 50
+    got = m.render(background=BG[:3])
+    want, st = model_frame(scene, dict(x0=0, y0=0, cells_w=200, cells_h=200, flip_y=True, background=BG))
+    assert got.shape == (200, 200, 4) and np.array_equal(got, want)
+    assert (st["top"] >= 0).sum() > 50
+    got = m.render(x0=150, y0=161, w=70, h=50, zoom=3, flip_y=False, background=BG[:3])
+    want, _ = model_frame(scene, dict(x0=150, y0=161, cells_w=70, cells_h=50, zoom=3, background=BG))
+    assert np.array_equal(got, want)
+    got = m.render(shrink=3, heat="flow", background=BG[:3])
+    flow = sum(m.engine.observe_plane(p).astype(np.uint64) for p in capi.OBS_ENTER)
+    want, _ = model_frame(scene, dict(x0=0, y0=0, cells_w=200, cells_h=200, shrink=3, flip_y=True, background=BG, heat_max=int(flow.max()),
+                                      layers=capi.RL_SIGNALS | capi.RL_RAIN | capi.RL_VEHICLES | capi.RL_HEAT), heat="flow")
+    assert flow.max() > 1 and np.array_equal(got, want)
+    vs = m.active_vehicle_agents[:4]
+    got = m.render(routes=vs, flip_y=False)
+    scene.routes = [v._spawn_idx for v in vs]
+    st = scene.state()
+    st["route_rgba"] = (255, 0, 255, 160)            # (CApi.render_set_routes' default colour)
+    want = rx.render(st, dict(x0=0, y0=0, cells_w=200, cells_h=200, layers=capi.RL_SIGNALS | capi.RL_RAIN | capi.RL_VEHICLES | capi.RL_ROUTES))
+    assert st["route"].any() and np.array_equal(got, want)
+    scene.routes = []
+
+
+def test_portrayal_colour_is_the_pixel(city):
+    m, _ = city
+    frame = m.render(layers=("signals", "rain"), flip_y=False)
+    rain, stop = m.rain_map, m.stop_map
+    rng = np.random.default_rng(7)
+    cells = [(int(x), int(y)) for x, y in rng.integers(0, 200, size=(150, 2))]
+    cells += [c.position for c in m.traffic_lights[:20]] + [c.position for c in m.controlled_roads[:20]]
+    cells += [c.position for g in m.intersection_light_groups[:30] for c in g.intersection_cells[:1]]
+    ys, xs = np.nonzero(rain > 0)
+    cells += list(zip(xs[::97].tolist(), ys[::97].tolist()))
+    names = hexes = 0
+    for (x, y) in cells:
+        col = m.cell(x, y).get_portrayal()["Color"]
+        assert tuple(frame[y, x, :3]) == rn.to_rgb(col), f"cell {(x, y)} ({m.cell(x, y).cell_type}): portrayal {col}, pixel {frame[y, x]}"
+        names += not col.startswith("#")
+        hexes += col.startswith("#")
+    assert names and hexes, "the sample holds colour names (where the reference returns names) and hex strings (desaturate's output)"
+
+
+def test_save_load_copy_and_pickle_render_again(city, tmp_path):
+    m, _ = city
+    want = m.render()
+    path = str(tmp_path / "city.npz")
+    m.save(path)
+    for how, other in (("load", CityModel.load(path)), ("deepcopy", copy.deepcopy(m)), ("pickle", pickle.loads(pickle.dumps(m)))):
+        assert other.engine.render_info()["n_types"] == 0, f"{how}: a new engine starts without tables"
+        got = other.render()
+        assert other.engine.render_info()["n_types"] == len(rn.RENDER_TYPE_NAMES)
+        # the list order inside a cell is part of a checkpoint, so the frame is the same frame
+        assert np.array_equal(got, want), how
+        other.close()
+    assert np.array_equal(m.render(), want)
+
+
+def test_run_city_writes_frames(tmp_path):
+    out = tmp_path / "frames"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "run_city.py"), "--size", "96", "--ticks", "30", "--frames", str(out),
+                        "--frame-every", "10", "--zoom", "2"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    files = sorted(os.listdir(out))
+    assert len(files) == 3 and files[0].startswith("frame_000010."), files
+    path = os.path.join(out, files[0])
+    if path.endswith(".png"):
+        from PIL import Image
+        with Image.open(path) as im:
+            assert im.size == (192, 192) and im.mode == "RGB"
+    else:
+        with open(path, "rb") as f:
+            assert f.read(15) == b"P6\n192 192\n255\n"

@@ -1,0 +1,140 @@
+"""The render entries (include/trafficsim_render.h) without a GPU: the header declares exactly them, its constants and
+structs match the Python side, the HIP library exports them, ts_render_size does its arithmetic (it takes no handle), and the
+oracle-backed CApi - which shares the class and has no renderer - refuses them cleanly."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from trafficsimulation_amd import _capi as capi
+from trafficsimulation_amd import render as rn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ["ts_render", "ts_render_device", "ts_render_info", "ts_render_set_cells", "ts_render_set_heat_lut",
+           "ts_render_set_routes", "ts_render_set_vehicle_palette", "ts_render_size"]
+
+
+def header(name):
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+
+
+def test_header_declares_exactly_the_render_entries():
+    assert sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", header("trafficsim_render.h")))) == ENTRIES
+
+
+def test_header_constants_match_the_python_names():
+    src = header("trafficsim_render.h")
+    for k, name in enumerate(capi.RENDER_LAYERS):
+        assert re.search(rf"\bTS_RL_{name.upper()}\s*=\s*{1 << k}\b", src), name
+        assert getattr(capi, f"RL_{name.upper()}") == 1 << k
+    assert re.search(rf"\bTS_RL_ALL\s*=\s*{capi.RL_ALL}\b", src) and capi.RL_ALL == (1 << len(capi.RENDER_LAYERS)) - 1
+    for name in ("MAX_TYPES", "MAX_ROUTES", "MAX_SCALE", "MAX_SIDE", "DEFAULT_RADIUS"):
+        assert re.search(rf"\bTS_RENDER_{name}\s*=\s*{getattr(capi, 'RENDER_' + name)}\b", src), name
+    assert len(rn.VEHICLE_KINDS) == 3 and len(rn.VEHICLE_STATUS) == 4
+
+
+@pytest.mark.parametrize("struct,cls", [("TsRenderView", capi.TsRenderView), ("TsRenderInfo", capi.TsRenderInfo)])
+def test_structs_match_field_for_field(struct, cls):
+    body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header("trafficsim_render.h"), flags=re.S).group(1)
+    ctype = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+             "uint8_t": ctypes.c_uint8}
+    want = []
+    for typ, names in re.findall(r"\b(u?int(?:8|32|64)_t)\s+([^;]+);", body):
+        for n in names.split(","):
+            m = re.fullmatch(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*", n)
+            want.append((m.group(1), ctype[typ] * int(m.group(2)) if m.group(2) else ctype[typ]))
+    got = [(n, t) for n, t in cls._fields_]
+    assert [n for n, _ in got] == [n for n, _ in want]
+    for (n, t), (_, w) in zip(got, want):
+        assert ctypes.sizeof(t) == ctypes.sizeof(w) and (t is w or hasattr(t, "_length_")), n
+    assert ctypes.sizeof(cls) == {"TsRenderView": 48, "TsRenderInfo": 40}[struct]
+
+
+def test_render_entries_stay_out_of_the_main_header():
+    assert "render" not in header("trafficsim.h") and "TS_RL_" not in header("trafficsim.h")
+
+
+def hip_lib():
+    import __graft_entry__ as ge
+    ge.build_hip()
+    from trafficsimulation_amd._lib import LIB_PATH
+    return ctypes.CDLL(LIB_PATH)
+
+
+def test_hip_library_exports_the_render_entries():
+    lib = hip_lib()
+    for s in ENTRIES:
+        assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
+
+
+def size_of(lib, **kw):
+    fn = lib.ts_render_size
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.POINTER(capi.TsRenderView), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    w, h = ctypes.c_int32(-7), ctypes.c_int32(-7)
+    v = rn.make_view(**kw)
+    rc = fn(ctypes.byref(v), ctypes.byref(w), ctypes.byref(h))
+    return rc, w.value, h.value
+
+
+def test_render_size_arithmetic():
+    """ts_render_size takes no handle and touches no device: zoom multiplies, shrink divides rounding up, the limit is 8192
+    pixels a side, and a refused view writes nothing."""
+    lib = hip_lib()
+    assert size_of(lib, cells_w=100, cells_h=75) == (0, 100, 75)
+    assert size_of(lib, cells_w=100, cells_h=75, zoom=3) == (0, 300, 225)
+    assert size_of(lib, cells_w=11, cells_h=9, zoom=64) == (0, 704, 576)
+    for s in (2, 3, 7, 64):
+        assert size_of(lib, cells_w=100, cells_h=75, shrink=s) == (0, -(-100 // s), -(-75 // s))
+    assert size_of(lib, x0=-1000, y0=5000, cells_w=1, cells_h=1) == (0, 1, 1)
+    assert size_of(lib, cells_w=8192, cells_h=8192) == (0, 8192, 8192)
+    assert size_of(lib, cells_w=128, cells_h=128, zoom=64) == (0, 8192, 8192)
+    assert size_of(lib, cells_w=8192 * 64, cells_h=8192 * 64 - 63, shrink=64) == (0, 8192, 8192)
+    for kw in (dict(cells_w=8193, cells_h=1), dict(cells_w=1, cells_h=8193), dict(cells_w=129, cells_h=1, zoom=64),
+               dict(cells_w=8192 * 64 + 1, cells_h=1, shrink=64), dict(cells_w=0x7FFFFFFF, cells_h=0x7FFFFFFF, zoom=64)):
+        assert size_of(lib, **kw) == (capi.TS_E_CAPACITY, -7, -7), kw
+    for kw in (dict(cells_w=0, cells_h=1), dict(cells_w=1, cells_h=-3), dict(cells_w=1, cells_h=1, zoom=0), dict(cells_w=1, cells_h=1, zoom=65),
+               dict(cells_w=1, cells_h=1, shrink=0), dict(cells_w=1, cells_h=1, shrink=65), dict(cells_w=4, cells_h=4, zoom=2, shrink=2),
+               dict(cells_w=1, cells_h=1, layers=32), dict(cells_w=1, cells_h=1, vehicle_radius_256=-1),
+               dict(cells_w=1, cells_h=1, layers=capi.RL_HEAT, heat_plane=8), dict(cells_w=1, cells_h=1, layers=capi.RL_HEAT, heat_max=0)):
+        assert size_of(lib, **kw) == (capi.TS_E_INVALID, -7, -7), kw
+    fn = lib.ts_render_size
+    w = ctypes.c_int32()
+    v = rn.make_view()
+    assert fn(None, ctypes.byref(w), ctypes.byref(w)) == capi.TS_E_INVALID and fn(ctypes.byref(v), None, ctypes.byref(w)) == capi.TS_E_INVALID
+
+
+def test_make_view_defaults_and_layer_names():
+    v = rn.make_view(cells_w=3, cells_h=2, layers=["vehicles", "heat"], heat_plane="flow", background=(1, 2, 3))
+    assert (v.zoom, v.shrink, v.flip_y, v.vehicle_radius_256) == (1, 1, 0, 169)
+    assert v.layers == capi.RL_VEHICLES | capi.RL_HEAT and v.heat_plane == len(capi.OBS_PLANES) and list(v.background) == [1, 2, 3, 255]
+    assert rn.make_view().layers == capi.RL_SIGNALS | capi.RL_RAIN | capi.RL_VEHICLES
+    with pytest.raises(ValueError):
+        capi.render_layer_mask(["clouds"])
+
+
+def oracle_api():
+    from oracle import pyoracle
+    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
+
+
+def test_oracle_capi_constructs_and_has_no_renderer():
+    api = oracle_api()
+    assert api.prefix == "tso_" and api.has_render is False
+
+
+@pytest.mark.parametrize("call", ["set_cells", "set_vehicle_palette", "set_heat_lut", "set_routes", "size", "render", "device", "info"])
+def test_oracle_render_is_unsupported(call):
+    api = oracle_api()
+    api.W = api.H = 4
+    view = rn.make_view(cells_w=4, cells_h=4)
+    calls = {"set_cells": lambda: api.render_set_cells(np.zeros((4, 4), dtype=np.uint8), rn.cell_palette()),
+             "set_vehicle_palette": lambda: api.render_set_vehicle_palette(rn.vehicle_palette()),
+             "set_heat_lut": lambda: api.render_set_heat_lut(rn.heat_lut()),
+             "set_routes": lambda: api.render_set_routes([0]), "size": lambda: api.render_size(view),
+             "render": lambda: api.render(view), "device": lambda: api.render_device(view), "info": api.render_info}
+    with pytest.raises(capi.EngineError) as ex:
+        calls[call]()
+    assert ex.value.code == capi.TS_E_UNSUPPORTED

@@ -94,6 +94,38 @@ OBS_ENTER = OBS_PLANES[3:]
 OG_FIELDS = ["ns_waiting", "ns_present", "ew_waiting", "ew_present", "enter_n", "enter_e", "enter_s", "enter_w"]
 
 
+# include/trafficsim_render.h: the TS_RL_* layer bits (bit k = RENDER_LAYERS[k]), limits, TsRenderView, TsRenderInfo
+RENDER_LAYERS = ["signals", "rain", "vehicles", "heat", "routes"]
+RL_SIGNALS, RL_RAIN, RL_VEHICLES, RL_HEAT, RL_ROUTES = (1 << k for k in range(5))
+RL_ALL = 31
+RENDER_MAX_TYPES, RENDER_MAX_ROUTES, RENDER_MAX_SCALE, RENDER_MAX_SIDE, RENDER_DEFAULT_RADIUS = 64, 4096, 64, 8192, 169
+
+
+class TsRenderView(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("cells_w", C.c_int32), ("cells_h", C.c_int32), ("zoom", C.c_int32),
+                ("shrink", C.c_int32), ("layers", C.c_uint32), ("flip_y", C.c_int32), ("heat_plane", C.c_int32),
+                ("heat_max", C.c_uint32), ("vehicle_radius_256", C.c_int32), ("background", C.c_uint8 * 4)]
+
+
+class TsRenderInfo(C.Structure):
+    _fields_ = [("n_types", C.c_int32), ("has_vehicle_palette", C.c_int32), ("has_heat_lut", C.c_int32), ("n_routes", C.c_int32),
+                ("last_w", C.c_int32), ("last_h", C.c_int32), ("frames", C.c_int64), ("device_bytes", C.c_uint64)]
+
+
+def render_layer_mask(layers) -> int:
+    """A TS_RL_* mask from None (signals, rain and vehicles), a ready mask, one name or names of RENDER_LAYERS."""
+    if layers is None:
+        return RL_SIGNALS | RL_RAIN | RL_VEHICLES
+    if isinstance(layers, (int, np.integer)):
+        return int(layers)
+    mask = 0
+    for name in ([layers] if isinstance(layers, str) else layers):
+        if name not in RENDER_LAYERS:
+            raise ValueError(f"unknown render layer {name!r} (one of {', '.join(RENDER_LAYERS)})")
+        mask |= 1 << RENDER_LAYERS.index(name)
+    return mask
+
+
 class TsObserveInfo(C.Structure):
     _fields_ = [("plane_mask", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("ticks", C.c_int64),
                 ("device_bytes", C.c_uint64)]
@@ -1139,6 +1171,110 @@ class CApi:
             raise RuntimeError("lights_device: torch cannot reach the engine's device - import torch before the engine "
                                "library is loaded, or use lights_observe") from ex
         return out
+
+    # ---- device renderer (include/trafficsim_render.h) ------------------------------------------------
+    def _rn_fn(self, name: str):
+        """The render entries, bound on first use: the CPU oracle shares this class and has none of them."""
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no renderer")
+        fn.restype = C.c_int
+        fn.argtypes = {"render_set_cells": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
+                       "render_set_vehicle_palette": [C.c_void_p, C.c_void_p],
+                       "render_set_heat_lut": [C.c_void_p, C.c_void_p],
+                       "render_set_routes": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+                       "render_size": [C.POINTER(TsRenderView), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+                       "render": [C.c_void_p, C.POINTER(TsRenderView), C.c_void_p],
+                       "render_device": [C.c_void_p, C.POINTER(TsRenderView), C.POINTER(C.c_void_p)],
+                       "render_info": [C.c_void_p, C.POINTER(TsRenderInfo)]}[name]
+        return fn
+
+    @property
+    def has_render(self) -> bool:
+        return self.prefix == "ts_" and hasattr(self.lib, "ts_render")
+
+    @staticmethod
+    def _heat_plane(name) -> int:
+        """A TS_OBS_* index from a plane name or index; "flow" is TS_OBS_NPLANES, the sum of the four ENTER planes."""
+        return len(OBS_PLANES) if name == "flow" else CApi._obs_plane(name)
+
+    @staticmethod
+    def _u8(a, shape, what) -> np.ndarray:
+        a = np.asarray(a)
+        if a.shape != tuple(shape) or a.dtype.kind not in "iub" or (a.size and (a.min() < 0 or a.max() > 255)):
+            raise ValueError(f"{what} must be integers 0..255 of shape {tuple(shape)}, got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a, dtype=np.uint8)
+
+    def render_set_cells(self, type_plane, cell_palette):
+        """The static type code per cell ((H, W), every code < n_types) and the cell palette
+        ((n_types, 2 pend, 2 stop, 2 rain, 4) RGBA; render.cell_palette builds the reference's)."""
+        fn = self._rn_fn("render_set_cells")
+        pal = np.asarray(cell_palette)
+        n_types = pal.shape[0] if pal.ndim == 5 else -1
+        pal = self._u8(pal, (max(n_types, 0), 2, 2, 2, 4), "cell_palette")
+        tp = self._u8(type_plane, (self.H, self.W), "type_plane")
+        self._chk(fn(self.h, tp.ctypes.data, n_types, pal.ctypes.data))
+
+    def render_set_vehicle_palette(self, pal):
+        """(3 kind, 4 status, 2 flash, 4) RGBA; render.vehicle_palette builds the reference's."""
+        fn = self._rn_fn("render_set_vehicle_palette")
+        self._chk(fn(self.h, self._u8(pal, (3, 4, 2, 4), "vehicle palette").ctypes.data))
+
+    def render_set_heat_lut(self, lut):
+        """(256, 4) RGBA, A = blend weight."""
+        fn = self._rn_fn("render_set_heat_lut")
+        self._chk(fn(self.h, self._u8(lut, (256, 4), "heat LUT").ctypes.data))
+
+    def render_set_routes(self, spawn_idx, rgba=(255, 0, 255, 160)):
+        """The vehicles (spawn indices, at most RENDER_MAX_ROUTES; an empty list clears) whose remaining paths the routes
+        layer draws, and the colour they are blended in with (A = blend weight)."""
+        fn = self._rn_fn("render_set_routes")
+        ids = _i32(np.asarray(spawn_idx, dtype=np.int64).reshape(-1))
+        col = self._u8(rgba, (4,), "route colour")
+        self._chk(fn(self.h, len(ids), ids.ctypes.data if len(ids) else None, col.ctypes.data))
+
+    def render_size(self, view: TsRenderView):
+        """(width, height) in pixels of the frame a view gives."""
+        fn = self._rn_fn("render_size")
+        w, h = C.c_int32(), C.c_int32()
+        self._chk(fn(C.byref(view), C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def render(self, view: TsRenderView) -> np.ndarray:
+        """One frame as an (h, w, 4) uint8 array (RGBA, alpha 255)."""
+        fn = self._rn_fn("render")
+        w, h = self.render_size(view)
+        out = np.zeros((h, w, 4), dtype=np.uint8)
+        self._chk(fn(self.h, C.byref(view), out.ctypes.data))
+        return out
+
+    def render_device(self, view: TsRenderView, device=None):
+        """One frame as an (h, w, 4) uint8 torch tensor over the engine's own frame buffer (no copy; valid until the next
+        render or close).  torch must have been imported before the engine library was loaded, as for observe_device."""
+        fn = self._rn_fn("render_device")
+        try:
+            import torch
+        except ImportError as ex:
+            raise RuntimeError("render_device needs torch (use render for a host array)") from ex
+        w, h = self.render_size(view)
+        ptr = C.c_void_p()
+        self._chk(fn(self.h, C.byref(view), C.byref(ptr)))
+        from .dist import ShardedReplans
+        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        try:
+            t = ShardedReplans._wrap_device(ptr.value, w * h * 4, device)
+        except RuntimeError as ex:
+            raise RuntimeError("render_device: torch cannot reach the engine's device - import torch before the engine "
+                               "library is loaded, or render to the host with render") from ex
+        return t.view(torch.uint8).view(h, w, 4)
+
+    def render_info(self) -> dict:
+        """{"n_types", "has_vehicle_palette", "has_heat_lut", "n_routes", "last_w", "last_h", "frames", "device_bytes"}"""
+        info = TsRenderInfo()
+        self._chk(self._rn_fn("render_info")(self.h, C.byref(info)))
+        return {"n_types": int(info.n_types), "has_vehicle_palette": bool(info.has_vehicle_palette),
+                "has_heat_lut": bool(info.has_heat_lut), "n_routes": int(info.n_routes), "last_w": int(info.last_w),
+                "last_h": int(info.last_h), "frames": int(info.frames), "device_bytes": int(info.device_bytes)}
 
     BATCH_INFO = ("slots", "side_slots", "arena_shared", "arena_quad", "last_waves", "last_usable", "last_arena_quad",
                   "last_passes", "device")

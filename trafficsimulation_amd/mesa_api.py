@@ -184,11 +184,14 @@ class CellAgent:
         x, y = self.position
         ct = self.cell_type
         is_stop = self.model.stop_map[y, x] == 1
-        color = Defaults.ZONE_COLORS.get(ct, "white")
-        if ct == "TrafficLight" and is_stop:
-            color = Defaults.ZONE_COLORS["TrafficLightStop"]
-        if ct == "ControlledRoad" and is_stop:
-            color = Defaults.ZONE_COLORS["ControlledRoadStop"]
+        # cell.py:274-299 through the table the device renderer uses (render.py): a name where the reference returns the
+        # name, '#rrggbb' where it returns desaturate's output - one cell and one pixel cannot disagree
+        from . import render as _render
+        grp = self.intersection_group
+        pend = ct == "Intersection" and grp is not None and grp.pending_phase is not None
+        base = self.model._cell_base_type_map
+        rt = f"ControlledRoad:{_CELL_TYPE_NAMES[int(base[y, x])]}" if ct == "ControlledRoad" and base is not None and self.model._cell_type_map is not None else ct
+        color = _render.cell_color(rt, pend, bool(is_stop), bool(self.model.rain_map[y, x] > 0), self.model._render_defaults())
         p = {"Shape": "rect", "w": 1.0, "h": 1.0, "Filled": True, "Layer": 0, "Color": color, "Position": self.position}
         if ct == "ControlledRoad":
             p["Control State"] = "Stop" if is_stop else "Go"
@@ -670,6 +673,7 @@ class CityModel:
             d = defaults or {}
             if capi.LIGHT_ALGORITHMS.get(d.get("TRAFFIC_LIGHT_AGENT_ALGORITHM")) == capi.LIGHT_ALGORITHMS["EXTERNAL"]:
                 world_kwargs = dict(world_kwargs, approach_road_types=True)   # (penalty_score of the state vector)
+            world_kwargs = dict(world_kwargs, cell_base_types=True)           # (the renderer's palette: render.type_plane)
             tables = worldgen.generate_world(width, height, seed=global_seed if global_seed is not None else self._seed,
                                              rain_enabled=bool(d.get("RAIN_ENABLED", True)), enable_traffic=traffic is not None,
                                              block_entrance_road_level=int(d.get("BLOCK_ENTRANCE_ROAD_LEVEL", 0)), **world_kwargs)
@@ -705,6 +709,7 @@ class CityModel:
         self.intersection_map = np.asarray(tables["intersection_map"], dtype=np.int8)
         self._cell_type_map = np.asarray(tables["cell_type_map"]) if "cell_type_map" in tables else None
         self._block_id_map = np.asarray(tables["block_id_map"]) if "block_id_map" in tables else None
+        self._cell_base_type_map = np.asarray(tables["cell_base_type_map"]) if "cell_base_type_map" in tables else None
         self._stop_host = np.zeros((self.height, self.width), dtype=np.int8)
         self._stop_dirty = False
         self.step_count = 0
@@ -713,6 +718,7 @@ class CityModel:
         self._vehicle_by_uid: Dict[int, VehicleAgent] = {}
         self._cells: Dict[tuple, CellAgent] = {}
         self._snap = None
+        self._render_ready = False      # the renderer's tables go to the engine on the first render() of every model
         self.user_selected_traffic_light = self.user_selected_intersection = self.user_selected_opposite = None
         # lights / groups
         lxy = np.asarray(tables["light_xy"]).reshape(-1, 2)
@@ -1009,6 +1015,59 @@ class CityModel:
         return out
 
     # ---- getters used by the UI (city_model.py:1965-2149) ------------------------------------------
+    # ---- device renderer (include/trafficsim_render.h) ---------------------------------------------------
+    def _render_defaults(self):
+        """`Defaults` with the colour settings CityModel(defaults={...}) overrode (ZONE_COLORS, VEHICLE_*_COLOR, ...)."""
+        over = {k: v for k, v in self._defaults.items() if k == "ZONE_COLORS" or k.endswith("_COLOR") or k == "CHANGE_ASSIGNED_CELL_COLOR_ON_STOP"}
+        if not over:
+            return Defaults
+        if "ZONE_COLORS" in over:
+            over["ZONE_COLORS"] = dict(Defaults.ZONE_COLORS, **over["ZONE_COLORS"])
+        return type("Defaults", (Defaults,), over)
+
+    def render_type_plane(self):
+        """(type codes (H, W) uint8, type names): the `cell_type_map` table where the world has one, else the plane
+        CellAgent.cell_type's fallback derives (light, intersection, controlled road, road, nothing), vectorised."""
+        from . import render as _render
+        if self._cell_type_map is not None:
+            return _render.type_plane(self._cell_type_map, self._cell_base_type_map), _render.RENDER_TYPE_NAMES
+        return (_render.fallback_type_plane(self.is_road_map, self.intersection_map, sorted(self._controlled_cells),
+                                            sorted(self._light_index)), _render.fallback_type_names())
+
+    def render(self, x0=0, y0=0, w=None, h=None, zoom=1, shrink=1, layers=("signals", "rain", "vehicles"), heat=None,
+               heat_max=None, routes=None, flip_y=True, device=False, background=(0, 0, 0), vehicle_radius_256=None):
+        """One RGBA8 frame of the cells [x0, x0 + w) x [y0, y0 + h) (default: the whole map) rendered on the device: an
+        (h', w', 4) uint8 array, or with device=True a torch tensor over the engine's frame buffer (valid until the next
+        render).  `layers`: names of capi.RENDER_LAYERS or a TS_RL_* mask; `heat`: an observation plane name or "flow" (adds
+        the heat layer; the plane must be observed, see observe()), scaled to `heat_max` (default: the plane's maximum,
+        at least 1); `routes`: vehicles or spawn indices whose remaining paths to draw (adds the routes layer).  flip_y=True
+        puts the largest y in row 0, the way a CanvasGrid shows the city.  The colour tables (render.py) go to the engine
+        on the first call."""
+        from . import render as _render
+        eng = self.engine
+        self._flush_host_writes()
+        if not self._render_ready:
+            d = self._render_defaults()
+            plane, names = self.render_type_plane()
+            eng.render_set_cells(plane, _render.cell_palette(d, names))
+            eng.render_set_vehicle_palette(_render.vehicle_palette(d))
+            eng.render_set_heat_lut(_render.heat_lut())
+            self._render_ready = True
+        mask = capi.render_layer_mask(layers)
+        if heat is not None:
+            mask |= capi.RL_HEAT
+            if heat_max is None:
+                planes = capi.OBS_ENTER if heat == "flow" else [heat]
+                heat_max = max(1, int(sum(eng.observe_plane(p).astype(np.uint64) for p in planes).max()))
+        if routes is not None:
+            mask |= capi.RL_ROUTES
+            eng.render_set_routes([int(getattr(v, "_spawn_idx", v)) for v in routes])
+        view = _render.make_view(x0=x0, y0=y0, cells_w=self.width - x0 if w is None else w, cells_h=self.height - y0 if h is None else h,
+                                 zoom=zoom, shrink=shrink, layers=mask, flip_y=flip_y, heat_plane=heat if heat is not None else 0,
+                                 heat_max=heat_max if heat_max is not None else 1, background=background,
+                                 vehicle_radius_256=capi.RENDER_DEFAULT_RADIUS if vehicle_radius_256 is None else vehicle_radius_256)
+        return eng.render_device(view) if device else eng.render(view)
+
     @property
     def active_vehicle_agents(self):
         rows = self._snapshot()["rows"]

@@ -923,6 +923,16 @@ class WorldBuilder:
             return []
         return sorted(cand, key=lambda rc: min(abs(rc[0] - ex) + abs(rc[1] - ey) for ex, ey in entrances))
 
+    def cell_base_types(self) -> np.ndarray:
+        """(H, W) int8: the cell type whose ZONE_COLORS entry is the cell's base_color.  That is the cell's own type except on
+        a ControlledRoad, which keeps the colour of the road it was carved from (city_model.py:1458): there it is the original
+        type, CellAgent.road_type.  What the portrayal layer desaturates for a controlled road on "go"."""
+        base = np.asarray(self.ct, dtype=np.int8).reshape(self.H, self.W).copy()
+        for i, t in enumerate(self.ct):
+            if t == CONTROLLED and self.rtype[i] is not None:
+                base[i // self.W, i % self.W] = self.rtype[i]
+        return base
+
     def approach_road_types(self) -> np.ndarray:
         """(G, 4) int32 per light group: [blocks, R1, R2, R3] over every light's incoming + outgoing road blocks - the four
         ns / ew, in / out coordinate lists together - by CellAgent.road_type: what IntersectionLightGroup.penalty_score is a
@@ -1035,12 +1045,13 @@ class WorldBuilder:
         return out
 
 
-def generate_world(width=200, height=200, seed=None, approach_road_types=False, **options) -> dict:
+def generate_world(width=200, height=200, seed=None, approach_road_types=False, cell_base_types=False, **options) -> dict:
     """`CityModel(width, height, seed=seed, **options)` after `random.seed(seed)`, as world tables.
 
     `options` are the reference constructor's keyword arguments (city_model.py:27-53) plus the `Defaults` switches that
     reach the tables: `block_entrance_road_level`, `rain_enabled`, `enable_traffic`.  `approach_road_types` adds the table
-    g_approach_road_types (WorldBuilder.approach_road_types), which the external light control's penalty_score needs."""
+    g_approach_road_types (WorldBuilder.approach_road_types), which the external light control's penalty_score needs;
+    `cell_base_types` adds cell_base_type_map (WorldBuilder.cell_base_types), which the renderer's palette needs."""
     import gc
     was_enabled = gc.isenabled()
     gc.disable()          # millions of small tracked objects and no garbage: the cyclic collector only costs (1.6x at 1024^2)
@@ -1049,6 +1060,8 @@ def generate_world(width=200, height=200, seed=None, approach_road_types=False, 
         out = b.tables()
         if approach_road_types:
             out["g_approach_road_types"] = b.approach_road_types()
+        if cell_base_types:
+            out["cell_base_type_map"] = b.cell_base_types()
         return out
     finally:
         if was_enabled:
