@@ -61,7 +61,9 @@
  * Calls
  *   - only between ts_step calls, from the handle's caller thread (trafficsim.h conventions).
  *   - TS_E_UNSUPPORTED  the handle's algorithm is not TS_LIGHTS_EXTERNAL (every entry).
- *   - TS_E_STATE        ts_set_lights has not run; ts_lights_ext_config / _set_static after the first control call.
+ *   - TS_E_STATE        ts_set_lights has not run; ts_lights_ext_config / _set_static after the first control call;
+ *                       ts_lights_ext_config / _observe / _act once another protocol is configured (trafficsim_lights_proto.h,
+ *                       which brings the reference's A2C and GAT-DQN rewards onto the device).
  *   - TS_E_INVALID      a null pointer, a dimension outside {7, 11, 13, 17, 19}, min_green < 0, an action outside {0, 1},
  *                       a requested phase outside {-1, 0, 1}.  Nothing is applied then.
  *
@@ -108,7 +110,7 @@ typedef struct TsLightsExtDevice {
 int ts_lights_ext_config(ts_handle h, int32_t state_dim, int32_t min_green);
 
 /* intersection_size / penalty_score of every group ([G] doubles each; NULL = leave as it is).  Only before the first
- * control call.  Not part of a checkpoint: like the light tables, a load target is set up the same way first. */
+ * control call (of any protocol).  Not part of a checkpoint: like the light tables, a load target is set up the same way first. */
 int ts_lights_ext_set_static(ts_handle h, const double* intersection_size, const double* penalty_score);
 
 /* Phase A.  out: [G][state_dim] floats or NULL.  A second call before the next ts_lights_ext_act or ts_step returns the

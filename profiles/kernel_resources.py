@@ -13,6 +13,8 @@ WANT = ["k_replan", "k_replan_quad", "quad_policy", "replan_turn", "k_astar_sing
         "k_decide_despawn", "k_remove_one", "k_spawn", "k_tl_mark", "k_tl_count", "k_tl_emit", "k_tl_finish", "k_triplog_od",
         # the external light control (lights_ext.h; k_le_sums: the last instance of the template the compiler reports)
         "k_le_sums", "k_le_static", "k_le_state", "k_le_commit", "k_le_check", "k_le_act", "k_le_request",
+        # the A2C / GAT-DQN light protocols (lights_proto.h)
+        "k_lp_a2c_state", "k_lp_gat_state", "k_lp_act", "k_lp_gat_next", "k_lp_greedy",
         # the renderer (render.h): the pre-pass and the two frame kernels
         "k_render_pend", "k_render_vehicles", "k_render_routes", "k_render_frame", "k_render_shrink"]
 r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-pthread", "--offload-arch=gfx950", "--cuda-device-only", "-c",

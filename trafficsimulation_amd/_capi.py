@@ -155,6 +155,26 @@ class TsLightsExtDevice(C.Structure):
                 ("n_groups", C.c_int32), ("state_dim", C.c_int32)]
 
 
+class TsLightsProtoConfig(C.Structure):
+    _fields_ = [("protocol", C.c_int32), ("min_green", C.c_int32), ("eps_min", C.c_double), ("eps_decay", C.c_double)]
+
+
+class TsLightsProtoInfo(C.Structure):
+    _fields_ = [("protocol", C.c_int32), ("min_green", C.c_int32), ("n_groups", C.c_int32), ("state_floats", C.c_int32),
+                ("eps_min", C.c_double), ("eps_decay", C.c_double), ("calls", C.c_int64), ("device_bytes", C.c_uint64)]
+
+
+class TsLightsProtoDevice(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("mask", C.c_void_p), ("next_state", C.c_void_p), ("reward", C.c_void_p),
+                ("actions", C.c_void_p), ("epsilon", C.c_void_p), ("n_groups", C.c_int32), ("protocol", C.c_int32)]
+
+
+# include/trafficsim_lights_proto.h: the protocols of the external light control beyond the simple one, by the reference's
+# algorithm names.  Not light algorithms of the engine: world.build_engine translates them to EXTERNAL plus a protocol.
+LIGHT_PROTOCOLS = {"RL_A2C_BATCHED": 1, "GAT_DQN_BATCHED": 2}
+LP_A2C, LP_GAT = 1, 2
+
+
 class TsCounters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "stuck", "collisions", "malfunctions", "overtaking", "in_stuck_detour", "parked", "live_internal",
@@ -1170,6 +1190,124 @@ class CApi:
         except RuntimeError as ex:
             raise RuntimeError("lights_device: torch cannot reach the engine's device - import torch before the engine "
                                "library is loaded, or use lights_observe") from ex
+        return out
+
+    # ---- A2C / GAT-DQN light protocols (include/trafficsim_lights_proto.h) ------------------------------
+    def _lp_fn(self, name: str):
+        """The protocol entries, bound on first use: the CPU oracle shares this class and has none of them."""
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no light protocols")
+        fn.restype = C.c_int
+        fn.argtypes = {"lights_proto_config": [C.c_void_p, C.POINTER(TsLightsProtoConfig)],
+                       "lights_proto_observe": [C.c_void_p, C.c_void_p, C.c_void_p],
+                       "lights_proto_act": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+                       "lights_proto_act_q": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+                       "lights_proto_download": [C.c_void_p, C.c_void_p],
+                       "lights_proto_device": [C.c_void_p, C.POINTER(TsLightsProtoDevice)],
+                       "lights_proto_info": [C.c_void_p, C.POINTER(TsLightsProtoInfo)]}[name]
+        return fn
+
+    def lights_proto_config(self, protocol, min_green: int = 5, eps_min: float = 0.1, eps_decay: float = 1e-5):
+        """Choose the A2C (1, "RL_A2C_BATCHED") or GAT-DQN (2, "GAT_DQN_BATCHED") protocol; once, before the first control call."""
+        cfg = TsLightsProtoConfig(int(LIGHT_PROTOCOLS.get(protocol, protocol)), int(min_green), float(eps_min), float(eps_decay))
+        self._chk(self._lp_fn("lights_proto_config")(self.h, C.byref(cfg)))
+
+    def lights_proto_info(self) -> dict:
+        """{"protocol" (0: none), "min_green", "n_groups", "state_floats", "eps_min", "eps_decay", "calls", "device_bytes"}"""
+        info = TsLightsProtoInfo()
+        self._chk(self._lp_fn("lights_proto_info")(self.h, C.byref(info)))
+        return {n: (float if t is C.c_double else int)(getattr(info, n)) for n, t in TsLightsProtoInfo._fields_}
+
+    def lights_proto_observe(self, to_host: bool = True):
+        """A2C: the state (G, 13) float32.  GAT: (features (G, 5, 9), mask (G, 5)) float32.  No side effects.
+        to_host=False only runs it (nothing comes down; the results are in lights_proto_device()) and returns None."""
+        fn = self._lp_fn("lights_proto_observe")
+        if not to_host:
+            self._chk(fn(self.h, None, None))
+            return None
+        gat = self.lights_proto_info()["protocol"] == LP_GAT
+        G = max(self.n_groups, 1)
+        state = np.zeros((G, 5, 9) if gat else (G, 13), dtype=np.float32)
+        mask = np.zeros((G, 5), dtype=np.float32) if gat else None
+        self._chk(fn(self.h, state.ctypes.data, mask.ctypes.data if gat else None))
+        return (state[:self.n_groups], mask[:self.n_groups]) if gat else state[:self.n_groups]
+
+    def lights_proto_act(self, actions, want_next=None, to_host: bool = True):
+        """The action rule with caller-chosen actions (numpy, a sequence or an int8 torch tensor on the engine's device): draws
+        nothing, leaves epsilon alone.  Returns the rewards (G,) float64 under A2C, (rewards, next features) under GAT
+        (want_next=False: the rewards only).  to_host=False: nothing comes down (the results are in lights_proto_device())
+        and None is returned."""
+        fn = self._lp_fn("lights_proto_act")
+        ptr, on_dev, keep = self._le_bytes(actions, "actions")
+        if not to_host:
+            self._chk(fn(self.h, ptr, on_dev, None, None))
+            return None
+        if want_next is None:
+            want_next = self.lights_proto_info()["protocol"] == LP_GAT
+        G = max(self.n_groups, 1)
+        reward = np.zeros(G, dtype=np.float64)
+        nxt = np.zeros((G, 5, 9), dtype=np.float32) if want_next else None
+        self._chk(fn(self.h, ptr, on_dev, reward.ctypes.data, nxt.ctypes.data if nxt is not None else None))
+        del keep
+        return (reward[:self.n_groups], nxt[:self.n_groups]) if nxt is not None else reward[:self.n_groups]
+
+    def lights_proto_act_q(self, q, want_next: bool = True, to_host: bool = True):
+        """GAT: the epsilon-greedy step on q (G, 2) float32 - numpy or a torch tensor on the engine's device - drawing from
+        the engine's global stream.  Returns (actions int8, rewards float64, next features); want_next=False leaves the next
+        features on the device ((actions, rewards)); to_host=False brings nothing down (actions, rewards and next state are in
+        lights_proto_device()) and returns None."""
+        fn = self._lp_fn("lights_proto_act_q")
+        keep, on_dev = q, 0
+        if type(q).__module__.split(".")[0] == "torch" and q.is_cuda:
+            import torch
+            if q.dtype != torch.float32 or tuple(q.shape) != (self.n_groups, 2) or not q.is_contiguous():
+                raise ValueError(f"q: a torch tensor must be contiguous float32 of shape ({self.n_groups}, 2)")
+            if q.device.index != self.debug_batch_info()["device"]:
+                raise ValueError(f"q: the tensor is on {q.device}, not on the engine's device")
+            torch.cuda.current_stream(q.device).synchronize()
+            ptr, on_dev = q.data_ptr(), 1
+        else:
+            keep = np.ascontiguousarray(q.numpy() if hasattr(q, "numpy") else q, dtype=np.float32)
+            if keep.shape != (self.n_groups, 2):
+                raise ValueError(f"q: two values per group ({self.n_groups}, 2), got shape {keep.shape}")
+            ptr = keep.ctypes.data if keep.size else np.zeros(2, np.float32).ctypes.data
+        if not to_host:
+            self._chk(fn(self.h, ptr, on_dev, None, None, None))
+            return None
+        G = max(self.n_groups, 1)
+        acts, reward = np.zeros(G, dtype=np.int8), np.zeros(G, dtype=np.float64)
+        nxt = np.zeros((G, 5, 9), dtype=np.float32) if want_next else None
+        self._chk(fn(self.h, ptr, on_dev, acts.ctypes.data, reward.ctypes.data, nxt.ctypes.data if nxt is not None else None))
+        del keep
+        out = (acts[:self.n_groups], reward[:self.n_groups])
+        return out + (nxt[:self.n_groups],) if nxt is not None else out
+
+    def lights_proto_controller(self) -> np.ndarray:
+        """(G,) float64: epsilon of every group (zeros under A2C); _rl_phase / rl_timer are lights_controller()."""
+        out = np.zeros(max(self.n_groups, 1), dtype=np.float64)
+        self._chk(self._lp_fn("lights_proto_download")(self.h, out.ctypes.data))
+        return out[:self.n_groups]
+
+    def lights_proto_device(self, device=None) -> dict:
+        """{"state", "mask", "next_state", "reward", "actions", "epsilon"} as torch tensors over the engine's own device memory
+        (entries the protocol does not have are left out); torch must have been imported before the engine library was loaded."""
+        import torch
+        d = TsLightsProtoDevice()
+        self._chk(self._lp_fn("lights_proto_device")(self.h, C.byref(d)))
+        from .dist import ShardedReplans
+        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        G = int(d.n_groups)
+        gat = int(d.protocol) == LP_GAT
+        spec = {"state": (d.state, torch.float32, (G, 5, 9) if gat else (G, 13)), "reward": (d.reward, torch.float64, (G,)),
+                "actions": (d.actions, torch.int8, (G,))}
+        if gat:
+            spec.update(mask=(d.mask, torch.float32, (G, 5)), next_state=(d.next_state, torch.float32, (G, 5, 9)),
+                        epsilon=(d.epsilon, torch.float64, (G,)))
+        out = {}
+        for k, (ptr, dt, shape) in spec.items():
+            n = int(np.prod(shape)) * torch.empty(0, dtype=dt).element_size()
+            out[k] = (ShardedReplans._wrap_device(ptr, n, device).view(dt).view(*shape) if G else torch.zeros(shape, dtype=dt, device=device))
         return out
 
     # ---- device renderer (include/trafficsim_render.h) ------------------------------------------------

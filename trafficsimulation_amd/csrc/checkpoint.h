@@ -199,6 +199,16 @@ struct CkLightsExt {
 };
 constexpr uint32_t CK_LE_MAGIC = 0x3154584Cu;   // "LXT1"
 static_assert(sizeof(CkLightsExt) == 24, "checkpoint: external light control section");
+// The A2C / GAT-DQN protocols (lights_proto_api.h): a second trailing section behind it, written only once a protocol is
+// configured - every other blob is what it was.  The scalars, then epsilon [G] as doubles.
+struct CkLightsProto {
+  uint32_t magic;
+  int32_t protocol, min_green, pad_;
+  double eps_min, eps_decay;
+  int64_t calls;
+};
+constexpr uint32_t CK_LP_MAGIC = 0x3152504Cu;   // "LPR1"
+static_assert(sizeof(CkLightsProto) == 40, "checkpoint: light protocol section");
 
 // what is in flight between two ticks: the shuffle pipeline (idle once tick() returned), the take-ahead table on the copy
 // stream, the permutation copies, the quad searcher's stream and the main stream
@@ -331,6 +341,11 @@ int ck_write(E* e, CkSink& s, uint64_t path_words, bool stage) {
     s.dev(x.ctrl, (size_t)x.G * 8);
     s.dev(x.stored, (size_t)x.G * 8);
     s.dev(x.state, (size_t)x.G * x.dim * 4);
+    if (e->lp.protocol) {
+      const CkLightsProto Q{CK_LP_MAGIC, e->lp.protocol, e->lp.min_green, 0, e->lp.eps_min, e->lp.eps_decay, e->lp.calls};
+      s.val(Q);
+      s.put(e->lp.eps.data(), (size_t)x.G * 8);
+    }
   }
   return TS_OK;
 }
@@ -510,6 +525,24 @@ int ts_checkpoint_load(ts_handle e, const void* src, uint64_t n) {
     le_stored_p = r.take((size_t)d.G * 8);
     le_state_p = r.take((size_t)d.G * L.dim * 4);
   }
+  CkLightsProto Q{};
+  const uint8_t* lp_eps_p = nullptr;
+  if (le_on && r.ok && (e->lp.protocol || r.pos != n)) {
+    // (a blob without the section on a handle with a protocol, or the other way round, is another configuration too)
+    const bool have = r.pos != n;
+    if (have && (!r.val(Q) || Q.magic != CK_LP_MAGIC)) return bad("light protocol");
+    if (!have || Q.protocol != e->lp.protocol || Q.min_green != e->lp.min_green || Q.eps_min != e->lp.eps_min || Q.eps_decay != e->lp.eps_decay)
+      return fail(e, TS_E_INVALID, "checkpoint: the blob's light protocol is " + std::to_string(have ? Q.protocol : 0) + " (min-green " +
+                  std::to_string(have ? Q.min_green : 0) + "), the handle is configured with protocol " + std::to_string(e->lp.protocol) +
+                  " (min-green " + std::to_string(e->lp.min_green) + ") or other epsilon settings");
+    if (Q.calls < 0) return bad("light protocol");
+    lp_eps_p = r.take((size_t)d.G * 8);
+    for (int g = 0; lp_eps_p && g < d.G; g++) {
+      double v;
+      memcpy(&v, lp_eps_p + (size_t)g * 8, 8);
+      if (!(v >= 0.0 && v <= 1.0)) return bad("light protocol: epsilon outside [0, 1]");
+    }
+  }
   if (!r.ok) return bad("device sections truncated");
   if (r.pos != n) return bad("trailing bytes");
   {
@@ -632,6 +665,14 @@ int ts_checkpoint_load(ts_handle e, const void* src, uint64_t n) {
   e->tl_pending = 0;
   if (e->tl_on) TRY(tl_forget_origins(e));
   if (le_on) { e->le.calls = L.calls; e->le.observed = L.observed != 0; }
+  if (lp_eps_p) {
+    e->lp.calls = Q.calls;
+    if (d.G) memcpy(e->lp.eps.data(), lp_eps_p, (size_t)d.G * 8);
+    if (d.G && e->lp.d_eps) {
+      HIPOK(hipMemcpyAsync(e->lp.d_eps, e->lp.eps.data(), (size_t)d.G * 8, hipMemcpyHostToDevice, e->stream));
+      HIPOK(hipStreamSynchronize(e->stream));
+    }
+  }
   return TS_OK;
 }
 

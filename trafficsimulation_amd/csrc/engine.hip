@@ -45,6 +45,7 @@
 #include "triplog.h"
 #include "kernels.h"
 #include "lights_ext.h"
+#include "lights_proto.h"
 #include "render.h"
 #include "host_state.h"
 #include "host_shuffle.h"
@@ -2187,4 +2188,5 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
 #include "observe_api.h"
 #include "triplog_api.h"
 #include "lights_ext_api.h"
+#include "lights_proto_api.h"
 #include "render_api.h"

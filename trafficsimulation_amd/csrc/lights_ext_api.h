@@ -16,6 +16,13 @@ int le_enter(E* e) {
   return TS_OK;
 }
 
+// ... of the three entries of the simple protocol: not once another protocol is configured (lights_proto_api.h)
+int le_enter_simple(E* e) {
+  TRY(le_enter(e));
+  if (e->lp.protocol) return fail(e, TS_E_STATE, "lights_ext: the handle is configured for another protocol (ts_lights_proto_config)");
+  return TS_OK;
+}
+
 int le_grid(const E* e, int per_block_items) { return std::max(1, (e->le.x.G + per_block_items - 1) / per_block_items); }
 
 int le_sums(E* e) {
@@ -109,6 +116,9 @@ static int le_init(ts_handle e) {
   HIPOK(hipGetLastError());
   HIPOK(hipStreamSynchronize(e->stream));
   e->le.calls = 0; e->le.observed = false;
+  // (a protocol is configured per set of light tables: none now, and none of the previous one's arrays)
+  e->lp.p = LightsProto{}; e->lp.protocol = 0; e->lp.calls = 0; e->lp.bytes = 0;
+  e->lp.d_eps = nullptr; e->lp.q_stage = nullptr; e->lp.eps.clear();
   e->le.ready = true;
   return TS_OK;
 }
@@ -117,7 +127,7 @@ extern "C" {
 
 int ts_lights_ext_config(ts_handle e, int32_t state_dim, int32_t min_green) {
   if (!e) return TS_E_INVALID;
-  TRY(le_enter(e));
+  TRY(le_enter_simple(e));
   if (!le_dim_ok(state_dim) || min_green < 0) return fail(e, TS_E_INVALID, "lights_ext: state_dim must be 7, 11, 13, 17 or 19 and min_green >= 0");
   if (e->le.calls > 0) return fail(e, TS_E_STATE, "lights_ext: configure before the first control call");
   e->le.x.dim = state_dim; e->le.x.min_green = min_green;
@@ -127,7 +137,7 @@ int ts_lights_ext_config(ts_handle e, int32_t state_dim, int32_t min_green) {
 int ts_lights_ext_set_static(ts_handle e, const double* intersection_size, const double* penalty_score) {
   if (!e) return TS_E_INVALID;
   TRY(le_enter(e));
-  if (e->le.calls > 0) return fail(e, TS_E_STATE, "lights_ext: set the static features before the first control call");
+  if (e->le.calls > 0 || e->lp.calls > 0) return fail(e, TS_E_STATE, "lights_ext: set the static features before the first control call");
   const size_t n = (size_t)e->le.x.G * sizeof(double);
   if (intersection_size && n) HIPOK(hipMemcpyAsync(e->le.x.size, intersection_size, n, hipMemcpyHostToDevice, e->stream));
   if (penalty_score && n) HIPOK(hipMemcpyAsync(e->le.x.pen, penalty_score, n, hipMemcpyHostToDevice, e->stream));
@@ -137,14 +147,14 @@ int ts_lights_ext_set_static(ts_handle e, const double* intersection_size, const
 
 int ts_lights_ext_observe(ts_handle e, float* out) {
   if (!e) return TS_E_INVALID;
-  TRY(le_enter(e));
+  TRY(le_enter_simple(e));
   if (!e->le.observed) TRY(le_phase_a(e));
   return le_rows_out(e, e->le.x.state, out);
 }
 
 int ts_lights_ext_act(ts_handle e, const int8_t* actions, int32_t on_device, float* next_state) {
   if (!e) return TS_E_INVALID;
-  TRY(le_enter(e));
+  TRY(le_enter_simple(e));
   if (!actions) return fail(e, TS_E_INVALID, "lights_ext: null pointer");
   const int8_t* dev = nullptr;
   TRY(le_bytes(e, actions, on_device, 0, "an action", &dev));

@@ -25,8 +25,11 @@ Differences from the reference that a caller can observe:
   * learning light controllers are not part of the engine.  Under TRAFFIC_LIGHT_AGENT_ALGORITHM = "EXTERNAL" (or the
     reference's name "NEIGHBOR_RL_BATCHED") the groups decide nothing themselves and the caller drives them between ticks:
     `model.light_states()`, `model.control_lights(actions)`, `model.request_phases(phases)`
-    (include/trafficsim_lights_ext.h); the policy and its training are the caller's torch code.  The other RL variants
-    (NEIGHBOR_RL, RL_A2C_BATCHED, GAT_DQN*) are out of scope.
+    (include/trafficsim_lights_ext.h); the policy and its training are the caller's torch code.  "RL_A2C_BATCHED" and
+    "GAT_DQN_BATCHED" select the environment side of those two controllers (include/trafficsim_lights_proto.h): their
+    states, rewards and - `model.control_lights_q(q)` - GAT-DQN's epsilon-greedy step on the global stream; the learners
+    (update_a2c, _train_dqn) stay the caller's.  The non-batched variants (NEIGHBOR_RL, GAT_DQN) draw and infer inside the
+    shuffled schedule and are out of scope.
   * rain clouds are not exposed as agents (only `model.rain_map`).
 """
 from __future__ import annotations
@@ -499,6 +502,7 @@ class IntersectionLightGroup:
     # external light control only (intersection_light_group.py:91-92)
     _rl_phase = property(lambda s: int(s.model._light_controller()[s.index, 0]))
     rl_timer = property(lambda s: int(s.model._light_controller()[s.index, 1]))
+    epsilon = property(lambda s: float(s.model._light_epsilon()[s.index]))      # GAT_DQN_BATCHED (intersection_light_group.py:102)
 
     # ---- links (intersection_light_group.py:293-307) --------------------------------------------------------------
     def get_opposite_traffic_lights(self):
@@ -671,7 +675,8 @@ class CityModel:
             # engine's global stream continues from where that leaves it, as the reference's agents would
             from . import worldgen
             d = defaults or {}
-            if capi.LIGHT_ALGORITHMS.get(d.get("TRAFFIC_LIGHT_AGENT_ALGORITHM")) == capi.LIGHT_ALGORITHMS["EXTERNAL"]:
+            algo = d.get("TRAFFIC_LIGHT_AGENT_ALGORITHM")
+            if capi.LIGHT_ALGORITHMS.get(algo) == capi.LIGHT_ALGORITHMS["EXTERNAL"] or algo in capi.LIGHT_PROTOCOLS:
                 world_kwargs = dict(world_kwargs, approach_road_types=True)   # (penalty_score of the state vector)
             world_kwargs = dict(world_kwargs, cell_base_types=True)           # (the renderer's palette: render.type_plane)
             tables = worldgen.generate_world(width, height, seed=global_seed if global_seed is not None else self._seed,
@@ -857,18 +862,48 @@ class CityModel:
             s["light_ctrl"] = self.engine.lights_controller()
         return s["light_ctrl"]
 
-    # ---- external light control (include/trafficsim_lights_ext.h), between two step() calls ---------------------------
-    def light_states(self) -> np.ndarray:
-        """The state vector of every light group, (G, SRL_INPUT_DIMENSIONS) float32, as the reference's get_rl_state
-        builds it (rl_simple.py:95-143).  Calling it again before control_lights or step returns the same vectors."""
-        self._flush_host_writes()
-        return self.engine.lights_observe()
+    def _light_epsilon(self):
+        s = self._snapshot()
+        if s.get("light_eps") is None:
+            s["light_eps"] = self.engine.lights_proto_controller()
+        return s["light_eps"]
 
-    def control_lights(self, actions) -> np.ndarray:
-        """One action per group (0 keep, 1 ask for the other phase; numpy, a sequence or an int8 torch tensor on the
-        engine's device): the reference's action protocol (rl_simple.py:226-236).  Returns the next-state vectors."""
+    def _light_protocol(self) -> int:
+        """0: the simple protocol; 1 / 2: RL_A2C_BATCHED / GAT_DQN_BATCHED (include/trafficsim_lights_proto.h)"""
+        return capi.LIGHT_PROTOCOLS.get((self._defaults or {}).get("TRAFFIC_LIGHT_AGENT_ALGORITHM"), 0)
+
+    # ---- external light control (include/trafficsim_lights_ext.h, _lights_proto.h), between two step() calls ----------
+    def light_states(self, to_host: bool = True):
+        """The state vector of every light group, (G, SRL_INPUT_DIMENSIONS) float32, as the reference's get_rl_state
+        builds it (rl_simple.py:95-143).  Calling it again before control_lights or step returns the same vectors.
+        Under RL_A2C_BATCHED: (G, 13) as rl_a2c.get_rl_state; under GAT_DQN_BATCHED: (features (G, 5, 9), mask (G, 5)) as
+        rl_gatdqn.get_gat_state.  to_host=False computes them on the device only (engine.lights_device() /
+        lights_proto_device() hold them) and returns None."""
         self._flush_host_writes()
-        out = self.engine.lights_act(actions)
+        if self._light_protocol():
+            return self.engine.lights_proto_observe(to_host=to_host)
+        return self.engine.lights_observe(to_host=to_host)
+
+    def control_lights_q(self, q, want_next: bool = True, to_host: bool = True):
+        """GAT_DQN_BATCHED: the reference's epsilon-greedy step on q (G, 2) - numpy or a float32 torch tensor on the engine's
+        device - which draws from the global `random` stream like rl_gatdqn.py:289-292.  Returns (actions, rewards, next
+        features), (actions, rewards) with want_next=False, None with to_host=False (everything stays in
+        engine.lights_proto_device())."""
+        self._flush_host_writes()
+        out = self.engine.lights_proto_act_q(q, want_next=want_next, to_host=to_host)
+        self._invalidate()
+        return out
+
+    def control_lights(self, actions, to_host: bool = True):
+        """One action per group (0 keep, 1 ask for the other phase; numpy, a sequence or an int8 torch tensor on the
+        engine's device): the reference's action protocol (rl_simple.py:226-236).  Returns the next-state vectors; under
+        RL_A2C_BATCHED the rewards, under GAT_DQN_BATCHED (rewards, next features) - nothing is drawn.  to_host=False
+        brings nothing down and returns None."""
+        self._flush_host_writes()
+        if self._light_protocol():
+            out = self.engine.lights_proto_act(actions, to_host=to_host)
+        else:
+            out = self.engine.lights_act(actions, want_next=to_host)
         self._invalidate()
         return out
 

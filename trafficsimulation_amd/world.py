@@ -18,6 +18,14 @@ def build_engine(api: capi.CApi, tables, defaults: Optional[dict] = None, params
                  global_state=None, sched_state=None, global_seed: Optional[int] = None,
                  sched_seed: Optional[int] = None) -> capi.CApi:
     """CityModel.__init__ minus world-gen: maps -> light groups -> schedule -> RNG streams."""
+    d0 = (json.loads(defaults) if isinstance(defaults, (str, bytes)) else defaults) or {}
+    # the reference's A2C / GAT-DQN names are EXTERNAL plus a protocol of the extension (include/trafficsim_lights_proto.h)
+    proto = capi.LIGHT_PROTOCOLS.get(d0.get("TRAFFIC_LIGHT_AGENT_ALGORITHM"))
+    if proto and params is not None and int(params.light_algorithm) != capi.LIGHT_ALGORITHMS["EXTERNAL"]:
+        raise capi.EngineError(capi.TS_E_INVALID, f"{d0['TRAFFIC_LIGHT_AGENT_ALGORITHM']} in defaults needs params.light_algorithm = "
+                               f"EXTERNAL ({capi.LIGHT_ALGORITHMS['EXTERNAL']}), got {int(params.light_algorithm)}")
+    if proto:
+        defaults = {**d0, "TRAFFIC_LIGHT_AGENT_ALGORITHM": "EXTERNAL"}
     p = params if params is not None else api.params_from_defaults(defaults)
     api.create(tables["allowed_dirs_map"], tables["is_road_map"], tables["road_type_map"],
                tables["intersection_map"], p)
@@ -27,6 +35,9 @@ def build_engine(api: capi.CApi, tables, defaults: Optional[dict] = None, params
         d = json.loads(defaults) if isinstance(defaults, (str, bytes)) else defaults
         if "SRL_INPUT_DIMENSIONS" in d or "SRL_MIN_GREEN" in d:
             api.lights_config(int(d.get("SRL_INPUT_DIMENSIONS", 13)), int(d.get("SRL_MIN_GREEN", 5)))
+    if proto:
+        api.lights_proto_config(proto, int(d0.get("GAT_TRAFFIC_RL_MIN_GREEN", 5)) if proto == capi.LP_GAT else 5,
+                                float(d0.get("EPS_MIN", 0.1)), float(d0.get("EPS_DECAY_RATE", 1e-5)))
     kinds = np.asarray(tables["schedule_kinds0"]).astype(int)
     # run-length encode consecutive kinds into schedule_add calls (insertion order is preserved)
     i = 0
