@@ -722,12 +722,12 @@ class CApi:
         return c
 
     QUAD_STATS = ("jobs", "handbacks", "window", "heap", "budget", "path_buffer", "policy_bail", "policy_overflow",
-                  "searches", "epoch_wraps", "passes")
+                  "searches", "epoch_wraps", "passes", "sift_third_level", "sift_blocking_steps")
 
     def debug_quad_stats(self) -> dict:
         """Debugging hook (ts_debug_quad_stats, not part of include/trafficsim.h): the quad searcher's counters over this
         engine's quad passes - entries it took, hand-backs to k_replan in all and by reason, searches started, table-epoch
-        wraps, passes."""
+        wraps, passes, and the sift-down's steps beyond LDS (on the third level fetched ahead / blocking, below it)."""
         fn = getattr(self.lib, self.prefix + "debug_quad_stats", None) if self.prefix == "ts_" else None
         if fn is None:
             raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}debug_quad_stats: this engine has no quad searcher")

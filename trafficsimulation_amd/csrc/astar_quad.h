@@ -10,8 +10,12 @@
 //     (16 x 156 x 8 B = 19.5 KB per wave: seven waves per CU beside k_replan's side waves), deeper slots in the search's
 //     HBM spill.  Sift-down, two levels per LDS round trip: lanes 0 / 1 of the quad fetch the hole's two children, the four
 //     lanes its four grandchildren, one DPP swap shows each its sibling's key, "my entry moves up" is one compare (strict
-//     '<', ties to the parent, then to the left child: astar_numba.py:67-85).  Sift-up: the four lanes fetch four
-//     ancestors of the new slot at once (52-65);
+//     '<', ties to the parent, then to the left child: astar_numba.py:67-85).  Beyond LDS the first step takes three
+//     levels in one HBM round trip - with the children and grandchildren every lane requests the two children of its
+//     own grandchild, and the lane whose grandchild the hole moves to decides that level from its registers - so the
+//     blocking loads start three levels below the LDS share (heaps beyond 1 022 entries), two per round trip.  Sixteen
+//     searches in lockstep wait for every round trip any one of them needs: one a quad takes on 18 % of its turns is on
+//     96 % of the wave's.  Sift-up: the four lanes fetch the twelve ancestors a slot can have in one LDS round trip (52-65);
 //   * dir_arr (indexed by heap SLOT, never moved by the sifts: the stale-slot quirk) is only ever read at the heap's
 //     last slot and written at the slots behind it - a stack.  Two bits per slot, the 32 slots around the heap's end in
 //     a register pair, the rest in HBM; slot 0 in a register of its own;
@@ -32,8 +36,9 @@
 // first unfinished one suspends the pass (DV_SUSPEND) and becomes the quad's search.
 // Measured: 86 instructions per expansion against k_replan's 289, but only ~50 heaps of this workload
 // fit the LDS of a CU whatever the kernel, so the quads run at one to two waves per SIMD with half of each heap in HBM: worth
-// 25-30 % on a replanning wave, and slower than k_replan on a queue that is bounded by its longest search - run_replans
-// (engine.hip) sends them queues of TS_QUAD_MIN = 262 144 entries and more.
+// 25-30 % on a replanning wave (and 7 % more since the sifts' round trips above: DESIGN.md section 5), and slower than
+// k_replan on a queue that is bounded by its longest search - run_replans (engine.hip) sends them queues of
+// TS_QUAD_MIN = 262 144 entries and more.
 #pragma once
 #include "replan.h"
 
@@ -71,9 +76,11 @@ constexpr int Q_MAX_EXP = TS_QUAD_MAX_EXP;  // expansions after which a quad han
 constexpr uint32_t Q_DIST_MASK = (1u << 22) - 1, Q_STAMP_SHIFT = 24, Q_DIR_SHIFT = 22;
 enum { QS_NEEDJOB = 0, QS_POLICY = 1, QS_SEARCH = 2, QS_FOUND = 3, QS_EMPTY = 4, QS_ABANDON = 5, QS_IDLE = 6 };
 // the quads' own diagnostics (QSlots::stats, added up per engine by run_quad_pass, read by ts_debug_quad_stats): hand-backs
-// to k_replan by reason, searches started, table-epoch wraps.  Not simulation state: never exchanged, never checkpointed.
+// to k_replan by reason, searches started, table-epoch wraps, and the sift-down's steps beyond LDS: those that consulted the
+// third level fetched ahead (QST_STEP3) and the blocking steps below it (QST_DEEP).  Not simulation state: never exchanged,
+// never checkpointed.
 enum { QST_WINDOW = 1, QST_HEAP = 2, QST_BUDGET = 3, QST_PATHBUF = 4, QST_BAIL = 5, QST_OVERFLOW = 6, QST_SEARCHES = 7, QST_WRAPS = 8,
-       QST_N = 16 };
+       QST_STEP3 = 9, QST_DEEP = 10, QST_N = 16 };
 
 struct QSlots {
   int n_slots;            // searches = quads: sixteen per wave
@@ -91,6 +98,7 @@ struct QSlots {
 constexpr int Q_DWORDS = (QL + Q_SPILL) / 16 + 4;
 constexpr int Q_HEAP_MAX = (QL + Q_SPILL) < (32 * QL - 2) ? (QL + Q_SPILL) : (32 * QL - 2);   // largest heap a quad carries
 
+static_assert(Q_HEAP_MAX < (1 << 13), "a push fetches the twelve ancestors a slot can have at once (quad_turn's sift-up)");
 __shared__ unsigned long long q_lds[16 * QL + 64];     // (the last 64 entries: one scratch slot per lane, see q_lput_if)
 
 // what a quad keeps about its search while the lockstep loop runs (every lane of the quad holds the same values)
@@ -107,8 +115,9 @@ struct QState {
   int n_exp, n_relax;
   unsigned long long xpre;  // heap entry hs - 1 when it lies beyond LDS (requested at the end of the previous turn)
   int why;                  // why the search was abandoned (QST_WINDOW / g, QST_HEAP, QST_BUDGET, QST_PATHBUF): QSlots::stats
+  unsigned n_step3, n_deep; // QST_STEP3 / QST_DEEP of this quad over the kernel's lifetime (counted out once, at its end)
 #ifdef TS_QUAD_PROF
-  long long pf[8], pt;
+  long long pf[10], pt;   // (8: delivery of xpre; 9: the deep sift's first step, before its blocking levels)
 #endif
 };
 #ifdef TS_QUAD_PROF
@@ -158,10 +167,9 @@ __device__ __forceinline__ u64 q_gload_now(const TS_GLOBAL u64* p) {
   asm volatile("global_load_dwordx2 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
-__device__ __forceinline__ u64 q_hget(const QConst& K, int k) {
-  u64 v;
-  if (k < QL) v = q_lds[K.lbase + k]; else v = q_gload_now(K.gq + (k - QL));
-  return v;
+// (two of them on their way together, one wait)
+__device__ __forceinline__ void q_gload2_now(const TS_GLOBAL u64* pa, const TS_GLOBAL u64* pb, u64& a, u64& b) {
+  asm volatile("global_load_dwordx2 %0, %2, off\n\tglobal_load_dwordx2 %1, %3, off\n\ts_waitcnt vmcnt(0)" : "=&v"(a), "=&v"(b) : "v"(pa), "v"(pb) : "memory");
 }
 __device__ __forceinline__ void q_hput(const QConst& K, int k, u64 v) {
   if (k < QL) q_lds[K.lbase + k] = v; else K.gq[k - QL] = v;
@@ -180,9 +188,12 @@ __device__ __forceinline__ QPair quad_sift2_load(const QConst& K, int p, int siz
   QPair r;
   r.cv = c < size; r.gv = gc < size;
   r.ce = 0; r.ge = 0;
-  if (DEEP) {
-    if (r.cv) r.ce = q_hget(K, c);
-    if (r.gv) r.ge = q_hget(K, gc);
+  if (DEEP) {    // (the blocking levels: both entries requested together and waited for once; LDS and HBM both read, clamped)
+    const u64 cl = q_lget(K, min(c, QL - 1)), gl = q_lget(K, min(gc, QL - 1));
+    u64 cg, gg;
+    q_gload2_now(K.gq + ((r.cv & (c >= QL)) ? c - QL : 0), K.gq + ((r.gv & (gc >= QL)) ? gc - QL : 0), cg, gg);
+    r.ce = c < QL ? cl : cg;
+    r.ge = gc < QL ? gl : gg;
   } else {       // (no branch around the reads: a slot that does not exist is read at the root and not used)
     r.ce = q_lget(K, r.cv ? c : 0);
     r.ge = q_lget(K, r.gv ? gc : 0);
@@ -193,14 +204,21 @@ __device__ __forceinline__ QPair quad_sift2_load(const QConst& K, int p, int siz
 // a valid address when the slot lies on the other side or does not exist), the right one picked afterwards.  A load the
 // compiler can count is a load it can wait for precisely: behind a branch it would make every later wait for an older
 // load (the expansion's map entries and table records) a wait for all of them.
-struct QBoth { u64 cl, cg, gl, gg; int c, gc; bool cv, gv; };
+// With them travels a third level: each lane requests the two children of its grandchild (h0 / h1: slots 2 gc + 1, 2 gc + 2),
+// so the lane whose grandchild the hole moves to decides the next level from its own registers (quad_sift1_apply) and the
+// blocking loads only start three levels below the LDS share.  This step runs where 4 p + 6 >= QL, so those slots
+// (8 p + 7 and up) always lie in the spill.  A slot that does not exist is requested at the spill's first entry (a line the
+// quad keeps hitting) and not used.
+struct QBoth { u64 cl, cg, gl, gg, h0, h1; int c, gc; bool cv, gv; };
 __device__ __forceinline__ QBoth quad_sift2_load_both(const QConst& K, int p, int size) {
   const int j = K.j, side = j & 1;
   QBoth r;
   r.c = 2 * p + 1 + side; r.gc = 4 * p + 3 + j;
+  const int hc = 2 * r.gc + 1;
   r.cv = r.c < size; r.gv = r.gc < size;
   r.cl = q_lget(K, min(r.c, QL - 1)); r.gl = q_lget(K, min(r.gc, QL - 1));
-  r.cg = K.gq[max(min(r.c, QL + Q_SPILL - 1) - QL, 0)]; r.gg = K.gq[max(min(r.gc, QL + Q_SPILL - 1) - QL, 0)];
+  r.cg = K.gq[r.cv ? max(r.c - QL, 0) : 0]; r.gg = K.gq[r.gv ? max(r.gc - QL, 0) : 0];
+  r.h0 = K.gq[hc < size ? max(hc - QL, 0) : 0]; r.h1 = K.gq[hc + 1 < size ? max(hc + 1 - QL, 0) : 0];
   return r;
 }
 template <bool DEEP>
@@ -233,11 +251,30 @@ __device__ __forceinline__ bool quad_sift2_apply(const QConst& K, int& p, int xf
   return false;
 }
 
+// One level more below the hole at slot p, a grandchild of the step before: lane t = (p + 1) & 3 of the quad fetched that
+// slot and, with it, both of its children (QBoth::h0 / h1).  It decides alone - smallest of (x, left, right), ties to x, then
+// to the left - and one OR over the quad tells the others.  Returns true when x has found its place (p); `wr`: the slot written.
+__device__ __forceinline__ bool quad_sift1_apply(const QConst& K, int& p, int xf, u64 h0, u64 h1, int size, int& wr) {
+  const int c0 = 2 * p + 1;
+  const bool mine = K.j == ((p + 1) & 3);
+  const int f0 = c0 < size ? hq_f(h0) : 0x7FFFFFFF, f1 = c0 + 1 < size ? hq_f(h1) : 0x7FFFFFFF;
+  const bool lw = (unsigned)f0 < min((unsigned)xf, (unsigned)f1 + 1u);
+  const bool rw = (unsigned)f1 < min((unsigned)xf, (unsigned)f0);
+  const int bits = quad_or(mine ? (lw ? 1 : 0) | (rw ? 2 : 0) : 0);
+  wr = -1;
+  if (bits == 0) return true;
+  const int sdn = bits >> 1;
+  q_hput_if(K, mine, p, sdn ? h1 : h0);
+  wr = p;
+  p = c0 + sdn;
+  return false;
+}
+
 // One turn of astar_core's main loop (astar_numba.py:136-237) for every quad whose search is on.  Returns the quad's
 // new state: QS_SEARCH, QS_FOUND (the goal was popped), QS_EMPTY (heap empty: `return []`) or QS_ABANDON.
 // Order of the turn (what the reference does one after the other is only reordered where the results cannot tell):
 //   pop -> the expansion's loads leave (map entries, table records; the parents of the next two heap slots when they lie
-//   beyond LDS) -> sift-down through the levels in LDS -> the loads of its first two levels beyond LDS leave -> the popped
+//   beyond LDS) -> sift-down through the levels in LDS -> the loads of its first three levels beyond LDS leave -> the popped
 //   cell's neighbours are evaluated (registers only) while those travel -> the sift-down finishes -> table records, pushes.
 __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
   if (s.hs <= 0) return QS_EMPTY;
@@ -283,6 +320,10 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
   // (both loads always leave - of the spill's first entry when there is nothing to fetch: see quad_sift2_load_both)
   const u64 pv0 = K.gq[max(pa0 - QL, 0)], pv1 = K.gq[max(pa1 - QL, 0)];
   QP(0);
+#ifdef TS_QUAD_PROF
+  asm volatile("" : : "v"(s.xpre));     // (the stamp takes delivery of the entry requested at the end of the previous turn)
+  QP(8);
+#endif
   int p = 0;
   bool sinking = false;
   u64 x = 0;
@@ -335,25 +376,37 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
   // leave: a load still pending on some path would be waited for behind them - stores included - where its register is
   // next written.)
   asm volatile("" : : "v"(relax), "v"(nf_l), "v"(nxy_l), "v"(ngi));   // (the evaluation first ...)
-  asm volatile("" : : "v"(db.cg), "v"(db.gg), "v"(pv0), "v"(pv1));
+  asm volatile("" : : "v"(db.cg), "v"(db.gg), "v"(db.h0), "v"(db.h1), "v"(pv0), "v"(pv1));
   QPair dp;
   dp.cv = db.cv; dp.gv = db.gv;
   dp.ce = db.c < QL ? db.cl : db.cg;
   dp.ge = db.gc < QL ? db.gl : db.gg;
-  if (last_i > 0) {
-    if (sinking) {
-      bool done;
-      int w0, w1;
-      done = quad_sift2_apply<true>(K, p, xf, dp, w0, w1);
+  bool deep = false;                    // the hole sinks on below the entries that were fetched ahead
+  if (sinking) {
+    int w0, w1;
+    deep = !quad_sift2_apply<true>(K, p, xf, dp, w0, w1);
+    if ((w0 >= 0) & ((w0 == pa0) | (w0 == pa1))) { if (w0 == pa0) pa0 = -1; if (w0 == pa1) pa1 = -1; }
+    if ((w1 >= 0) & ((w1 == pa0) | (w1 == pa1))) { if (w1 == pa0) pa0 = -1; if (w1 == pa1) pa1 = -1; }
+    // (the third level that travelled with the two: the lane that holds the hole's new slot holds its children)
+    deep = deep & (2 * p + 1 < last_i);
+    if (deep) {
+      s.n_step3++;
+      deep = !quad_sift1_apply(K, p, xf, db.h0, db.h1, last_i, w0);
       if ((w0 >= 0) & ((w0 == pa0) | (w0 == pa1))) { if (w0 == pa0) pa0 = -1; if (w0 == pa1) pa1 = -1; }
-      if ((w1 >= 0) & ((w1 == pa0) | (w1 == pa1))) { if (w1 == pa0) pa0 = -1; if (w1 == pa1) pa1 = -1; }
-      while (!done) {
-        const QPair r = quad_sift2_load<true>(K, p, last_i);
-        done = quad_sift2_apply<true>(K, p, xf, r, w0, w1);
-        if ((w0 >= 0) & ((w0 == pa0) | (w0 == pa1))) { if (w0 == pa0) pa0 = -1; if (w0 == pa1) pa1 = -1; }
-        if ((w1 >= 0) & ((w1 == pa0) | (w1 == pa1))) { if (w1 == pa0) pa0 = -1; if (w1 == pa1) pa1 = -1; }
-      }
+      deep = deep & (2 * p + 1 < last_i);
     }
+  }
+  QP(9);
+  while (deep) {    // (the blocking levels: a hole that still has children three levels below the LDS share)
+    int w0, w1;
+    s.n_deep++;
+    const QPair r = quad_sift2_load<true>(K, p, last_i);
+    deep = !quad_sift2_apply<true>(K, p, xf, r, w0, w1);
+    if ((w0 >= 0) & ((w0 == pa0) | (w0 == pa1))) { if (w0 == pa0) pa0 = -1; if (w0 == pa1) pa1 = -1; }
+    if ((w1 >= 0) & ((w1 == pa0) | (w1 == pa1))) { if (w1 == pa0) pa0 = -1; if (w1 == pa1) pa1 = -1; }
+    deep = deep & (2 * p + 1 < last_i);
+  }
+  if (last_i > 0) {
     q_hput_if(K, j == 0, p, x);
     if (p == pa0) pa0 = -1;
     if (p == pa1) pa1 = -1;
@@ -389,31 +442,32 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
         const int sh = 2 * ((i - s.wb) & 31);
         s.dwin = (s.dwin & ~(3ull << sh)) | ((u64)(unsigned)dd << sh);
       }
-      // heap_sift_up (52-65): the four lanes fetch four ancestors of slot i at a time; ancestor k = ((i + 1) >> k) - 1.
+      // heap_sift_up (52-65): ancestor k of slot i is slot ((i + 1) >> k) - 1, and a heap of Q_HEAP_MAX entries has at most
+      // twelve levels above a slot: lane j of the quad fetches ancestors 1 + j, 5 + j and 9 + j in ONE LDS round trip (a
+      // wave's sixteen pushes rise 0 to 12 levels: fetched four at a time, the wave paid three round trips for the one
+      // that rises furthest).  No store of this push lies between the reads: reading them first changes nothing.
       // (ancestors 1-4 of a slot beyond 2 QL can lie beyond LDS: those of the first two pushes of a turn were requested at
       // the pop, unless something has written to them since; the rest are fetched like any slot)
       const int depth = 31 - __builtin_clz((unsigned)(i + 1));
       const int pa = npush == 0 ? pa0 : npush == 1 ? pa1 : -1;
       const u64 pv = npush == 0 ? pv0 : pv1;
-      int rise = 0;
-      for (int base = 0; base < depth; base += 4) {
-        const int k = base + 1 + j;
-        const bool has = k <= depth;
-        const int a = (int)(((unsigned)(i + 1) >> (k & 31)) - 1u);
-        // (the read is unconditional - of the root for a lane without an ancestor, or whose ancestor lies beyond LDS: that
-        // entry was requested at the pop or is fetched behind one branch)
-        u64 anc = q_lget(K, (has & (a < QL)) ? a : 0);
-        if (base == 0 && i > 2 * QL) {
-          if (has & (a >= QL)) { if (a == pa) anc = pv; else anc = q_gload_now(K.gq + (a - QL)); }
-        }
-        const bool up = has & (nf < hq_f(anc));
-        const int um = quad_or(up ? (1 << j) : 0);
-        const int cnt = __builtin_ctz(~(unsigned)um);      // the entry passes a PREFIX of its ancestors (heap order)
-        const int dst = (int)(((unsigned)(i + 1) >> ((k - 1) & 31)) - 1u);
-        q_hput_if(K, up, dst, anc);                        // ancestor k moves to where k - 1 was
-        rise += cnt;
-        if (cnt < 4) break;
+      const int k0 = 1 + j, k1 = 5 + j, k2 = 9 + j;
+      const bool has0 = k0 <= depth, has1 = k1 <= depth, has2 = k2 <= depth;
+      const int a0 = (int)(((unsigned)(i + 1) >> k0) - 1u), a1 = (int)(((unsigned)(i + 1) >> k1) - 1u), a2 = (int)(((unsigned)(i + 1) >> k2) - 1u);
+      // (the reads are unconditional - of the root for a lane without an ancestor, or whose ancestor lies beyond LDS: that
+      // entry was requested at the pop or is fetched behind one branch)
+      u64 anc0 = q_lget(K, (has0 & (a0 < QL)) ? a0 : 0);
+      const u64 anc1 = q_lget(K, (has1 & (a1 < QL)) ? a1 : 0), anc2 = q_lget(K, (has2 & (a2 < QL)) ? a2 : 0);
+      if (i > 2 * QL) {
+        if (has0 & (a0 >= QL)) { if (a0 == pa) anc0 = pv; else anc0 = q_gload_now(K.gq + (a0 - QL)); }
       }
+      const bool up0 = has0 & (nf < hq_f(anc0)), up1 = has1 & (nf < hq_f(anc1)), up2 = has2 & (nf < hq_f(anc2));
+      const int um = quad_or((up0 ? (1 << j) : 0) | (up1 ? (16 << j) : 0) | (up2 ? (256 << j) : 0));
+      const int rise = __builtin_ctz(~(unsigned)um);       // the entry passes a PREFIX of its ancestors (heap order)
+      // ancestor k moves to where k - 1 was
+      q_hput_if(K, up0, (int)(((unsigned)(i + 1) >> (k0 - 1)) - 1u), anc0);
+      q_hput_if(K, up1, (int)(((unsigned)(i + 1) >> (k1 - 1)) - 1u), anc1);
+      q_hput_if(K, up2, (int)(((unsigned)(i + 1) >> (k2 - 1)) - 1u), anc2);
       const int fin = (int)(((unsigned)(i + 1) >> (rise & 31)) - 1u);
       q_hput_if(K, j == 0, fin, hq_pack(nf, nxy));
       // (this push wrote ancestors 0 .. rise of slot i: a lane's copy for the next push is stale if its slot is one of them -
@@ -492,14 +546,14 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
   K.rt2_3 = (int)((double)P.road_type_penalty_r3 * 2.0);
   uint32_t epoch = qs.slot_epoch[slot];
   QState s;
-  s.hs = 0; s.dir0 = -1; s.wb = 0; s.dwin = 0; s.xpre = 0; s.why = 0; s.gx = s.gy = s.sx = s.sy = 0; s.ox = s.oy = 0; s.goal_xy = 0; s.stamp = 0; s.soft = 0; s.n_exp = 0; s.n_relax = 0;
+  s.hs = 0; s.dir0 = -1; s.wb = 0; s.dwin = 0; s.xpre = 0; s.why = 0; s.n_step3 = 0; s.n_deep = 0; s.gx = s.gy = s.sx = s.sy = 0; s.ox = s.oy = 0; s.goal_xy = 0; s.stamp = 0; s.soft = 0; s.n_exp = 0; s.n_relax = 0;
   QReq req;
   req.start = req.goal = req.soft = req.cap = 0; req.out = nullptr;
   int st = QS_NEEDJOB, job = -1, n_done = 0;
   unsigned n_started = 0, n_wraps = 0;      // (QST_SEARCHES / QST_WRAPS of this quad: counted out once, at the end)
 #ifdef TS_QUAD_PROF
   long long pf_t0 = clock64(), pf_search = 0, pf_turns = 0, pf_quadturns = 0;
-  for (int k = 0; k < 8; k++) s.pf[k] = 0;
+  for (int k = 0; k < 10; k++) s.pf[k] = 0;
   s.pt = clock64();
 #endif
   for (;;) {
@@ -607,12 +661,15 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
     atomicAdd((unsigned long long*)&d.cnt->prof[2], (unsigned long long)pf_turns);
     atomicAdd((unsigned long long*)&d.cnt->prof[3], (unsigned long long)pf_quadturns);
     for (int k = 0; k < 8; k++) atomicAdd((unsigned long long*)&d.cnt->qprof[k], (unsigned long long)s.pf[k]);
+    for (int k = 8; k < 10; k++) atomicAdd((unsigned long long*)&d.cnt->prof[k - 4], (unsigned long long)s.pf[k]);   // (prof[4..5]: DevCnt keeps its layout)
   }
 #endif
   if (one) {
     qs.slot_epoch[slot] = epoch;
     if (n_started) atomicAdd(&qs.stats[QST_SEARCHES], (unsigned long long)n_started);
     if (n_wraps) atomicAdd(&qs.stats[QST_WRAPS], (unsigned long long)n_wraps);
+    if (s.n_step3) atomicAdd(&qs.stats[QST_STEP3], (unsigned long long)s.n_step3);
+    if (s.n_deep) atomicAdd(&qs.stats[QST_DEEP], (unsigned long long)s.n_deep);
   }
   // every hand-back of this wave is published before the wave counts itself out (k_replan's replan_turn waits on both)
   __threadfence();

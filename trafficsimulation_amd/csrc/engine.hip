@@ -195,6 +195,9 @@ int run_quad_pass(E* e) {
     HIPOK(hipMemcpy(qf, d.cnt->qprof, sizeof(qf), hipMemcpyDeviceToHost));
     fprintf(stderr, "[quadprof] per wave turn: pop+loads %.0f, sift LDS %.0f, sift deep %.0f, goal/stale %.0f, eval %.0f, pushes(+skipped) %.0f, tail %.0f, between turns %.0f\n",
             (double)qf[0] / pf[2], (double)qf[1] / pf[2], (double)qf[2] / pf[2], (double)qf[3] / pf[2], (double)qf[4] / pf[2], (double)qf[5] / pf[2], (double)qf[6] / pf[2], (double)qf[7] / pf[2]);
+    // (stamped apart from "sift LDS" / "sift deep": the wait for the entry the pop moves to the root; the deep sift's first step, on
+    // the entries fetched ahead - "sift deep" is what follows it, the blocking levels)
+    fprintf(stderr, "[quadprof] per wave turn: delivery of the last entry %.0f, deep sift's first step %.0f\n", (double)pf[4] / pf[2], (double)pf[5] / pf[2]);
     HIPOK(hipMemset(d.cnt->qprof, 0, sizeof(qf)));
   }
 #endif
@@ -2117,14 +2120,16 @@ int ts_debug_read(ts_handle e, int32_t* out8) {
 
 // debugging hook (not part of include/trafficsim.h): the quad searcher's counters over this engine's quad passes, as int64 -
 // [0] entries given to k_replan_quad, [1] hand-backs to k_replan, [2 .. 7] hand-backs by reason (window / g, heap, expansion
-// budget, path buffer, policy bail, policy overflow), [8] searches started, [9] table-epoch wraps, [10] quad passes.  Writes
+// budget, path buffer, policy bail, policy overflow), [8] searches started, [9] table-epoch wraps, [10] quad passes, [11] sift-down
+// steps that consulted the third heap level fetched ahead, [12] blocking sift-down steps below it.  Writes
 // min(n, TS_QUAD_STATS_N) words and returns TS_QUAD_STATS_N.
-constexpr int TS_QUAD_STATS_N = 11;
+constexpr int TS_QUAD_STATS_N = 13;
 int ts_debug_quad_stats(ts_handle e, int64_t* out, int32_t n) {
   if (!e || (!out && n > 0) || n < 0) return TS_E_INVALID;
   const long long* qs = e->quad_stats;
   const long long v[TS_QUAD_STATS_N] = {e->quad_jobs, e->quad_fallbacks, qs[QST_WINDOW], qs[QST_HEAP], qs[QST_BUDGET], qs[QST_PATHBUF],
-                                        qs[QST_BAIL], qs[QST_OVERFLOW], qs[QST_SEARCHES], qs[QST_WRAPS], e->quad_passes};
+                                        qs[QST_BAIL], qs[QST_OVERFLOW], qs[QST_SEARCHES], qs[QST_WRAPS], e->quad_passes,
+                                        qs[QST_STEP3], qs[QST_DEEP]};
   for (int k = 0; k < std::min<int>(n, TS_QUAD_STATS_N); k++) out[k] = v[k];
   return TS_QUAD_STATS_N;
 }
