@@ -1,0 +1,115 @@
+"""Route demand through the Mesa-style facade: CityModel.planned_load() and intersection_demand() on a seed-built city
+against CApi and against download_path, `vehicles=` as agents and as spawn indices, save / load / deepcopy / pickle, and
+examples/run_city.py --demand."""
+import copy
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import demand_expect as de
+from tests import observe_util as ou
+from trafficsimulation_amd import _capi as capi
+from trafficsimulation_amd.mesa_api import CityModel
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+TICKS = 30
+
+
+@pytest.fixture(scope="module")
+def city():
+    from run_city import TRAFFIC
+    m = CityModel(96, 96, seed=5, traffic=dict(TRAFFIC, P_int=200000, P_thr=60000, service_food=40, service_waste=40))
+    for _ in range(TICKS):
+        m.step()
+    yield m
+    m.close()
+
+
+def capi_planes(eng, n_bins):
+    return np.stack([np.stack([eng.demand_plane(b, d) for d in range(4)]) for b in range(n_bins)])
+
+
+def test_planned_load_agrees_with_capi_and_download_path(city):
+    m = city
+    eng = m.engine
+    veh, _ = de.engine_vehicles(eng)
+    assert len(veh) > 20 and len(veh) == len(m.active_vehicle_agents)
+    got = m.planned_load()
+    want = de.planes(m.height, m.width, veh)
+    assert got["load"].shape == (1, m.height, m.width) and got["by_direction"].shape == (1, 4, m.height, m.width)
+    assert np.array_equal(got["by_direction"], want) and np.array_equal(got["load"][0], want[0].sum(axis=0, dtype=np.uint32))
+    assert got["steps"] == int(want.sum()) == de.remaining_steps(veh) > 0 and got["vehicles"] == len(veh) and got["tick"] == TICKS
+    got = m.planned_load(bins=4, bin_cells=16, open_tail=False)
+    assert np.array_equal(got["by_direction"], capi_planes(eng, 4)) and np.array_equal(got["by_direction"], de.planes(m.height, m.width, veh, 4, 16, False))
+    assert got["bin_steps"] == [int(got["load"][b].sum()) for b in range(4)] and eng.demand_info()["n_bins"] == 4
+    pooled = m.planned_load(bins=2, bin_cells=10, pooled=8)
+    full = de.planes(m.height, m.width, veh, 2, 10, True)
+    assert pooled["load"].shape == (2, 12, 12) and pooled["by_direction"].shape == (2, 4, 12, 12)
+    for b in range(2):
+        assert np.array_equal(pooled["load"][b], ou.pooled(full[b].sum(axis=0, dtype=np.uint32), 8))
+        for d in range(4):
+            assert np.array_equal(pooled["by_direction"][b, d], ou.pooled(full[b, d], 8))
+
+
+def test_intersection_demand_is_keyed_like_the_report(city):
+    m = city
+    m.observe()
+    report = m.intersection_report()
+    m.observe(False)
+    got = m.intersection_demand(bins=3, bin_cells=8)
+    rows = m.engine.demand_groups()
+    assert len(got) == len(report) == len(rows) > 0 and rows.shape[1:] == (3, len(capi.DG_FIELDS))
+    f = capi.DG_FIELDS.index
+    for g, (d, r) in enumerate(zip(got, report)):
+        assert (d["group"], d["index"]) == (r["group"], r["index"]) and d["bins"] == 3 and d["tick"] == TICKS
+        assert d["planned_ns"] == rows[g, :, f("ns_in")].tolist() and d["planned_ew"] == rows[g, :, f("ew_in")].tolist()
+        assert set(d["planned_throughput_by_direction"]) == set(r["throughput_by_direction"]) == set("NESW")
+        assert d["planned_throughput"] == rows[g, :, 2:].sum(axis=1).tolist()
+    assert sum(sum(d["planned_throughput"]) for d in got) > 0
+
+
+def test_vehicles_as_agents_and_as_spawn_indices(city):
+    m = city
+    agents = m.active_vehicle_agents[::3]
+    idx = [v._spawn_idx for v in agents]
+    veh, spawn = de.engine_vehicles(m.engine)
+    want = de.planes(m.height, m.width, [v for v, s in zip(veh, spawn) if int(s) in set(idx)], 2, 12, True)
+    by_agent = m.planned_load(bins=2, bin_cells=12, vehicles=agents)
+    by_index = m.planned_load(bins=2, bin_cells=12, vehicles=idx)
+    assert by_agent["selected"] and by_agent["vehicles"] == len(agents) == by_index["vehicles"]
+    assert np.array_equal(by_agent["by_direction"], want) and np.array_equal(by_index["by_direction"], want) and want.sum() > 0
+    assert m.planned_load(vehicles=[])["steps"] == 0
+    with pytest.raises(ValueError):
+        m.planned_load(vehicles=[m.engine.num_spawned()])
+
+
+def test_save_load_copy_and_pickle_start_without_a_result(city, tmp_path):
+    m = city
+    want = m.planned_load(bins=2, bin_cells=12)
+    path = str(tmp_path / "city.npz")
+    m.save(path)
+    for how, other in (("load", CityModel.load(path)), ("deepcopy", copy.deepcopy(m)), ("pickle", pickle.loads(pickle.dumps(m)))):
+        assert other.engine.demand_info()["n_bins"] == 0, f"{how}: a new engine starts without a result"
+        with pytest.raises(capi.EngineError) as ex:
+            other.engine.demand_plane()
+        assert ex.value.code == capi.TS_E_STATE
+        got = other.planned_load(bins=2, bin_cells=12)
+        assert np.array_equal(got["by_direction"], want["by_direction"]) and got["steps"] == want["steps"], how
+        other.close()
+    assert m.engine.demand_info()["n_bins"] == 2
+
+
+def test_run_city_writes_the_planned_load(tmp_path):
+    out = tmp_path / "demand.npy"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "run_city.py"), "--size", "96", "--ticks", "30", "--demand", str(out)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "planned load:" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+    load = np.load(out)
+    assert load.shape == (96, 96) and load.dtype == np.uint32 and load.sum() > 0

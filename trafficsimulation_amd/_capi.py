@@ -131,6 +131,22 @@ class TsObserveInfo(C.Structure):
                 ("device_bytes", C.c_uint64)]
 
 
+# include/trafficsim_demand.h: the fields of ts_demand_groups, TsDemandQuery, TsDemandInfo
+DEMAND_MAX_BINS = 8
+DG_FIELDS = ["ns_in", "ew_in", "enter_n", "enter_e", "enter_s", "enter_w"]
+
+
+class TsDemandQuery(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("bin_cells", C.c_int32), ("open_tail", C.c_int32), ("n_select", C.c_int32),
+                ("select_on_device", C.c_int32), ("reserved", C.c_int32), ("select", C.c_void_p)]
+
+
+class TsDemandInfo(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("bin_cells", C.c_int32), ("open_tail", C.c_int32), ("selected", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("tick", C.c_int64), ("vehicles", C.c_int64),
+                ("steps", C.c_uint64), ("bin_steps", C.c_uint64 * 8), ("device_bytes", C.c_uint64)]
+
+
 # include/trafficsim_triplog.h: TsTripRecord as a numpy record, the TS_TRIP_END_* codes, TsTripLogInfo
 TRIP_DTYPE = np.dtype([(n, np.int32) for n in (
     "spawn_idx", "population", "vehicle_type", "end_reason", "origin_x", "origin_y", "dest_x", "dest_y", "end_x", "end_y",
@@ -946,6 +962,123 @@ class CApi:
             raise RuntimeError("observe_device: torch cannot reach the engine's device - import torch before the engine "
                                "library is loaded, or download with observe_plane") from ex
         return t.view(torch.int32).view(self.H, self.W)
+
+    # ---- route demand (include/trafficsim_demand.h) ---------------------------------------------------
+    def _dm_fn(self, name: str):
+        """The route-demand entries, bound on first use: the CPU oracle shares this class and has none of them."""
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no route demand")
+        fn.restype = C.c_int
+        fn.argtypes = {"demand_compute": [C.c_void_p, C.POINTER(TsDemandQuery), C.POINTER(TsDemandInfo)],
+                       "demand_info": [C.c_void_p, C.POINTER(TsDemandInfo)],
+                       "demand_download": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+                       "demand_pooled": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+                       "demand_groups": [C.c_void_p, C.c_void_p],
+                       "demand_device": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
+                       "demand_release": [C.c_void_p]}[name]
+        return fn
+
+    @property
+    def has_demand(self) -> bool:
+        return self.prefix == "ts_" and hasattr(self.lib, "ts_demand_compute")
+
+    @staticmethod
+    def _dm_info(info: TsDemandInfo) -> dict:
+        return {"n_bins": int(info.n_bins), "bin_cells": int(info.bin_cells), "open_tail": bool(info.open_tail),
+                "selected": bool(info.selected), "width": int(info.width), "height": int(info.height), "tick": int(info.tick),
+                "vehicles": int(info.vehicles), "steps": int(info.steps),
+                "bin_steps": [int(info.bin_steps[b]) for b in range(int(info.n_bins))], "device_bytes": int(info.device_bytes)}
+
+    @staticmethod
+    def _dm_dir(dir) -> int:
+        if dir is None:
+            return -1
+        if isinstance(dir, str):
+            if dir.upper() not in ("N", "E", "S", "W"):
+                raise ValueError(f"unknown direction {dir!r} (one of N, E, S, W)")
+            return "NESW".index(dir.upper())
+        return int(dir)
+
+    def demand_compute(self, n_bins: int = 1, bin_cells: int = 1, open_tail: bool = True, select=None) -> dict:
+        """Count the remaining main path of every live vehicle (or of those whose byte in `select`, indexed by spawn index, is
+        not 0) into [bin][direction] planes on the device: step k of a path goes to bin k // bin_cells, steps beyond the last
+        bin to the last one (`open_tail`) or nowhere.  `select`: a numpy array, or a uint8 torch tensor on the engine's device
+        (read there, no copy).  Returns demand_info()."""
+        fn = self._dm_fn("demand_compute")
+        q = TsDemandQuery(n_bins=int(n_bins), bin_cells=int(bin_cells), open_tail=int(bool(open_tail)))
+        keep = None
+        if select is not None:
+            if hasattr(select, "data_ptr"):
+                import torch
+                if select.dtype != torch.uint8 or not select.is_cuda or not select.is_contiguous() or select.dim() != 1:
+                    raise ValueError("demand_compute: a tensor select is 1-d contiguous uint8 on the engine's device")
+                torch.cuda.current_stream(select.device).synchronize()
+                keep = select
+                q.select, q.n_select, q.select_on_device = select.data_ptr() or None, int(select.numel()), 1
+            else:
+                sel = np.ascontiguousarray(np.asarray(select).reshape(-1) != 0, dtype=np.uint8)
+                keep = sel if sel.size else np.zeros(1, dtype=np.uint8)   # (an empty mask still reaches the length check)
+                q.select, q.n_select = keep.ctypes.data, int(sel.size)
+        info = TsDemandInfo()
+        self._chk(fn(self.h, C.byref(q), C.byref(info)))
+        del keep
+        return self._dm_info(info)
+
+    def demand_info(self) -> dict:
+        """{"n_bins", "bin_cells", "open_tail", "selected", "width", "height", "tick", "vehicles", "steps", "bin_steps",
+        "device_bytes"} of the result held; n_bins 0 when there is none."""
+        info = TsDemandInfo()
+        self._chk(self._dm_fn("demand_info")(self.h, C.byref(info)))
+        return self._dm_info(info)
+
+    def demand_plane(self, bin: int = 0, dir=None) -> np.ndarray:
+        """One plane as an (H, W) uint32 array; dir 0..3 or "N" / "E" / "S" / "W", None: the sum of the four (added on the
+        device)."""
+        out = np.zeros((self.H, self.W), dtype=np.uint32)
+        self._chk(self._dm_fn("demand_download")(self.h, int(bin), self._dm_dir(dir), out.ctypes.data))
+        return out
+
+    def demand_pooled(self, factor: int, bin: int = 0, dir=None) -> np.ndarray:
+        """The plane summed over factor x factor blocks on the device: (ceil(H / factor), ceil(W / factor)) uint64."""
+        fn = self._dm_fn("demand_pooled")
+        f = int(factor)
+        out = np.zeros((-(-self.H // f), -(-self.W // f)) if f >= 1 else (1, 1), dtype=np.uint64)
+        self._chk(fn(self.h, int(bin), self._dm_dir(dir), max(min(f, 0x7FFFFFFF), -1), out.ctypes.data))
+        return out
+
+    def demand_groups(self) -> np.ndarray:
+        """[G][n_bins][DG_FIELDS] int64: the direction-summed plane over every light group's ns_in / ew_in approach cells,
+        the four direction planes over its intersection cells."""
+        fn = self._dm_fn("demand_groups")
+        n, bins = self._chk(self._f("num_groups")(self.h)), self.demand_info()["n_bins"]
+        out = np.zeros((max(n, 1), max(bins, 1), len(DG_FIELDS)), dtype=np.int64)
+        self._chk(fn(self.h, out.ctypes.data))
+        return out[:n, :bins]
+
+    def demand_device(self, bin: int = 0, dir=0, device=None):
+        """A direction plane as an (H, W) int32 torch tensor over the engine's own device memory (no copy; the bits are the
+        plane's uint32 counts; valid until the next demand_compute, demand_release or close).  torch must have been imported
+        before the engine library was loaded, as for observe_device."""
+        fn = self._dm_fn("demand_device")
+        try:
+            import torch
+        except ImportError as ex:
+            raise RuntimeError("demand_device needs torch (use demand_plane for a host array)") from ex
+        ptr = C.c_void_p()
+        self._chk(fn(self.h, int(bin), self._dm_dir(dir), C.byref(ptr)))
+        from .dist import ShardedReplans
+        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        try:
+            t = ShardedReplans._wrap_device(ptr.value, self.W * self.H * 4, device)
+        except RuntimeError as ex:
+            raise RuntimeError("demand_device: torch cannot reach the engine's device - import torch before the engine "
+                               "library is loaded, or download with demand_plane") from ex
+        return t.view(torch.int32).view(self.H, self.W)
+
+    def demand_release(self):
+        """Free the planes; there is no result afterwards."""
+        self._chk(self._dm_fn("demand_release")(self.h))
 
     # ---- trip log (include/trafficsim_triplog.h) ----------------------------------------------------
     def _tl_fn(self, name: str):

@@ -42,6 +42,7 @@
 #include "astar_quad.h"
 #include "astar_batch.h"
 #include "observe.h"
+#include "demand.h"
 #include "triplog.h"
 #include "kernels.h"
 #include "lights_ext.h"
@@ -2195,3 +2196,4 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
 #include "lights_ext_api.h"
 #include "lights_proto_api.h"
 #include "render_api.h"
+#include "demand_api.h"

@@ -1049,6 +1049,51 @@ class CityModel:
                         "throughput": sum(by_dir.values()), "throughput_by_direction": by_dir})
         return out
 
+    # ---- route demand (include/trafficsim_demand.h) ---------------------------------------------------
+    def _demand_compute(self, bins, bin_cells, open_tail, vehicles) -> dict:
+        self._flush_host_writes()
+        select = None
+        if vehicles is not None:
+            select = np.zeros(self.engine.num_spawned(), dtype=np.uint8)
+            idx = np.asarray([v._spawn_idx if hasattr(v, "_spawn_idx") else int(v) for v in vehicles], dtype=np.int64)
+            if len(idx) and (idx.min() < 0 or idx.max() >= len(select)):
+                raise ValueError("planned_load: a vehicle is not a spawn index handed out so far")
+            select[idx] = 1
+        return self.engine.demand_compute(bins, bin_cells, open_tail, select)
+
+    def planned_load(self, bins: int = 1, bin_cells: int = 1, open_tail: bool = True, vehicles=None, pooled=None) -> dict:
+        """Where traffic is going: the remaining main path of every live vehicle (or of `vehicles`: vehicle agents or spawn
+        indices) counted per cell on the device.  Step k of a path (k = 0: the vehicle's next cell) goes to bin k // bin_cells;
+        steps beyond the last bin go to the last one (`open_tail`) or are left out.  Returns {"load": (bins, H, W) uint32 (uint64,
+        (bins, ceil(H / pooled), ceil(W / pooled)), with `pooled`: sums over pooled x pooled blocks), "by_direction":
+        (bins, 4, H, W) by the direction N E S W of the step into the cell} and the fields of `engine.demand_info()`.  A snapshot
+        of the state between two steps: not updated by step() and not carried by save / load / deepcopy / pickle."""
+        info = self._demand_compute(bins, bin_cells, open_tail, vehicles)
+        eng, nb = self.engine, info["n_bins"]
+        if pooled is None:
+            load = np.stack([eng.demand_plane(b) for b in range(nb)])
+            by_dir = np.stack([np.stack([eng.demand_plane(b, d) for d in range(4)]) for b in range(nb)])
+        else:
+            load = np.stack([eng.demand_pooled(pooled, b) for b in range(nb)])
+            by_dir = np.stack([np.stack([eng.demand_pooled(pooled, b, d) for d in range(4)]) for b in range(nb)])
+        return dict(info, load=load, by_direction=by_dir)
+
+    def intersection_demand(self, bins: int = 1, bin_cells: int = 1, open_tail: bool = True, vehicles=None) -> List[dict]:
+        """Per light group, keyed like intersection_report(): the planned entries into its N-S and W-E approach cells and into
+        the intersection's cells (in all and by direction), one number per bin (lists of `bins` ints)."""
+        info = self._demand_compute(bins, bin_cells, open_tail, vehicles)
+        rows = self.engine.demand_groups()
+        f = capi.DG_FIELDS.index
+        out = []
+        for g, r in enumerate(rows):
+            by_dir = {d: [int(v) for v in r[:, f("enter_" + d.lower())]] for d in "NESW"}
+            out.append({"group": self.intersection_light_groups[g].id if g < len(self.intersection_light_groups) else g,
+                        "index": g, "tick": info["tick"], "bins": info["n_bins"], "bin_cells": info["bin_cells"],
+                        "planned_ns": [int(v) for v in r[:, f("ns_in")]], "planned_ew": [int(v) for v in r[:, f("ew_in")]],
+                        "planned_throughput": [sum(by_dir[d][b] for d in "NESW") for b in range(info["n_bins"])],
+                        "planned_throughput_by_direction": by_dir})
+        return out
+
     # ---- getters used by the UI (city_model.py:1965-2149) ------------------------------------------
     # ---- device renderer (include/trafficsim_render.h) ---------------------------------------------------
     def _render_defaults(self):
