@@ -1,0 +1,271 @@
+"""Every device extension switched on next to one trace replay, and one bundle of their outputs per check tick.
+
+`Sidecar(api, tr)` turns on observation (all seven planes), the trip log, the renderer (tables, palettes, heat LUT, a route
+list) on an engine that was set up from trace `tr`; `Sidecar.check(t)`, called after tick t, asserts the rules that need
+nothing but the engine's own downloads and the trace (paths against the rows' CRCs, demand against download_path, the route
+layer against download_path, observation growth against the rows, the trip log against the rows) and returns a bundle: a
+dict of numpy arrays holding every output.  The simulation state of a trace replay is the reference's whichever way the
+engine computes it (other searcher, other build, collected pool, sharded ranks), so the bundles of two replays of one trace
+are equal byte for byte - `assert_same_bundles`.  tests/test_gpu_ext_paths.py runs the matrix.
+
+No pytest in here: the worker scripts of the sharded runs import this module.  `check_query` and `read_planes` are the route
+demand checks of tests/test_gpu_demand.py, which imports them back."""
+import numpy as np
+
+from tests import demand_expect as de
+from tests import observe_util as ou
+from tests import render_expect as rx
+from tests import triplog_util as tu
+from tests.trace_util import replay_and_compare
+from trafficsimulation_amd import _capi as capi
+from trafficsimulation_amd import render as rn
+
+V = ou.V
+SAMPLED, ENTER = slice(0, 3), slice(3, 7)
+DEMAND_QUERIES = [(1, 1, 1), (4, 16, 1)]
+ROUTE_RGBA = (1, 2, 3, 255)            # weight 255: a route cell is exactly this colour
+BG = (17, 34, 51, 0)
+CHECK_EVERY = 10
+GC_MIN_CELLS = 17                      # cells driven since a path was written: a collection has dropped its first word
+
+
+def read_planes(api, n_bins):
+    return np.stack([np.stack([api.demand_plane(b, d) for d in range(4)]) for b in range(n_bins)])
+
+
+def check_query(api, tr, veh, query, ctx, tick):
+    """One compute of `query` against the numpy rule on `veh`: every plane, the direction sums, pooled reads, the group rows
+    and the totals."""
+    n_bins, bin_cells, open_tail = query
+    H, W = int(tr["height"]), int(tr["width"])
+    want = de.planes(H, W, veh, n_bins, bin_cells, bool(open_tail))
+    info = api.demand_compute(n_bins, bin_cells, bool(open_tail))
+    ctx = f"{ctx}, query {query}"
+    assert info == api.demand_info(), ctx
+    assert (info["n_bins"], info["bin_cells"], info["open_tail"], info["selected"]) == (n_bins, bin_cells, bool(open_tail), False), ctx
+    assert (info["width"], info["height"], info["tick"], info["vehicles"]) == (W, H, tick, len(veh)), ctx
+    assert info["device_bytes"] == n_bins * 4 * H * W * 4, ctx
+    got = read_planes(api, n_bins)
+    assert np.array_equal(got, want), f"{ctx}: planes differ at [bin, dir, y, x] {np.argwhere(got != want)[:4].tolist()}"
+    assert info["bin_steps"] == [int(want[b].sum()) for b in range(n_bins)] and info["steps"] == int(want.sum()), ctx
+    for b in range(n_bins):
+        assert np.array_equal(api.demand_plane(b), want[b].sum(axis=0, dtype=np.uint32)), f"{ctx}: bin {b}, the sum of the directions"
+    for f in (1, 7, 64):
+        b = n_bins - 1
+        assert np.array_equal(api.demand_pooled(f, b), ou.pooled(want[b].sum(axis=0, dtype=np.uint32), f)), f"{ctx}: pooled by {f}"
+        assert np.array_equal(api.demand_pooled(f, 0, "E"), ou.pooled(want[0, 1], f)), f"{ctx}: E plane pooled by {f}"
+    assert np.array_equal(api.demand_groups(), de.group_rows(tr, want)), f"{ctx}: group rows"
+
+
+# ---- what the fixtures alone decide (checked on the CPU by tests/test_ext_sidecar.py) ------------------------------------
+def ticks_of(tr):
+    """The ticks a mode replays: the whole trace where it has at most 80, otherwise the first 60."""
+    T = ou.n_ticks(tr)
+    return T if T <= 80 else 60
+
+
+def check_ticks(T):
+    """After every 10th tick and after the last."""
+    return [t for t in range(T) if t % CHECK_EVERY == CHECK_EVERY - 1 or t == T - 1]
+
+
+def spawned_by(tr, t):
+    """Vehicles placed up to and including tick t, as far as the rows show them (spawn indices are handed out in order)."""
+    n0 = len(tr["v_start_xy"])
+    rows = tr["veh_rows"][:tr["veh_off"][t + 1]]
+    return max(n0, int(rows[:, V["spawn_idx"]].max()) + 1 if len(rows) else 0)
+
+
+def first_parked_tick(tr):
+    """The first tick after which a row carries F_PARKED (a service vehicle standing at its block), or None."""
+    for t in range(ou.n_ticks(tr)):
+        if ((ou.rows_at(tr, t)[:, V["flags"]] & capi.F_PARKED) != 0).any():
+            return t
+    return None
+
+
+def generator_ticks(tr):
+    """(T, vehicles spawned by T, first tick with a parked vehicle): T is the smallest multiple of 10 by which the rows show
+    more than twice the initial population spawned and a parked service vehicle; None where the trace never gets there."""
+    n0, parked = len(tr["v_start_xy"]), first_parked_tick(tr)
+    if parked is None:
+        return None
+    for T in range(CHECK_EVERY, ou.n_ticks(tr) + 1, CHECK_EVERY):
+        if spawned_by(tr, T - 1) > 2 * n0 and parked < T:
+            return T, spawned_by(tr, T - 1), parked
+    return None
+
+
+def since_written(tr, ticks):
+    """{check tick: the most cells a vehicle alive after it has driven since its path was last written}, from the rows alone.
+    A trace without searches (astar_per_tick is 0 throughout): every path was written at spawn, so that is steps_traveled.
+    A trace with searches: every path computation resets the vehicle's cooldown to PATHFINDING_COOLDOWN
+    (ou.keeps_its_path), so a row whose cooldown is not that value after a tick kept its path through the tick; a row that
+    carries it counts as rewritten there (a lower bound).  17 cells or more: under a collection per tick the path has lost
+    its first word and path_cur stands inside a word."""
+    searches = int(np.sum(tr["astar_per_tick"])) > 0
+    pc = ou.cooldown_param(tr)
+    written = {}
+    out = {}
+    due = set(check_ticks(ticks))
+    for t in range(ticks):
+        rows = ou.rows_at(tr, t)
+        for r in rows:
+            v, s = int(r[V["spawn_idx"]]), int(r[V["steps_traveled"]])
+            if v not in written:
+                written[v] = 0
+            if searches and int(r[V["cooldown"]]) == pc:
+                written[v] = s
+        if t in due and len(rows):
+            out[t] = max(int(r[V["steps_traveled"]]) - written[int(r[V["spawn_idx"]])] for r in rows)
+    return out
+
+
+def light_fixtures_with_searches(names):
+    """The light-control fixtures in whose recorded run searches ran inside ticks."""
+    from trafficsimulation_amd.world import load_trace
+    from tests.trace_util import trace_path
+    return [n for n in names if int(np.sum(load_trace(trace_path(n))["astar_per_tick"])) > 0]
+
+
+def replay_tick(api, tr, t):
+    """trace_util.replay_and_compare over the one tick t (the slice of the trace as a trace of its own)."""
+    sub = dict(tr)
+    for k in ("occ_t", "stop_t", "stuck_t", "rain_t", "grp_rows", "nsched_t", "rng_rows", "cnt_rows", "blk_rows"):
+        if k in sub:
+            sub[k] = tr[k][t:t + 1]
+    off = np.asarray(tr["veh_off"])
+    sub["veh_rows"], sub["veh_off"] = tr["veh_rows"][off[t]:off[t + 1]], off[t:t + 2] - off[t]
+    sub.pop("raised_at_tick", None)
+    assert replay_and_compare(api, sub, ticks=1) == 1
+
+
+def type_tables(tables):
+    """(type plane, cell palette) of a world: from its cell_type_map, or the facade's fallback where the trace has none."""
+    if "cell_type_map" in tables:
+        return rn.type_plane(tables["cell_type_map"], tables.get("cell_base_type_map")), rn.cell_palette()
+    plane = rn.fallback_type_plane(tables["is_road_map"], tables["intersection_map"], tables["light_ctrl_xy"], tables["light_xy"])
+    return plane, rn.cell_palette(type_names=rn.fallback_type_names())
+
+
+class Sidecar:
+    def __init__(self, api, tr, tables=None, fixture_paths=False):
+        """`api` is set up from `tr` and has not stepped.  `tables` (default: the trace) holds the world tables the renderer
+        is configured from.  fixture_paths: the trace's vehicles keep their spawn-time paths (explicit paths, no search):
+        demand is held to de.fixture_vehicles instead of download_path."""
+        self.api, self.tr, self.fixture_paths = api, tr, fixture_paths
+        tables = tr if tables is None else tables
+        self.H, self.W = int(tr["height"]), int(tr["width"])
+        api.observe_start()
+        ever = spawned_by(tr, ou.n_ticks(tr) - 1)
+        api.triplog_start(-(-ever // 64) * 64)
+        plane, pal = type_tables(tables)
+        api.render_set_cells(plane, pal)
+        api.render_set_vehicle_palette(rn.vehicle_palette())
+        api.render_set_heat_lut(rn.heat_lut())
+        live = [int(v) for v in api.vehicles()[:, V["spawn_idx"]]]
+        seq = tu.sequence(tr)
+        leaver = [int(seq[0, 1])] if len(seq) and int(seq[0, 1]) in live else []
+        self.routes = sorted(set(live[::3] + leaver))
+        self.leaver = leaver[0] if leaver else None
+        api.render_set_routes(self.routes, ROUTE_RGBA)
+        self.last = -1                                             # the tick of the previous check
+        self.planes = np.zeros((7, self.H, self.W), dtype=np.uint32)
+        self.steps = {v: 0 for v in live}                          # steps_traveled at the previous check
+        self.n_records = 0
+        self.stats = {"checks": 0, "paths": 0}
+
+    def views(self):
+        W, H = self.W, self.H
+        common = dict(layers=capi.RL_ALL, heat_plane="present", heat_max=5, background=BG)
+        return {"full": rn.make_view(cells_w=W, cells_h=H, **common),
+                "shrunk": rn.make_view(cells_w=W, cells_h=H, shrink=4, **common),
+                "window": rn.make_view(x0=(W - 7) | 1, y0=H - 5, cells_w=11, cells_h=9, zoom=3, **common)}
+
+    def check(self, t):
+        api, tr, H, W = self.api, self.tr, self.H, self.W
+        ctx = f"tick {t}"
+        out = {}
+        rows = api.vehicles()
+        # paths: download_path is the path the row's CRC and length speak of
+        paths = [api.path(k) for k in range(len(rows))]
+        for k, r in enumerate(rows):
+            assert len(paths[k]) == int(r[V["path_len"]]), f"{ctx}: vehicle {int(r[0])}: {len(paths[k])} cells downloaded, the row has {int(r[V['path_len']])}"
+            crc = capi.path_crc(paths[k]) if len(paths[k]) else 0
+            assert crc == int(r[V["path_crc"]]) & 0xFFFFFFFF, f"{ctx}: vehicle {int(r[0])}: the downloaded path has another CRC than the row"
+        self.stats["paths"] += len(rows)
+        out["path_len"] = np.asarray([len(p) for p in paths], dtype=np.int64)
+        out["path_xy"] = np.concatenate(paths + [np.zeros((0, 2), np.int32)]).astype(np.int32)
+        # demand
+        veh = [(int(r[V["x"]]), int(r[V["y"]]), paths[k]) for k, r in enumerate(rows)]
+        if self.fixture_paths:
+            fveh, _ = de.fixture_vehicles(tr, t)
+            assert len(fveh) == len(veh) and all(a[:2] == b[:2] and np.array_equal(a[2], b[2]) for a, b in zip(veh, fveh)), \
+                f"{ctx}: download_path is not the rest of the spawn-time path"
+            veh = fveh
+        for q in DEMAND_QUERIES:
+            check_query(api, tr, veh, q, ctx, t + 1)
+            info = api.demand_info()
+            out[f"demand_{q[0]}_{q[1]}"] = read_planes(api, q[0])
+            out[f"demand_totals_{q[0]}_{q[1]}"] = np.asarray([info["steps"], info["vehicles"]] + list(info["bin_steps"]), dtype=np.int64)
+            out[f"demand_groups_{q[0]}_{q[1]}"] = api.demand_groups()
+            out[f"demand_pooled7_{q[0]}_{q[1]}"] = api.demand_pooled(7)
+        # routes: the layer alone, over the whole map
+        frame = api.render(rn.make_view(cells_w=W, cells_h=H, layers=capi.RL_ROUTES, background=BG))
+        got = (frame[..., :3] == np.asarray(ROUTE_RGBA[:3], dtype=np.uint8)).all(axis=2)
+        pos_of = {int(s): k for k, s in enumerate(rows[:, V["spawn_idx"]])}
+        want = np.zeros((H, W), dtype=bool)
+        for v in self.routes:
+            if v in pos_of:
+                want |= rx.mask_of(paths[pos_of[v]], H, W)
+        assert np.array_equal(got, want), f"{ctx}: the route layer is not the downloaded paths at (y, x) {np.argwhere(got != want)[:4].tolist()}"
+        out["frame_routes"] = frame
+        for name, view in self.views().items():
+            out[f"frame_{name}"] = api.render(view)
+        # observation
+        planes = ou.read_planes(api)
+        want_s = self.planes[SAMPLED].copy()
+        for u in range(self.last + 1, t + 1):
+            want_s += ou.sampled_delta(tr, u)
+        for k in range(3):
+            assert np.array_equal(planes[k], want_s[k]), f"{ctx}: plane {capi.OBS_PLANES[k]} did not grow by what the rows of ticks {self.last + 1} .. {t} add"
+        rec = api.trips()
+        ended = rec[self.n_records:]
+        now = {int(r[V["spawn_idx"]]): int(r[V["steps_traveled"]]) for r in rows}
+        moved = sum(s - self.steps.get(v, 0) for v, s in now.items())
+        moved += sum(int(r["distance"]) - self.steps.get(int(r["spawn_idx"]), 0) for r in ended)
+        grown = int(planes[ENTER].astype(np.int64).sum()) - int(self.planes[ENTER].astype(np.int64).sum())
+        assert grown == moved, f"{ctx}: the ENTER planes grew by {grown}, steps_traveled and the finished trips by {moved}"
+        out["observe"] = planes
+        # trip log
+        seq = np.stack([rec["end_step"], rec["spawn_idx"]], axis=1).astype(np.int64).reshape(-1, 2)
+        want_seq = tu.sequence(tr, t + 1)
+        assert np.array_equal(seq, want_seq), f"{ctx}: the trip log's (end_step, spawn_idx) is not the rows' sequence"
+        out["trips"] = np.frombuffer(rec.tobytes(), dtype=np.uint8).copy()
+        self.last, self.planes, self.steps, self.n_records = t, planes, now, len(rec)
+        self.stats["checks"] += 1
+        return out
+
+
+def run_trace(api, tr, ticks, sidecar):
+    """Replay ticks [0, ticks) one at a time, every tick against the trace; the bundles of the check ticks, in order."""
+    due = set(check_ticks(ticks))
+    bundles = []
+    for t in range(ticks):
+        replay_tick(api, tr, t)
+        if t in due:
+            bundles.append(sidecar.check(t))
+    return bundles
+
+
+def flatten(bundles):
+    """A list of bundles as one dict for np.savez."""
+    return {f"{i:03d}/{k}": v for i, b in enumerate(bundles) for k, v in b.items()}
+
+
+def assert_same_bundles(got, want, ctx):
+    """Two flattened bundle lists, byte for byte."""
+    assert sorted(got) == sorted(want), f"{ctx}: bundles hold {sorted(set(got) ^ set(want))[:6]} on one side only"
+    for k in sorted(want):
+        a, b = np.asarray(got[k]), np.asarray(want[k])
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"{ctx}: {k} differs from the default mode's"

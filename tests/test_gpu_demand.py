@@ -11,6 +11,7 @@ import pytest
 
 from tests import demand_expect as de
 from tests import observe_util as ou
+from tests.ext_sidecar import check_query, read_planes
 from tests.test_gpu_observe import assert_same_state, engine_for, full_state
 from tests.trace_util import setup_from_trace, trace_path
 from trafficsimulation_amd import _capi as capi
@@ -20,34 +21,6 @@ from trafficsimulation_amd.world import load_trace
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def read_planes(api, n_bins):
-    return np.stack([np.stack([api.demand_plane(b, d) for d in range(4)]) for b in range(n_bins)])
-
-
-def check_query(api, tr, veh, query, ctx, tick):
-    """One compute of `query` against the numpy rule on `veh`: every plane, the direction sums, pooled reads, the group rows
-    and the totals."""
-    n_bins, bin_cells, open_tail = query
-    H, W = int(tr["height"]), int(tr["width"])
-    want = de.planes(H, W, veh, n_bins, bin_cells, bool(open_tail))
-    info = api.demand_compute(n_bins, bin_cells, bool(open_tail))
-    ctx = f"{ctx}, query {query}"
-    assert info == api.demand_info(), ctx
-    assert (info["n_bins"], info["bin_cells"], info["open_tail"], info["selected"]) == (n_bins, bin_cells, bool(open_tail), False), ctx
-    assert (info["width"], info["height"], info["tick"], info["vehicles"]) == (W, H, tick, len(veh)), ctx
-    assert info["device_bytes"] == n_bins * 4 * H * W * 4, ctx
-    got = read_planes(api, n_bins)
-    assert np.array_equal(got, want), f"{ctx}: planes differ at [bin, dir, y, x] {np.argwhere(got != want)[:4].tolist()}"
-    assert info["bin_steps"] == [int(want[b].sum()) for b in range(n_bins)] and info["steps"] == int(want.sum()), ctx
-    for b in range(n_bins):
-        assert np.array_equal(api.demand_plane(b), want[b].sum(axis=0, dtype=np.uint32)), f"{ctx}: bin {b}, the sum of the directions"
-    for f in (1, 7, 64):
-        b = n_bins - 1
-        assert np.array_equal(api.demand_pooled(f, b), ou.pooled(want[b].sum(axis=0, dtype=np.uint32), f)), f"{ctx}: pooled by {f}"
-        assert np.array_equal(api.demand_pooled(f, 0, "E"), ou.pooled(want[0, 1], f)), f"{ctx}: E plane pooled by {f}"
-    assert np.array_equal(api.demand_groups(), de.group_rows(tr, want)), f"{ctx}: group rows"
 
 
 # ---- 1. the fixture expectation, at the default chunk, the smallest and one above the longest path --------------------

@@ -1103,6 +1103,7 @@ int tick(E* e) {
   const TsParams& P = e->P;
   hipStream_t st = e->stream;
   TickState ts;
+  if (getenv("TS_DEBUG_POOL_GC")) TRY(pool_make_room(e, 0));   // (tests: a collection per tick on traces that never replan, too)
   ts.nA = e->n_active; ts.nS = e->n_sched;
   // PATHFINDING_BATCHING=False (vehicle_base.py:669-670): no decide phase - every vehicle runs step_decide at the top of its own
   // step(), in the shuffled order.  Here: the move phase below stops in front of every vehicle (a "point", like the traffic
