@@ -109,14 +109,14 @@ def main():
             api.render_set_cells(type_plane, pal)
             api.render_set_vehicle_palette(vpal)
             ptr = ctypes.c_void_p()
-            dev = api._rn_fn("render_device")
+            dev = api._ext("render_device")
             for name, v in views.items():
                 for _ in range(args.warmup):
                     api._chk(dev(api.h, ctypes.byref(v), ctypes.byref(ptr)))
                 ms[name].append(timed(lambda: api._chk(dev(api.h, ctypes.byref(v), ctypes.byref(ptr))), args.frames))
             full = views["a_full_zoom1_device"]
             host = np.zeros((H, W, 4), dtype=np.uint8)
-            to_host = api._rn_fn("render")
+            to_host = api._ext("render")
             for _ in range(2):
                 api._chk(to_host(api.h, ctypes.byref(full), host.ctypes.data))
             ms["b_full_zoom1_host"].append(timed(lambda: api._chk(to_host(api.h, ctypes.byref(full), host.ctypes.data)), max(3, args.frames // 4)))

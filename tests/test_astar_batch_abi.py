@@ -2,22 +2,17 @@
 oracle-backed CApi - which shares the class and has no batch entry - constructing and refusing it cleanly, and the Python
 operator `pathfinding.astar_hip_batch` (argument handling, result shape, engine cache) against the reference KATs with
 the oracle library behind it."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
+from tests.abi_util import declared, header, hip_lib, oracle_api
 from trafficsimulation_amd import _capi as capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def batch_symbols():
-    src = open(os.path.join(ROOT, "include", "trafficsim_astar_batch.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", src)))
+    return sorted(declared("trafficsim_astar_batch.h"))
 
 
 def test_header_declares_the_batch_entries():
@@ -25,22 +20,13 @@ def test_header_declares_the_batch_entries():
 
 
 def test_batch_entries_stay_out_of_the_main_header():
-    src = open(os.path.join(ROOT, "include", "trafficsim.h")).read()
-    assert "astar_batch" not in re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    assert "astar_batch" not in header("trafficsim.h")
 
 
 def test_hip_library_exports_the_batch_entries():
-    import __graft_entry__ as ge
-    ge.build_hip()
-    from trafficsimulation_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = hip_lib()
     for s in batch_symbols():
         assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
-
-
-def oracle_api():
-    from oracle import pyoracle
-    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
 
 
 def test_oracle_capi_still_constructs_and_refuses_batches():

@@ -1,0 +1,54 @@
+"""The entry table of the ctypes binding (_capi.ENTRIES) against the headers under include/ - a wrong number of argtypes
+corrupts a call without a word - and the one lookup that binds the extension entries."""
+import pytest
+
+from tests.abi_util import declared, hip_lib, oracle_api
+from trafficsimulation_amd import _capi as capi
+
+EXTENSIONS = ["checkpoint", "astar_batch", "observe", "demand", "triplog", "lights_ext", "lights_proto", "render"]
+
+
+def test_the_groups_are_core_the_extension_headers_and_the_hooks():
+    assert sorted(capi.ENTRIES) == sorted(["core", "debug_batch", "debug_quad"] + EXTENSIONS)
+    names = [n for _, entries in capi.ENTRIES.values() for n in entries]
+    assert len(names) == len(set(names)) == len(capi._GROUP_OF)
+    assert set(capi.RESTYPES) <= set(names)
+
+
+@pytest.mark.parametrize("group", EXTENSIONS)
+def test_extension_group_is_its_header(group):
+    want = declared(f"trafficsim_{group}.h")
+    got = capi.ENTRIES[group][1]
+    assert sorted("ts_" + n for n in got) == sorted(want)
+    for n, argtypes in got.items():
+        assert len(argtypes) == want["ts_" + n], n
+
+
+def test_core_entries_are_declared_in_the_main_header():
+    want = declared("trafficsim.h")
+    for n, argtypes in capi.ENTRIES["core"][1].items():
+        assert "ts_" + n in want, n
+        assert len(argtypes) == want["ts_" + n], n
+    assert sorted(set(want) - {"ts_" + n for n in capi.ENTRIES["core"][1]}) == ["ts_profile_count"]     # (takes nothing: unbound)
+
+
+@pytest.mark.parametrize("group", EXTENSIONS + ["debug_batch", "debug_quad"])
+def test_oracle_has_no_entry_of_the_group(group):
+    api = oracle_api()
+    phrase, entries = capi.ENTRIES[group]
+    name = "debug_batch_info" if group == "debug_batch" else sorted(entries)[0]
+    with pytest.raises(capi.EngineError) as ex:
+        api._ext(name)
+    assert ex.value.code == capi.TS_E_UNSUPPORTED
+    assert str(ex.value).endswith(f"tso_{name}: this engine has no {phrase}")
+
+
+def test_an_entry_is_bound_once():
+    api = capi.CApi(hip_lib(), "ts_")
+    fn = api._ext("triplog_read")
+    assert fn.restype is capi.RESTYPES["triplog_read"] and list(fn.argtypes) == capi.ENTRIES["triplog"][1]["triplog_read"]
+    mine = list(fn.argtypes)
+    fn.argtypes = mine
+    again = api._ext("triplog_read")
+    assert again is fn and again.argtypes is mine
+    assert capi.CApi(api.lib, "ts_")._ext("triplog_read").argtypes is mine      # (per function object, not per CApi)

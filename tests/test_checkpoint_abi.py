@@ -1,20 +1,13 @@
 """The checkpoint entries (include/trafficsim_checkpoint.h) without a GPU: the HIP library exports them, and the
 oracle-backed CApi - which shares the class and has no checkpoints - still constructs and refuses them cleanly."""
-import ctypes
-import os
-import re
-
 import pytest
 
+from tests.abi_util import declared, header, hip_lib, oracle_api
 from trafficsimulation_amd import _capi as capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def checkpoint_symbols():
-    src = open(os.path.join(ROOT, "include", "trafficsim_checkpoint.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", src)))
+    return sorted(declared("trafficsim_checkpoint.h"))
 
 
 def test_header_declares_the_checkpoint_entries():
@@ -22,22 +15,13 @@ def test_header_declares_the_checkpoint_entries():
 
 
 def test_checkpoint_entries_stay_out_of_the_main_header():
-    src = open(os.path.join(ROOT, "include", "trafficsim.h")).read()
-    assert "checkpoint" not in re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    assert "checkpoint" not in header("trafficsim.h")
 
 
 def test_hip_library_exports_the_checkpoint_entries():
-    import __graft_entry__ as ge
-    ge.build_hip()
-    from trafficsimulation_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = hip_lib()
     for s in checkpoint_symbols():
         assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
-
-
-def oracle_api():
-    from oracle import pyoracle
-    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
 
 
 def test_oracle_capi_still_constructs():

@@ -223,7 +223,7 @@ def raw_compute(api, **kw):
     q = capi.TsDemandQuery(n_bins=1, bin_cells=1, open_tail=1)
     for k, v in kw.items():
         setattr(q, k, v)
-    return api._dm_fn("demand_compute")(api.h, ctypes.byref(q), None)
+    return api._ext("demand_compute")(api.h, ctypes.byref(q), None)
 
 
 def test_refusals_leave_the_previous_result_alone():
@@ -252,8 +252,8 @@ def test_refusals_leave_the_previous_result_alone():
                dict(select=buf.ctypes.data, n_select=api.num_spawned() + 1), dict(select=buf.ctypes.data, n_select=0)):
         assert raw_compute(api, **kw) == capi.TS_E_INVALID, kw
         assert unchanged(), kw
-    assert api._dm_fn("demand_compute")(api.h, None, None) == capi.TS_E_INVALID and unchanged()
-    dl, pooled, dev = api._dm_fn("demand_download"), api._dm_fn("demand_pooled"), api._dm_fn("demand_device")
+    assert api._ext("demand_compute")(api.h, None, None) == capi.TS_E_INVALID and unchanged()
+    dl, pooled, dev = api._ext("demand_download"), api._ext("demand_pooled"), api._ext("demand_device")
     ptr = ctypes.c_void_p()
     for bin_, dir_ in ((3, 0), (-1, 0), (0, 4), (0, -2)):
         assert dl(api.h, bin_, dir_, buf.ctypes.data) == capi.TS_E_INVALID, (bin_, dir_)
@@ -262,8 +262,8 @@ def test_refusals_leave_the_previous_result_alone():
     assert dev(api.h, 0, -1, ctypes.byref(ptr)) == capi.TS_E_INVALID               # the sum is no plane of the engine's
     assert pooled(api.h, 0, 0, 0, buf.ctypes.data) == capi.TS_E_INVALID and pooled(api.h, 0, 0, -3, buf.ctypes.data) == capi.TS_E_INVALID
     assert dl(api.h, 0, 0, None) == capi.TS_E_INVALID and pooled(api.h, 0, 0, 2, None) == capi.TS_E_INVALID
-    assert dev(api.h, 0, 0, None) == capi.TS_E_INVALID and api._dm_fn("demand_groups")(api.h, None) == capi.TS_E_INVALID
-    assert api._dm_fn("demand_info")(api.h, None) == capi.TS_E_INVALID
+    assert dev(api.h, 0, 0, None) == capi.TS_E_INVALID and api._ext("demand_groups")(api.h, None) == capi.TS_E_INVALID
+    assert api._ext("demand_info")(api.h, None) == capi.TS_E_INVALID
     assert unchanged()
     assert api.demand_pooled(10 ** 6).shape == (1, 1) and int(api.demand_pooled(10 ** 6)[0, 0]) == int(planes[0].sum())
     # a whole-path query with the largest bin: one bin holds everything

@@ -406,13 +406,13 @@ def test_refusals_leave_the_frame_buffer_alone(tmp_path):
     lib, h = api.lib, api.h
     v = to_view(ok)
     import ctypes as C
-    assert api._rn_fn("render")(h, None, frame.ctypes.data) == capi.TS_E_INVALID
-    assert api._rn_fn("render")(h, C.byref(v), None) == capi.TS_E_INVALID
-    assert api._rn_fn("render_device")(h, C.byref(v), None) == capi.TS_E_INVALID
-    assert api._rn_fn("render_set_cells")(h, None, len(s.cell_pal), s.cell_pal.ctypes.data) == capi.TS_E_INVALID
-    assert api._rn_fn("render_set_vehicle_palette")(h, None) == capi.TS_E_INVALID
-    assert api._rn_fn("render_set_heat_lut")(h, None) == capi.TS_E_INVALID
-    assert api._rn_fn("render_info")(h, None) == capi.TS_E_INVALID
+    assert api._ext("render")(h, None, frame.ctypes.data) == capi.TS_E_INVALID
+    assert api._ext("render")(h, C.byref(v), None) == capi.TS_E_INVALID
+    assert api._ext("render_device")(h, C.byref(v), None) == capi.TS_E_INVALID
+    assert api._ext("render_set_cells")(h, None, len(s.cell_pal), s.cell_pal.ctypes.data) == capi.TS_E_INVALID
+    assert api._ext("render_set_vehicle_palette")(h, None) == capi.TS_E_INVALID
+    assert api._ext("render_set_heat_lut")(h, None) == capi.TS_E_INVALID
+    assert api._ext("render_info")(h, None) == capi.TS_E_INVALID
     info = api.render_info()
     assert info["frames"] == frames0 and (info["last_w"], info["last_h"]) == (W, H)
     # the frame buffer still holds the last good frame: a device-side copy of it, read through a second good frame's pointer

@@ -454,11 +454,11 @@ def test_lifecycle_and_errors():
         with pytest.raises(capi.EngineError) as ex:
             call()
         assert ex.value.code == capi.TS_E_INVALID
-    fn = api._tl_fn("triplog_info")
+    fn = api._ext("triplog_info")
     assert fn(api.h, None) == capi.TS_E_INVALID
-    assert api._tl_fn("triplog_device")(api.h, None, None) == capi.TS_E_INVALID
-    assert api._tl_fn("triplog_od")(api.h, 1, None, None, None, None) == capi.TS_E_INVALID
-    assert api._tl_fn("triplog_read")(api.h, 0, 3, None) == capi.TS_E_INVALID
+    assert api._ext("triplog_device")(api.h, None, None) == capi.TS_E_INVALID
+    assert api._ext("triplog_od")(api.h, 1, None, None, None, None) == capi.TS_E_INVALID
+    assert api._ext("triplog_read")(api.h, 0, 3, None) == capi.TS_E_INVALID
     api.step(ou.n_ticks(tr))
     rec = api.trips()
     assert len(rec) > 0 and (rec["spawn_step"] == -1).all()      # (started after the vehicles were placed)

@@ -2,26 +2,20 @@
 structs have the layout the Python binding declares, the algorithm names map to TS_LIGHTS_EXTERNAL, the HIP library exports
 the entries, and the oracle-backed CApi - which shares the class and has no external control - refuses them cleanly."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_util import c_layout, declared, header, hip_lib, oracle_api
 from trafficsimulation_amd import _capi as capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["ts_lights_ext_act", "ts_lights_ext_config", "ts_lights_ext_device", "ts_lights_ext_download", "ts_lights_ext_info",
            "ts_lights_ext_observe", "ts_lights_ext_request", "ts_lights_ext_set_static"]
 
 
-def header(name):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
 def test_header_declares_exactly_the_entries():
-    assert sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", header("trafficsim_lights_ext.h")))) == ENTRIES
+    assert sorted(declared("trafficsim_lights_ext.h")) == ENTRIES
 
 
 def test_algorithm_names():
@@ -39,8 +33,7 @@ def test_algorithm_names():
 
 
 def test_params_accept_the_names_and_refuse_the_other_rl_variants():
-    from oracle import pyoracle
-    api = capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
+    api = oracle_api()
     for name in ("EXTERNAL", "NEIGHBOR_RL_BATCHED"):
         assert api.params_from_defaults({"TRAFFIC_LIGHT_AGENT_ALGORITHM": name}).light_algorithm == 6
     with pytest.raises(capi.EngineError) as ex:
@@ -51,36 +44,17 @@ def test_params_accept_the_names_and_refuse_the_other_rl_variants():
 def test_struct_layouts(tmp_path):
     """sizeof and every offsetof of TsLightsExtInfo and TsLightsExtDevice, as a C compiler sees the header."""
     structs = [("TsLightsExtInfo", capi.TsLightsExtInfo), ("TsLightsExtDevice", capi.TsLightsExtDevice)]
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "trafficsim_lights_ext.h"', 'int main(void) {']
-    for cname, cls in structs:
-        prog.append(f'  printf("%zu\\n", sizeof({cname}));')
-        prog += [f'  printf("%zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
-    prog += ['  return 0;', '}']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run([os.environ.get("CC", "cc"), "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    k = 0
-    for cname, cls in structs:
-        assert out[k] == ctypes.sizeof(cls), cname
-        assert out[k + 1:k + 1 + len(cls._fields_)] == [getattr(cls, f).offset for f, _ in cls._fields_], cname
-        k += 1 + len(cls._fields_)
+    out = c_layout("trafficsim_lights_ext.h", [(cname, [f for f, _ in cls._fields_]) for cname, cls in structs], tmp_path)
+    for (cname, cls), c in zip(structs, out):
+        assert c[0] == ctypes.sizeof(cls), cname
+        assert c[1:] == [getattr(cls, f).offset for f, _ in cls._fields_], cname
     assert ctypes.sizeof(capi.TsLightsExtInfo) == 32 and ctypes.sizeof(capi.TsLightsExtDevice) == 40
 
 
 def test_hip_library_exports_the_entries():
-    import __graft_entry__ as ge
-    ge.build_hip()
-    from trafficsimulation_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = hip_lib()
     for s in ENTRIES:
         assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
-
-
-def oracle_api():
-    from oracle import pyoracle
-    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
 
 
 def test_oracle_capi_has_no_external_control():

@@ -4,24 +4,19 @@ exports the entries, and the oracle-backed CApi - which shares the class and has
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_util import ROOT, c_layout, declared, header, hip_lib, oracle_api
 from trafficsimulation_amd import _capi as capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["ts_lights_proto_act", "ts_lights_proto_act_q", "ts_lights_proto_config", "ts_lights_proto_device",
            "ts_lights_proto_download", "ts_lights_proto_info", "ts_lights_proto_observe"]
 
 
-def header(name):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
 def test_header_declares_exactly_the_entries():
-    assert sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", header("trafficsim_lights_proto.h")))) == ENTRIES
+    assert sorted(declared("trafficsim_lights_proto.h")) == ENTRIES
 
 
 def test_constants_and_names():
@@ -43,36 +38,17 @@ def test_struct_layouts(tmp_path):
     """sizeof and every offsetof of the three structs, as a C compiler sees the header."""
     structs = [("TsLightsProtoConfig", capi.TsLightsProtoConfig), ("TsLightsProtoInfo", capi.TsLightsProtoInfo),
                ("TsLightsProtoDevice", capi.TsLightsProtoDevice)]
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "trafficsim_lights_proto.h"', 'int main(void) {']
-    for cname, cls in structs:
-        prog.append(f'  printf("%zu\\n", sizeof({cname}));')
-        prog += [f'  printf("%zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
-    prog += ['  return 0;', '}']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run([os.environ.get("CC", "cc"), "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    k = 0
-    for cname, cls in structs:
-        assert out[k] == ctypes.sizeof(cls), cname
-        assert out[k + 1:k + 1 + len(cls._fields_)] == [getattr(cls, f).offset for f, _ in cls._fields_], cname
-        k += 1 + len(cls._fields_)
+    out = c_layout("trafficsim_lights_proto.h", [(cname, [f for f, _ in cls._fields_]) for cname, cls in structs], tmp_path)
+    for (cname, cls), c in zip(structs, out):
+        assert c[0] == ctypes.sizeof(cls), cname
+        assert c[1:] == [getattr(cls, f).offset for f, _ in cls._fields_], cname
     assert [ctypes.sizeof(c) for _, c in structs] == [24, 48, 56]
 
 
 def test_hip_library_exports_the_entries():
-    import __graft_entry__ as ge
-    ge.build_hip()
-    from trafficsimulation_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = hip_lib()
     for s in ENTRIES:
         assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
-
-
-def oracle_api():
-    from oracle import pyoracle
-    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
 
 
 @pytest.mark.parametrize("call", ["config", "info", "observe", "act", "act_q", "controller", "device"])

@@ -1,25 +1,19 @@
 """The observation entries (include/trafficsim_observe.h) without a GPU: the header declares exactly them, the HIP library
 exports them, and the oracle-backed CApi - which shares the class and has no observation - still constructs and refuses
 them cleanly."""
-import ctypes
-import os
 import re
 
 import pytest
 
+from tests.abi_util import declared, header, hip_lib, oracle_api
 from trafficsimulation_amd import _capi as capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["ts_observe_device", "ts_observe_download", "ts_observe_groups", "ts_observe_info", "ts_observe_pooled",
            "ts_observe_regions", "ts_observe_reset", "ts_observe_start", "ts_observe_stop"]
 
 
-def header(name):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
 def test_header_declares_exactly_the_observe_entries():
-    assert sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", header("trafficsim_observe.h")))) == ENTRIES
+    assert sorted(declared("trafficsim_observe.h")) == ENTRIES
 
 
 def test_header_constants_match_the_python_names():
@@ -37,17 +31,9 @@ def test_observe_entries_stay_out_of_the_main_header():
 
 
 def test_hip_library_exports_the_observe_entries():
-    import __graft_entry__ as ge
-    ge.build_hip()
-    from trafficsimulation_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = hip_lib()
     for s in ENTRIES:
         assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
-
-
-def oracle_api():
-    from oracle import pyoracle
-    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
 
 
 def test_oracle_capi_constructs_and_has_no_observation():

@@ -2,26 +2,21 @@
 structs match the Python side, the HIP library exports them, ts_render_size does its arithmetic (it takes no handle), and the
 oracle-backed CApi - which shares the class and has no renderer - refuses them cleanly."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
+from tests.abi_util import declared, header, hip_lib, oracle_api, struct_fields
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import render as rn
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["ts_render", "ts_render_device", "ts_render_info", "ts_render_set_cells", "ts_render_set_heat_lut",
            "ts_render_set_routes", "ts_render_set_vehicle_palette", "ts_render_size"]
 
 
-def header(name):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
 def test_header_declares_exactly_the_render_entries():
-    assert sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", header("trafficsim_render.h")))) == ENTRIES
+    assert sorted(declared("trafficsim_render.h")) == ENTRIES
 
 
 def test_header_constants_match_the_python_names():
@@ -37,14 +32,7 @@ def test_header_constants_match_the_python_names():
 
 @pytest.mark.parametrize("struct,cls", [("TsRenderView", capi.TsRenderView), ("TsRenderInfo", capi.TsRenderInfo)])
 def test_structs_match_field_for_field(struct, cls):
-    body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header("trafficsim_render.h"), flags=re.S).group(1)
-    ctype = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
-             "uint8_t": ctypes.c_uint8}
-    want = []
-    for typ, names in re.findall(r"\b(u?int(?:8|32|64)_t)\s+([^;]+);", body):
-        for n in names.split(","):
-            m = re.fullmatch(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*", n)
-            want.append((m.group(1), ctype[typ] * int(m.group(2)) if m.group(2) else ctype[typ]))
+    want = struct_fields("trafficsim_render.h", struct)
     got = [(n, t) for n, t in cls._fields_]
     assert [n for n, _ in got] == [n for n, _ in want]
     for (n, t), (_, w) in zip(got, want):
@@ -54,13 +42,6 @@ def test_structs_match_field_for_field(struct, cls):
 
 def test_render_entries_stay_out_of_the_main_header():
     assert "render" not in header("trafficsim.h") and "TS_RL_" not in header("trafficsim.h")
-
-
-def hip_lib():
-    import __graft_entry__ as ge
-    ge.build_hip()
-    from trafficsimulation_amd._lib import LIB_PATH
-    return ctypes.CDLL(LIB_PATH)
 
 
 def test_hip_library_exports_the_render_entries():
@@ -113,11 +94,6 @@ def test_make_view_defaults_and_layer_names():
     assert rn.make_view().layers == capi.RL_SIGNALS | capi.RL_RAIN | capi.RL_VEHICLES
     with pytest.raises(ValueError):
         capi.render_layer_mask(["clouds"])
-
-
-def oracle_api():
-    from oracle import pyoracle
-    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
 
 
 def test_oracle_capi_constructs_and_has_no_renderer():

@@ -2,27 +2,20 @@
 TRIP_DTYPE's, the enum values are the Python names', the HIP library exports the entries, and the oracle-backed CApi - which
 shares the class and has no trip log - refuses them cleanly."""
 import ctypes
-import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.abi_util import c_layout, declared, header, hip_lib, oracle_api
 from trafficsimulation_amd import _capi as capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["ts_triplog_clear", "ts_triplog_device", "ts_triplog_info", "ts_triplog_od", "ts_triplog_read",
            "ts_triplog_set_zones", "ts_triplog_start", "ts_triplog_stop"]
 
 
-def header(name):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
 def test_header_declares_exactly_the_triplog_entries():
-    assert sorted(set(re.findall(r"\b(ts_[a-z_0-9]+)\s*\(", header("trafficsim_triplog.h")))) == ENTRIES
+    assert sorted(declared("trafficsim_triplog.h")) == ENTRIES
 
 
 def test_enum_values_match_the_python_names():
@@ -38,23 +31,11 @@ def test_record_layout_is_the_dtype(tmp_path):
     """sizeof and every offsetof of TsTripRecord and TsTripLogInfo, as a C compiler sees the header."""
     fields = list(capi.TRIP_DTYPE.names)
     info = [n for n, _ in capi.TsTripLogInfo._fields_]
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "trafficsim_triplog.h"', 'int main(void) {',
-            '  printf("%zu\\n", sizeof(TsTripRecord));']
-    prog += [f'  printf("%zu\\n", offsetof(TsTripRecord, {f}));' for f in fields]
-    prog += ['  printf("%zu\\n", sizeof(TsTripLogInfo));']
-    prog += [f'  printf("%zu\\n", offsetof(TsTripLogInfo, {f}));' for f in info]
-    prog += ['  return 0;', '}']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    cc = os.environ.get("CC", "cc")
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == capi.TRIP_DTYPE.itemsize == 72
-    assert out[1:1 + len(fields)] == [capi.TRIP_DTYPE.fields[f][1] for f in fields]
-    k = 1 + len(fields)
-    assert out[k] == ctypes.sizeof(capi.TsTripLogInfo)
-    assert out[k + 1:] == [getattr(capi.TsTripLogInfo, f).offset for f in info]
+    rec, inf = c_layout("trafficsim_triplog.h", [("TsTripRecord", fields), ("TsTripLogInfo", info)], tmp_path)
+    assert rec[0] == capi.TRIP_DTYPE.itemsize == 72
+    assert rec[1:] == [capi.TRIP_DTYPE.fields[f][1] for f in fields]
+    assert inf[0] == ctypes.sizeof(capi.TsTripLogInfo)
+    assert inf[1:] == [getattr(capi.TsTripLogInfo, f).offset for f in info]
     # 14 int32 then 2 doubles, nothing between
     assert [capi.TRIP_DTYPE.fields[f][0] for f in fields] == [np.dtype(np.int32)] * 14 + [np.dtype(np.float64)] * 2
 
@@ -65,17 +46,9 @@ def test_triplog_stays_out_of_the_main_header():
 
 
 def test_hip_library_exports_the_triplog_entries():
-    import __graft_entry__ as ge
-    ge.build_hip()
-    from trafficsimulation_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = hip_lib()
     for s in ENTRIES:
         assert hasattr(lib, s), f"{s} missing from libtrafficsim_hip.so"
-
-
-def oracle_api():
-    from oracle import pyoracle
-    return capi.CApi(ctypes.CDLL(pyoracle.build()), "tso_")
 
 
 def test_oracle_capi_has_no_trip_log():

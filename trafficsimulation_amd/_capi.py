@@ -315,6 +315,149 @@ class EngineError(RuntimeError):
         self.code = code
 
 
+# ---- the entries (every header under include/, plus the debugging hooks the headers leave out) ----------------------
+# group -> (what an engine without the group "has no", {entry name without the prefix: argtypes}).  "core" is
+# include/trafficsim.h: both libraries export all of it and CApi binds it at construction.  An extension group is
+# include/trafficsim_<group>.h; the CPU oracle has none of those, nor the hooks, so CApi._ext binds them on first use.
+_H, _P, _I32, _I64, _U32, _U64 = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64      # (_H: a ts_handle)
+_PP, _PI32, _PI64, _PU64 = C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+ENTRIES = {
+    "core": (None, {
+        "default_params": [C.POINTER(TsParams)],
+        "last_error": [_H],
+        "create": [C.POINTER(TsWorld), C.POINTER(TsParams), _PP],
+        "destroy": [_H],
+        "num_vehicles": [_H],
+        "num_groups": [_H],
+        "num_scheduled": [_H],
+        "num_blocks": [_H],
+        "num_spawned": [_H],
+        "rain_spawn": [_H],
+        "set_lights": [_H, C.POINTER(TsLightTables)],
+        "schedule_add": [_H, _I32, _I32],
+        "set_traffic_generator": [_H, C.POINTER(TsTrafficTables)],
+        "cached_stats": [_H, C.POINTER(TsCachedStats)],
+        "seed": [_H, _I32, _P, _U32],
+        "seed_int": [_H, _I32, _U64],
+        "rng_state": [_H, _I32, _P, C.POINTER(C.c_uint32)],
+        "add_vehicles": [_H, _I32] + [_P] * 5,
+        "add_vehicles_dirs": [_H, _I32] + [_P] * 5,
+        "remove_vehicle": [_H, _I32, _I32],
+        "upload_map": [_H, _I32, _P],
+        "step": [_H, _I32],
+        "download_map": [_H, _I32, _P],
+        "download_density": [_H, _P],
+        "download_vehicles": [_H, _P, _I32],
+        "download_path": [_H, _I32, _P, _I32],
+        "download_groups": [_H, _P],
+        "download_blocks": [_H, _P],
+        "rain_info": [_H, C.POINTER(TsRainInfo)],
+        "add_service_vehicle": [_H, _I32, _I32, _I32],
+        "group_links": [_H, _I32, _I32],
+        "download_vehicle_meta": [_H, _P, _I32],
+        "download_service_vehicles": [_H, _P, _P, _P, _I32],
+        "counters": [_H, C.POINTER(TsCounters)],
+        "astar": [_H] + [_I32] * 7 + [_P, _I32],
+        "debug_set_occupancy": [_H, _P],
+        "set_device": [_I32],
+        "set_replan_sharding": [_H, _I32, _I32, _P, _P],
+        "set_replan_sharding_device": [_H, _I32, _I32, _P, _P],
+        "profile_enable": [_H, _I32],
+        "profile_name": [_I32],
+        "profile_get": [_H, _I32, C.POINTER(C.c_double), _PI64, _PI64],
+    }),
+    "checkpoint": ("checkpoints", {
+        "checkpoint_size": [_H, _PU64],
+        "checkpoint_save": [_H, _P, _U64, _PU64],
+        "checkpoint_load": [_H, _P, _U64],
+    }),
+    "astar_batch": ("batched pathfinder", {
+        "astar_batch": [_H, _I32, _P, _PI64],
+        "astar_batch_fetch": [_H, _P, _P],
+        "astar_batch_device": [_H, _PP, _PP, _PI32, _PI64],
+    }),
+    "observe": ("traffic observation", {
+        "observe_start": [_H, _U32],
+        "observe_stop": [_H],
+        "observe_reset": [_H],
+        "observe_info": [_H, C.POINTER(TsObserveInfo)],
+        "observe_download": [_H, _I32, _P],
+        "observe_pooled": [_H, _I32, _I32, _P],
+        "observe_regions": [_H, _I32, _I32, _P, _P],
+        "observe_groups": [_H, _P],
+        "observe_device": [_H, _I32, _PP],
+    }),
+    "demand": ("route demand", {
+        "demand_compute": [_H, C.POINTER(TsDemandQuery), C.POINTER(TsDemandInfo)],
+        "demand_info": [_H, C.POINTER(TsDemandInfo)],
+        "demand_download": [_H, _I32, _I32, _P],
+        "demand_pooled": [_H, _I32, _I32, _I32, _P],
+        "demand_groups": [_H, _P],
+        "demand_device": [_H, _I32, _I32, _PP],
+        "demand_release": [_H],
+    }),
+    "triplog": ("trip log", {
+        "triplog_start": [_H, _I64],
+        "triplog_stop": [_H],
+        "triplog_clear": [_H],
+        "triplog_info": [_H, C.POINTER(TsTripLogInfo)],
+        "triplog_read": [_H, _I64, _I64, _P],
+        "triplog_device": [_H, _PP, _PI64],
+        "triplog_set_zones": [_H, _P, _I32],
+        "triplog_od": [_H, _U32, _P, _P, _P, _PU64],
+    }),
+    "lights_ext": ("external light control", {
+        "lights_ext_config": [_H, _I32, _I32],
+        "lights_ext_set_static": [_H, _P, _P],
+        "lights_ext_observe": [_H, _P],
+        "lights_ext_act": [_H, _P, _I32, _P],
+        "lights_ext_request": [_H, _P, _I32],
+        "lights_ext_download": [_H, _P],
+        "lights_ext_device": [_H, C.POINTER(TsLightsExtDevice)],
+        "lights_ext_info": [_H, C.POINTER(TsLightsExtInfo)],
+    }),
+    "lights_proto": ("light protocols", {
+        "lights_proto_config": [_H, C.POINTER(TsLightsProtoConfig)],
+        "lights_proto_observe": [_H, _P, _P],
+        "lights_proto_act": [_H, _P, _I32, _P, _P],
+        "lights_proto_act_q": [_H, _P, _I32, _P, _P, _P],
+        "lights_proto_download": [_H, _P],
+        "lights_proto_device": [_H, C.POINTER(TsLightsProtoDevice)],
+        "lights_proto_info": [_H, C.POINTER(TsLightsProtoInfo)],
+    }),
+    "render": ("renderer", {
+        "render_set_cells": [_H, _P, _I32, _P],
+        "render_set_vehicle_palette": [_H, _P],
+        "render_set_heat_lut": [_H, _P],
+        "render_set_routes": [_H, _I32, _P, _P],
+        "render_size": [C.POINTER(TsRenderView), _PI32, _PI32],
+        "render": [_H, C.POINTER(TsRenderView), _P],
+        "render_device": [_H, C.POINTER(TsRenderView), _PP],
+        "render_info": [_H, C.POINTER(TsRenderInfo)],
+    }),
+    # the hooks are two groups because their refusals name two different things
+    "debug_batch": ("batched pathfinder", {"debug_batch_info": [_H, _P, _I32]}),
+    "debug_quad": ("quad searcher", {"debug_quad_stats": [_H, _P, _I32]}),
+}
+# the entries that do not return an int status
+RESTYPES = {"default_params": None, "last_error": C.c_char_p, "profile_name": C.c_char_p, "triplog_read": C.c_int64}
+_GROUP_OF = {name: group for group, (_, entries) in ENTRIES.items() for name in entries}
+
+
+def _wrap_device(ptr, nbytes, device):
+    """A uint8 torch tensor over `nbytes` of device memory at `ptr` (no copy; the engine owns the memory)."""
+    import torch
+
+    class _Raw:
+        __cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+    return torch.as_tensor(_Raw(), device=device)
+
+
+def _info_dict(info) -> dict:
+    """An info struct field by field: the doubles as float, every other field as int."""
+    return {n: (float if t is C.c_double else int)(getattr(info, n)) for n, t in info._fields_}
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
@@ -345,51 +488,68 @@ class CApi:
         self.lib, self.prefix = lib, prefix
         self.h = C.c_void_p()
         self._keep = []
-        f = self._f
-        f("default_params").restype = None
-        f("last_error").restype = C.c_char_p
-        f("last_error").argtypes = [C.c_void_p]
-        for name in ("destroy", "num_vehicles", "num_groups", "num_scheduled", "num_blocks", "num_spawned", "rain_spawn"):
-            f(name).argtypes = [C.c_void_p]
-        f("create").argtypes = [C.POINTER(TsWorld), C.POINTER(TsParams), C.POINTER(C.c_void_p)]
-        f("set_lights").argtypes = [C.c_void_p, C.POINTER(TsLightTables)]
-        f("schedule_add").argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        f("set_traffic_generator").argtypes = [C.c_void_p, C.POINTER(TsTrafficTables)]
-        f("cached_stats").argtypes = [C.c_void_p, C.POINTER(TsCachedStats)]
-        f("seed").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32]
-        f("seed_int").argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
-        f("rng_state").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint32)]
-        f("add_vehicles").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5
-        f("add_vehicles_dirs").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5
-        f("remove_vehicle").argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        f("upload_map").argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-        f("step").argtypes = [C.c_void_p, C.c_int32]
-        f("download_map").argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-        f("download_density").argtypes = [C.c_void_p, C.c_void_p]
-        f("download_vehicles").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        f("download_path").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
-        f("download_groups").argtypes = [C.c_void_p, C.c_void_p]
-        f("download_blocks").argtypes = [C.c_void_p, C.c_void_p]
-        f("rain_info").argtypes = [C.c_void_p, C.POINTER(TsRainInfo)]
-        f("add_service_vehicle").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        f("group_links").argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        f("download_vehicle_meta").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        f("download_service_vehicles").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-        f("counters").argtypes = [C.c_void_p, C.POINTER(TsCounters)]
-        f("astar").argtypes = [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_int32]
-        f("debug_set_occupancy").argtypes = [C.c_void_p, C.c_void_p]
-        f("set_device").argtypes = [C.c_int32]
-        f("set_replan_sharding").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        if True:
-            f("set_replan_sharding_device").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        f("profile_enable").argtypes = [C.c_void_p, C.c_int32]
-        f("profile_name").restype = C.c_char_p
-        f("profile_name").argtypes = [C.c_int32]
-        f("profile_get").argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                                     C.POINTER(C.c_int64)]
+        for name, argtypes in ENTRIES["core"][1].items():
+            fn = self._f(name)
+            fn.restype, fn.argtypes = RESTYPES.get(name, C.c_int), argtypes
 
     def _f(self, name):
         return getattr(self.lib, self.prefix + name)
+
+    def _ext(self, name: str):
+        """An entry of an extension group or a debugging hook of ENTRIES, bound on first use: the CPU oracle shares this
+        class and has none of them."""
+        phrase, entries = ENTRIES[_GROUP_OF[name]]
+        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
+        if fn is None:
+            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no {phrase}")
+        if fn.argtypes is None:      # (the library hands out one function object per name: bound once, not per call)
+            fn.restype, fn.argtypes = RESTYPES.get(name, C.c_int), entries[name]
+        return fn
+
+    def _has(self, name: str) -> bool:
+        """Whether this engine has the extension group of entry `name`."""
+        return name in _GROUP_OF and self.prefix == "ts_" and hasattr(self.lib, self.prefix + name)
+
+    def _device_view(self, who: str, fallback: str, ptr, dtype: str, shape, device=None):
+        """A torch tensor of `dtype` (a torch dtype's name) and `shape` over the engine's own device memory at `ptr` (no
+        copy), on `device` (default: the device the engine was created on); a fresh empty tensor when the shape holds
+        nothing.  `who` is the calling method and `fallback` its host-side alternative, for the error messages."""
+        try:
+            import torch
+        except ImportError as ex:
+            raise RuntimeError(f"{who} needs torch ({fallback})") from ex
+        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        dt, shape = getattr(torch, dtype), tuple(int(n) for n in shape)
+        count = int(np.prod(shape, dtype=np.int64))
+        if count == 0:
+            return torch.zeros(shape, dtype=dt, device=device)
+        try:
+            raw = _wrap_device(ptr, count * torch.empty(0, dtype=dt).element_size(), device)
+        except RuntimeError as ex:
+            raise RuntimeError(f"{who}: torch cannot reach the engine's device - import torch before the engine library "
+                               f"is loaded, or {fallback}") from ex
+        return raw.view(dt).view(shape)
+
+    def _own_tensor(self, t, what: str, dtype: str, shape) -> bool:
+        """Check a torch tensor the engine is to read in place: contiguous, of `dtype` (a torch dtype's name) and `shape`,
+        and if it is on a GPU, on the engine's - its stream is then waited for (the engine reads on its own stream).
+        Returns whether it is on the device."""
+        import torch
+        if t.dtype != getattr(torch, dtype) or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"{what}: a torch tensor must be contiguous {dtype} of shape {tuple(shape)}")
+        if t.is_cuda:
+            dev = self.debug_batch_info()["device"]
+            if t.device.index != dev:
+                raise ValueError(f"{what}: the tensor is on {t.device}, the engine on cuda:{dev}")
+            torch.cuda.current_stream(t.device).synchronize()
+        return t.is_cuda
+
+    def _pooled_out(self, factor):
+        """(zeroed (ceil(H / factor), ceil(W / factor)) uint64 output, the factor as the int32 the entry takes) of the two
+        pooled downloads; a factor below 1 goes through for the engine to refuse."""
+        f = int(factor)
+        out = np.zeros((-(-self.H // f), -(-self.W // f)) if f >= 1 else (1, 1), dtype=np.uint64)
+        return out, max(min(f, 0x7FFFFFFF), -1)
 
     def _chk(self, rc: int) -> int:
         if rc < 0:
@@ -744,37 +904,22 @@ class CApi:
         """Debugging hook (ts_debug_quad_stats, not part of include/trafficsim.h): the quad searcher's counters over this
         engine's quad passes - entries it took, hand-backs to k_replan in all and by reason, searches started, table-epoch
         wraps, passes, and the sift-down's steps beyond LDS (on the third level fetched ahead / blocking, below it)."""
-        fn = getattr(self.lib, self.prefix + "debug_quad_stats", None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}debug_quad_stats: this engine has no quad searcher")
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        fn = self._ext("debug_quad_stats")
         out = np.zeros(len(self.QUAD_STATS), dtype=np.int64)
         n = self._chk(fn(self.h, out.ctypes.data, len(out)))
         assert n == len(out), f"ts_debug_quad_stats reports {n} counters, this wrapper knows {len(out)}"
         return dict(zip(self.QUAD_STATS, (int(v) for v in out)))
 
     # ---- checkpoints (include/trafficsim_checkpoint.h) ----------------------------------------------
-    def _ckpt_fn(self, name: str):
-        """The checkpoint entries, bound on first use: the CPU oracle shares this class and has none of them."""
-        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no checkpoints")
-        fn.restype = C.c_int
-        fn.argtypes = {"checkpoint_size": [C.c_void_p, C.POINTER(C.c_uint64)],
-                       "checkpoint_save": [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
-                       "checkpoint_load": [C.c_void_p, C.c_void_p, C.c_uint64]}[name]
-        return fn
-
     def checkpoint_size(self) -> int:
         """Exact size in bytes of a checkpoint of the current state."""
         n = C.c_uint64()
-        self._chk(self._ckpt_fn("checkpoint_size")(self.h, C.byref(n)))
+        self._chk(self._ext("checkpoint_size")(self.h, C.byref(n)))
         return n.value
 
     def checkpoint_save(self) -> bytes:
         """Every piece of dynamic state as one canonical blob (between steps only)."""
-        fn = self._ckpt_fn("checkpoint_save")
+        fn = self._ext("checkpoint_save")
         n = self.checkpoint_size()
         buf = np.empty(max(n, 1), dtype=np.uint8)
         got = C.c_uint64()
@@ -783,7 +928,7 @@ class CApi:
 
     def checkpoint_load(self, blob) -> None:
         """Replace all dynamic state with a blob from checkpoint_save of an engine built from the same world."""
-        fn = self._ckpt_fn("checkpoint_load")
+        fn = self._ext("checkpoint_load")
         a = np.frombuffer(bytes(blob) if not isinstance(blob, (bytes, bytearray, np.ndarray)) else blob, dtype=np.uint8)
         a = np.ascontiguousarray(a)
         self._chk(fn(self.h, a.ctypes.data if a.size else None, a.size))
@@ -796,21 +941,10 @@ class CApi:
         return out[:n].copy()
 
     # ---- query batches (include/trafficsim_astar_batch.h) -------------------------------------------
-    def _batch_fn(self, name: str):
-        """The batch entries, bound on first use: the CPU oracle shares this class and answers queries one by one."""
-        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no batched pathfinder")
-        fn.restype = C.c_int
-        fn.argtypes = {"astar_batch": [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)],
-                       "astar_batch_fetch": [C.c_void_p, C.c_void_p, C.c_void_p],
-                       "astar_batch_device": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
-                                              C.POINTER(C.c_int64)]}[name]
-        return fn
-
     @property
     def has_astar_batch(self) -> bool:
-        return self.prefix == "ts_" and hasattr(self.lib, "ts_astar_batch")
+        """(the CPU oracle answers queries one by one)"""
+        return self._has("astar_batch")
 
     @staticmethod
     def astar_queries(queries) -> np.ndarray:
@@ -828,7 +962,7 @@ class CApi:
 
     def astar_batch_run(self, queries) -> int:
         """ts_astar_batch: run the queries, leave the CSR result on the device; returns the total number of path cells."""
-        fn = self._batch_fn("astar_batch")
+        fn = self._ext("astar_batch")
         q = self.astar_queries(queries)
         total = C.c_int64()
         self._chk(fn(self.h, q.shape[0], q.ctypes.data if q.size else None, C.byref(total)))
@@ -836,12 +970,12 @@ class CApi:
 
     def astar_batch_fetch(self):
         """The last batch's result on the host: (off int64[n + 1], xy int32[total, 2])."""
-        dev = self._batch_fn("astar_batch_device")
+        dev = self._ext("astar_batch_device")
         n, total = C.c_int32(), C.c_int64()
         self._chk(dev(self.h, None, None, C.byref(n), C.byref(total)))
         off = np.zeros(n.value + 1, dtype=np.int64)
         xy = np.zeros((total.value, 2), dtype=np.int32)
-        self._chk(self._batch_fn("astar_batch_fetch")(self.h, off.ctypes.data, xy.ctypes.data if total.value else None))
+        self._chk(self._ext("astar_batch_fetch")(self.h, off.ctypes.data, xy.ctypes.data if total.value else None))
         return off, xy
 
     def astar_batch(self, queries):
@@ -852,26 +986,9 @@ class CApi:
         return self.astar_batch_fetch()
 
     # ---- traffic observation (include/trafficsim_observe.h) ------------------------------------------
-    def _obs_fn(self, name: str):
-        """The observation entries, bound on first use: the CPU oracle shares this class and has none of them."""
-        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no traffic observation")
-        fn.restype = C.c_int
-        fn.argtypes = {"observe_start": [C.c_void_p, C.c_uint32],
-                       "observe_stop": [C.c_void_p],
-                       "observe_reset": [C.c_void_p],
-                       "observe_info": [C.c_void_p, C.POINTER(TsObserveInfo)],
-                       "observe_download": [C.c_void_p, C.c_int32, C.c_void_p],
-                       "observe_pooled": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
-                       "observe_regions": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
-                       "observe_groups": [C.c_void_p, C.c_void_p],
-                       "observe_device": [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]}[name]
-        return fn
-
     @property
     def has_observe(self) -> bool:
-        return self.prefix == "ts_" and hasattr(self.lib, "ts_observe_start")
+        return self._has("observe_start")
 
     @staticmethod
     def _obs_plane(name) -> int:
@@ -884,7 +1001,7 @@ class CApi:
     def observe_start(self, planes=None):
         """Allocate and zero the named planes (default: all of OBS_PLANES; names, indices or a ready bit mask) and observe from
         the next tick on.  Starting again re-allocates and zeroes."""
-        fn = self._obs_fn("observe_start")
+        fn = self._ext("observe_start")
         if planes is None:
             mask = (1 << len(OBS_PLANES)) - 1
         elif isinstance(planes, (int, np.integer)):
@@ -898,16 +1015,16 @@ class CApi:
         self._chk(fn(self.h, mask))
 
     def observe_stop(self):
-        self._chk(self._obs_fn("observe_stop")(self.h))
+        self._chk(self._ext("observe_stop")(self.h))
 
     def observe_reset(self):
         """Zero the planes and the tick count."""
-        self._chk(self._obs_fn("observe_reset")(self.h))
+        self._chk(self._ext("observe_reset")(self.h))
 
     def observe_info(self) -> dict:
         """{"planes": names held, "mask", "ticks", "width", "height", "device_bytes"}; no planes when observation is off."""
         info = TsObserveInfo()
-        self._chk(self._obs_fn("observe_info")(self.h, C.byref(info)))
+        self._chk(self._ext("observe_info")(self.h, C.byref(info)))
         return {"planes": [n for k, n in enumerate(OBS_PLANES) if info.plane_mask >> k & 1], "mask": int(info.plane_mask),
                 "ticks": int(info.ticks), "width": int(info.width), "height": int(info.height),
                 "device_bytes": int(info.device_bytes)}
@@ -915,20 +1032,19 @@ class CApi:
     def observe_plane(self, name) -> np.ndarray:
         """One whole plane as an (H, W) uint32 array."""
         out = np.zeros((self.H, self.W), dtype=np.uint32)
-        self._chk(self._obs_fn("observe_download")(self.h, self._obs_plane(name), out.ctypes.data))
+        self._chk(self._ext("observe_download")(self.h, self._obs_plane(name), out.ctypes.data))
         return out
 
     def observe_pooled(self, name, factor: int) -> np.ndarray:
         """The plane summed over factor x factor blocks on the device: (ceil(H / factor), ceil(W / factor)) uint64."""
-        fn = self._obs_fn("observe_pooled")
-        f = int(factor)
-        out = np.zeros((-(-self.H // f), -(-self.W // f)) if f >= 1 else (1, 1), dtype=np.uint64)
-        self._chk(fn(self.h, self._obs_plane(name), max(min(f, 0x7FFFFFFF), -1), out.ctypes.data))
+        fn = self._ext("observe_pooled")
+        out, f = self._pooled_out(factor)
+        self._chk(fn(self.h, self._obs_plane(name), f, out.ctypes.data))
         return out
 
     def observe_regions(self, name, rects) -> np.ndarray:
         """Sums of the plane over rectangles (x0, y0, x1, y1), half-open, clipped to the map: uint64 [n]."""
-        fn = self._obs_fn("observe_regions")
+        fn = self._ext("observe_regions")
         r = np.ascontiguousarray(np.clip(np.asarray(rects, dtype=np.int64).reshape(-1, 4), -0x80000000, 0x7FFFFFFF), dtype=np.int32)
         out = np.zeros(len(r), dtype=np.uint64)
         self._chk(fn(self.h, self._obs_plane(name), len(r), r.ctypes.data if len(r) else None, out.ctypes.data if len(r) else None))
@@ -937,7 +1053,7 @@ class CApi:
     def observe_groups(self) -> np.ndarray:
         """[G][OG_FIELDS] int64: WAITING and PRESENT over every light group's ns_in / ew_in cells, the four ENTER planes
         over its intersection cells."""
-        fn = self._obs_fn("observe_groups")
+        fn = self._ext("observe_groups")
         n = self._chk(self._f("num_groups")(self.h))
         out = np.zeros((max(n, 1), len(OG_FIELDS)), dtype=np.int64)
         self._chk(fn(self.h, out.ctypes.data))
@@ -947,41 +1063,14 @@ class CApi:
         """A plane as an (H, W) int32 torch tensor over the engine's own device memory (no copy; the bits are the plane's
         uint32 counts; valid until observe_stop, the next observe_start or close).  torch must have been imported before the
         engine library was loaded, as for astar_batch_device."""
-        fn = self._obs_fn("observe_device")
-        try:
-            import torch
-        except ImportError as ex:
-            raise RuntimeError("observe_device needs torch (use observe_plane for a host array)") from ex
         ptr = C.c_void_p()
-        self._chk(fn(self.h, self._obs_plane(name), C.byref(ptr)))
-        from .dist import ShardedReplans
-        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
-        try:
-            t = ShardedReplans._wrap_device(ptr.value, self.W * self.H * 4, device)
-        except RuntimeError as ex:
-            raise RuntimeError("observe_device: torch cannot reach the engine's device - import torch before the engine "
-                               "library is loaded, or download with observe_plane") from ex
-        return t.view(torch.int32).view(self.H, self.W)
+        self._chk(self._ext("observe_device")(self.h, self._obs_plane(name), C.byref(ptr)))
+        return self._device_view("observe_device", "use observe_plane for a host array", ptr.value, "int32", (self.H, self.W), device)
 
     # ---- route demand (include/trafficsim_demand.h) ---------------------------------------------------
-    def _dm_fn(self, name: str):
-        """The route-demand entries, bound on first use: the CPU oracle shares this class and has none of them."""
-        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no route demand")
-        fn.restype = C.c_int
-        fn.argtypes = {"demand_compute": [C.c_void_p, C.POINTER(TsDemandQuery), C.POINTER(TsDemandInfo)],
-                       "demand_info": [C.c_void_p, C.POINTER(TsDemandInfo)],
-                       "demand_download": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
-                       "demand_pooled": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
-                       "demand_groups": [C.c_void_p, C.c_void_p],
-                       "demand_device": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
-                       "demand_release": [C.c_void_p]}[name]
-        return fn
-
     @property
     def has_demand(self) -> bool:
-        return self.prefix == "ts_" and hasattr(self.lib, "ts_demand_compute")
+        return self._has("demand_compute")
 
     @staticmethod
     def _dm_info(info: TsDemandInfo) -> dict:
@@ -1005,7 +1094,7 @@ class CApi:
         not 0) into [bin][direction] planes on the device: step k of a path goes to bin k // bin_cells, steps beyond the last
         bin to the last one (`open_tail`) or nowhere.  `select`: a numpy array, or a uint8 torch tensor on the engine's device
         (read there, no copy).  Returns demand_info()."""
-        fn = self._dm_fn("demand_compute")
+        fn = self._ext("demand_compute")
         q = TsDemandQuery(n_bins=int(n_bins), bin_cells=int(bin_cells), open_tail=int(bool(open_tail)))
         keep = None
         if select is not None:
@@ -1029,28 +1118,27 @@ class CApi:
         """{"n_bins", "bin_cells", "open_tail", "selected", "width", "height", "tick", "vehicles", "steps", "bin_steps",
         "device_bytes"} of the result held; n_bins 0 when there is none."""
         info = TsDemandInfo()
-        self._chk(self._dm_fn("demand_info")(self.h, C.byref(info)))
+        self._chk(self._ext("demand_info")(self.h, C.byref(info)))
         return self._dm_info(info)
 
     def demand_plane(self, bin: int = 0, dir=None) -> np.ndarray:
         """One plane as an (H, W) uint32 array; dir 0..3 or "N" / "E" / "S" / "W", None: the sum of the four (added on the
         device)."""
         out = np.zeros((self.H, self.W), dtype=np.uint32)
-        self._chk(self._dm_fn("demand_download")(self.h, int(bin), self._dm_dir(dir), out.ctypes.data))
+        self._chk(self._ext("demand_download")(self.h, int(bin), self._dm_dir(dir), out.ctypes.data))
         return out
 
     def demand_pooled(self, factor: int, bin: int = 0, dir=None) -> np.ndarray:
         """The plane summed over factor x factor blocks on the device: (ceil(H / factor), ceil(W / factor)) uint64."""
-        fn = self._dm_fn("demand_pooled")
-        f = int(factor)
-        out = np.zeros((-(-self.H // f), -(-self.W // f)) if f >= 1 else (1, 1), dtype=np.uint64)
-        self._chk(fn(self.h, int(bin), self._dm_dir(dir), max(min(f, 0x7FFFFFFF), -1), out.ctypes.data))
+        fn = self._ext("demand_pooled")
+        out, f = self._pooled_out(factor)
+        self._chk(fn(self.h, int(bin), self._dm_dir(dir), f, out.ctypes.data))
         return out
 
     def demand_groups(self) -> np.ndarray:
         """[G][n_bins][DG_FIELDS] int64: the direction-summed plane over every light group's ns_in / ew_in approach cells,
         the four direction planes over its intersection cells."""
-        fn = self._dm_fn("demand_groups")
+        fn = self._ext("demand_groups")
         n, bins = self._chk(self._f("num_groups")(self.h)), self.demand_info()["n_bins"]
         out = np.zeros((max(n, 1), max(bins, 1), len(DG_FIELDS)), dtype=np.int64)
         self._chk(fn(self.h, out.ctypes.data))
@@ -1060,70 +1148,42 @@ class CApi:
         """A direction plane as an (H, W) int32 torch tensor over the engine's own device memory (no copy; the bits are the
         plane's uint32 counts; valid until the next demand_compute, demand_release or close).  torch must have been imported
         before the engine library was loaded, as for observe_device."""
-        fn = self._dm_fn("demand_device")
-        try:
-            import torch
-        except ImportError as ex:
-            raise RuntimeError("demand_device needs torch (use demand_plane for a host array)") from ex
         ptr = C.c_void_p()
-        self._chk(fn(self.h, int(bin), self._dm_dir(dir), C.byref(ptr)))
-        from .dist import ShardedReplans
-        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
-        try:
-            t = ShardedReplans._wrap_device(ptr.value, self.W * self.H * 4, device)
-        except RuntimeError as ex:
-            raise RuntimeError("demand_device: torch cannot reach the engine's device - import torch before the engine "
-                               "library is loaded, or download with demand_plane") from ex
-        return t.view(torch.int32).view(self.H, self.W)
+        self._chk(self._ext("demand_device")(self.h, int(bin), self._dm_dir(dir), C.byref(ptr)))
+        return self._device_view("demand_device", "use demand_plane for a host array", ptr.value, "int32", (self.H, self.W), device)
 
     def demand_release(self):
         """Free the planes; there is no result afterwards."""
-        self._chk(self._dm_fn("demand_release")(self.h))
+        self._chk(self._ext("demand_release")(self.h))
 
     # ---- trip log (include/trafficsim_triplog.h) ----------------------------------------------------
-    def _tl_fn(self, name: str):
-        """The trip-log entries, bound on first use: the CPU oracle shares this class and has none of them."""
-        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no trip log")
-        fn.restype = C.c_int64 if name == "triplog_read" else C.c_int
-        fn.argtypes = {"triplog_start": [C.c_void_p, C.c_int64],
-                       "triplog_stop": [C.c_void_p],
-                       "triplog_clear": [C.c_void_p],
-                       "triplog_info": [C.c_void_p, C.POINTER(TsTripLogInfo)],
-                       "triplog_read": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
-                       "triplog_device": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)],
-                       "triplog_set_zones": [C.c_void_p, C.c_void_p, C.c_int32],
-                       "triplog_od": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]}[name]
-        return fn
-
     @property
     def has_triplog(self) -> bool:
-        return self.prefix == "ts_" and hasattr(self.lib, "ts_triplog_start")
+        return self._has("triplog_start")
 
     def triplog_start(self, capacity: int):
         """Allocate a log of `capacity` records and log every vehicle that leaves from now on.  Starting again frees the old
         log: the new one is empty."""
-        self._chk(self._tl_fn("triplog_start")(self.h, max(min(int(capacity), 2 ** 63 - 1), -1)))
+        self._chk(self._ext("triplog_start")(self.h, max(min(int(capacity), 2 ** 63 - 1), -1)))
         self._tl_zones = 0
 
     def triplog_stop(self):
-        self._chk(self._tl_fn("triplog_stop")(self.h))
+        self._chk(self._ext("triplog_stop")(self.h))
         self._tl_zones = 0
 
     def triplog_clear(self):
         """Empty the log; capacity and zone plane stay."""
-        self._chk(self._tl_fn("triplog_clear")(self.h))
+        self._chk(self._ext("triplog_clear")(self.h))
 
     def triplog_info(self) -> dict:
         """{"capacity", "count", "dropped", "groups", "device_bytes"}; all zero when the log is off."""
         info = TsTripLogInfo()
-        self._chk(self._tl_fn("triplog_info")(self.h, C.byref(info)))
-        return {n: int(getattr(info, n)) for n, _ in TsTripLogInfo._fields_}
+        self._chk(self._ext("triplog_info")(self.h, C.byref(info)))
+        return _info_dict(info)
 
     def trips(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Records [first, first + n) of the log (default: all from `first` on) as a TRIP_DTYPE array, in log order."""
-        fn = self._tl_fn("triplog_read")
+        fn = self._ext("triplog_read")
         if n is None:
             n = max(self.triplog_info()["count"] - int(first), 0)
         out = np.zeros(max(int(n), 1), dtype=TRIP_DTYPE)
@@ -1134,27 +1194,14 @@ class CApi:
         """The kept records as a (count, 18) int32 torch tensor over the engine's own device memory (no copy; a record is 18
         words: the 14 int32 fields, then the two doubles as word pairs; valid until triplog_stop, the next triplog_start or
         close).  torch must have been imported before the engine library was loaded, as for observe_device."""
-        fn = self._tl_fn("triplog_device")
-        try:
-            import torch
-        except ImportError as ex:
-            raise RuntimeError("triplog_device needs torch (use trips for a host array)") from ex
         ptr, count = C.c_void_p(), C.c_int64()
-        self._chk(fn(self.h, C.byref(ptr), C.byref(count)))
-        from .dist import ShardedReplans
-        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
-        if count.value == 0:
-            return torch.zeros((0, 18), dtype=torch.int32, device=device)
-        try:
-            t = ShardedReplans._wrap_device(ptr.value, count.value * TRIP_DTYPE.itemsize, device)
-        except RuntimeError as ex:
-            raise RuntimeError("triplog_device: torch cannot reach the engine's device - import torch before the engine "
-                               "library is loaded, or download with trips") from ex
-        return t.view(torch.int32).view(-1, 18)
+        self._chk(self._ext("triplog_device")(self.h, C.byref(ptr), C.byref(count)))
+        return self._device_view("triplog_device", "use trips for a host array", ptr.value, "int32",
+                                 (count.value, TRIP_DTYPE.itemsize // 4), device)
 
     def triplog_set_zones(self, zone_of_cell, n_zones: int):
         """One (H, W) int32 plane: the zone 0 .. n_zones - 1 of every cell, -1 = none.  n_zones = 0 drops the plane."""
-        fn = self._tl_fn("triplog_set_zones")
+        fn = self._ext("triplog_set_zones")
         z = None
         if zone_of_cell is not None:
             z = np.ascontiguousarray(zone_of_cell, dtype=np.int32)
@@ -1180,7 +1227,7 @@ class CApi:
         """Origin / destination sums over the records whose end reason is in `reasons` (names, a bit mask, default all),
         reduced on the device: {"count" uint64, "duration" float64, "distance" uint64} as (n_zones, n_zones) arrays indexed
         [zone(origin), zone(dest)] (a matrix switched off is left out), and "unzoned"."""
-        fn = self._tl_fn("triplog_od")
+        fn = self._ext("triplog_od")
         nz = getattr(self, "_tl_zones", 0)
         out = {}
         if count:
@@ -1199,33 +1246,17 @@ class CApi:
         return out
 
     # ---- external light control (include/trafficsim_lights_ext.h) ------------------------------------
-    def _le_fn(self, name: str):
-        """The external-control entries, bound on first use: the CPU oracle shares this class and has none of them."""
-        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no external light control")
-        fn.restype = C.c_int
-        fn.argtypes = {"lights_ext_config": [C.c_void_p, C.c_int32, C.c_int32],
-                       "lights_ext_set_static": [C.c_void_p, C.c_void_p, C.c_void_p],
-                       "lights_ext_observe": [C.c_void_p, C.c_void_p],
-                       "lights_ext_act": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
-                       "lights_ext_request": [C.c_void_p, C.c_void_p, C.c_int32],
-                       "lights_ext_download": [C.c_void_p, C.c_void_p],
-                       "lights_ext_device": [C.c_void_p, C.POINTER(TsLightsExtDevice)],
-                       "lights_ext_info": [C.c_void_p, C.POINTER(TsLightsExtInfo)]}[name]
-        return fn
-
     @property
     def has_lights_ext(self) -> bool:
-        return self.prefix == "ts_" and hasattr(self.lib, "ts_lights_ext_observe")
+        return self._has("lights_ext_observe")
 
     def lights_config(self, state_dim: int = 13, min_green: int = 5):
         """SRL_INPUT_DIMENSIONS (7, 11, 13, 17 or 19) and SRL_MIN_GREEN; only before the first control call."""
-        self._chk(self._le_fn("lights_ext_config")(self.h, int(state_dim), int(min_green)))
+        self._chk(self._ext("lights_ext_config")(self.h, int(state_dim), int(min_green)))
 
     def lights_set_static(self, intersection_size=None, penalty_score=None):
         """The two static features of every group as float64 [G] (None = leave); only before the first control call."""
-        fn = self._le_fn("lights_ext_set_static")
+        fn = self._ext("lights_ext_set_static")
         a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (intersection_size, penalty_score)]
         for v in a:
             if v is not None and v.shape != (self.n_groups,):
@@ -1235,13 +1266,13 @@ class CApi:
     def lights_info(self) -> dict:
         """{"state_dim", "min_green", "n_groups", "observed", "calls", "device_bytes"}"""
         info = TsLightsExtInfo()
-        self._chk(self._le_fn("lights_ext_info")(self.h, C.byref(info)))
-        return {n: int(getattr(info, n)) for n, _ in TsLightsExtInfo._fields_}
+        self._chk(self._ext("lights_ext_info")(self.h, C.byref(info)))
+        return _info_dict(info)
 
     def lights_observe(self, to_host: bool = True):
         """Phase A: the state vector of every group, (G, state_dim) float32.  A second call before the next lights_act or
         step returns the same (cached) vector.  to_host=False only runs it (the vector is in lights_device()["state"])."""
-        fn = self._le_fn("lights_ext_observe")
+        fn = self._ext("lights_ext_observe")
         if not to_host:
             self._chk(fn(self.h, None))
             return None
@@ -1254,14 +1285,7 @@ class CApi:
         """An int8 vector of one entry per group as (pointer, on_device, keep-alive): numpy / sequences on the host, a torch
         tensor on the engine's device as it is."""
         if type(v).__module__.split(".")[0] == "torch":
-            import torch
-            if v.dtype != torch.int8 or v.dim() != 1 or v.shape[0] != self.n_groups or not v.is_contiguous():
-                raise ValueError(f"{what}: a torch tensor must be contiguous int8 of shape ({self.n_groups},)")
-            if v.is_cuda:
-                dev = self.debug_batch_info()["device"]
-                if v.device.index != dev:
-                    raise ValueError(f"{what}: the tensor is on {v.device}, the engine on cuda:{dev}")
-                torch.cuda.current_stream(v.device).synchronize()   # (the engine reads it on its own stream)
+            if self._own_tensor(v, what, "int8", (self.n_groups,)):
                 return v.data_ptr(), 1, v
             v = v.numpy()
         a = np.ascontiguousarray(np.clip(np.asarray(v, dtype=np.int64), -128, 127), dtype=np.int8)
@@ -1273,7 +1297,7 @@ class CApi:
         """Phase B with one action (0 keep, 1 switch) per group - numpy, a sequence, or an int8 torch tensor on the engine's
         device (read there, no copy).  Runs phase A first if lights_observe has not run since the last step.  Returns the
         next-state vectors (G, state_dim) float32, or None with want_next=False."""
-        fn = self._le_fn("lights_ext_act")
+        fn = self._ext("lights_ext_act")
         ptr, on_dev, keep = self._le_bytes(actions, "actions")
         out = None
         if want_next:
@@ -1285,14 +1309,14 @@ class CApi:
     def lights_request(self, phases):
         """apply_phase(phase) on every group whose entry is 0 or 1; -1 = no request.  For controllers that do not follow the
         observe / act protocol; touches none of its state."""
-        fn = self._le_fn("lights_ext_request")
+        fn = self._ext("lights_ext_request")
         ptr, on_dev, keep = self._le_bytes(phases, "phases")
         self._chk(fn(self.h, ptr, on_dev))
         del keep
 
     def lights_controller(self) -> np.ndarray:
         """(G, 2) int32: _rl_phase, rl_timer of every group."""
-        fn = self._le_fn("lights_ext_download")
+        fn = self._ext("lights_ext_download")
         out = np.zeros((max(self.n_groups, 1), 2), dtype=np.int32)
         self._chk(fn(self.h, out.ctypes.data))
         return out[:self.n_groups]
@@ -1301,61 +1325,30 @@ class CApi:
         """{"state", "next_state": (G, state_dim) float32, "controller", "stored": (G, 2) int32} as torch tensors over the
         engine's own device memory (no copy; valid until close; the engine rewrites them in every control call).  torch must
         have been imported before the engine library was loaded, as for observe_device."""
-        fn = self._le_fn("lights_ext_device")
-        try:
-            import torch
-        except ImportError as ex:
-            raise RuntimeError("lights_device needs torch (use lights_observe / lights_controller for host arrays)") from ex
         d = TsLightsExtDevice()
-        self._chk(fn(self.h, C.byref(d)))
-        from .dist import ShardedReplans
-        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        self._chk(self._ext("lights_ext_device")(self.h, C.byref(d)))
         G, dim = int(d.n_groups), int(d.state_dim)
-        if G == 0:
-            z = lambda w, t: torch.zeros((0, w), dtype=t, device=device)   # noqa: E731
-            return {"state": z(dim, torch.float32), "next_state": z(dim, torch.float32), "controller": z(2, torch.int32), "stored": z(2, torch.int32)}
-        try:
-            wrap = lambda p, n: ShardedReplans._wrap_device(p, n, device)   # noqa: E731
-            out = {"state": wrap(d.state, G * dim * 4).view(torch.float32).view(G, dim),
-                   "next_state": wrap(d.next_state, G * dim * 4).view(torch.float32).view(G, dim),
-                   "controller": wrap(d.controller, G * 8).view(torch.int32).view(G, 2),
-                   "stored": wrap(d.stored, G * 8).view(torch.int32).view(G, 2)}
-        except RuntimeError as ex:
-            raise RuntimeError("lights_device: torch cannot reach the engine's device - import torch before the engine "
-                               "library is loaded, or use lights_observe") from ex
-        return out
+        spec = {"state": (d.state, "float32", (G, dim)), "next_state": (d.next_state, "float32", (G, dim)),
+                "controller": (d.controller, "int32", (G, 2)), "stored": (d.stored, "int32", (G, 2))}
+        return {k: self._device_view("lights_device", "use lights_observe / lights_controller for host arrays", ptr, dt, shape, device)
+                for k, (ptr, dt, shape) in spec.items()}
 
     # ---- A2C / GAT-DQN light protocols (include/trafficsim_lights_proto.h) ------------------------------
-    def _lp_fn(self, name: str):
-        """The protocol entries, bound on first use: the CPU oracle shares this class and has none of them."""
-        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no light protocols")
-        fn.restype = C.c_int
-        fn.argtypes = {"lights_proto_config": [C.c_void_p, C.POINTER(TsLightsProtoConfig)],
-                       "lights_proto_observe": [C.c_void_p, C.c_void_p, C.c_void_p],
-                       "lights_proto_act": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
-                       "lights_proto_act_q": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
-                       "lights_proto_download": [C.c_void_p, C.c_void_p],
-                       "lights_proto_device": [C.c_void_p, C.POINTER(TsLightsProtoDevice)],
-                       "lights_proto_info": [C.c_void_p, C.POINTER(TsLightsProtoInfo)]}[name]
-        return fn
-
     def lights_proto_config(self, protocol, min_green: int = 5, eps_min: float = 0.1, eps_decay: float = 1e-5):
         """Choose the A2C (1, "RL_A2C_BATCHED") or GAT-DQN (2, "GAT_DQN_BATCHED") protocol; once, before the first control call."""
         cfg = TsLightsProtoConfig(int(LIGHT_PROTOCOLS.get(protocol, protocol)), int(min_green), float(eps_min), float(eps_decay))
-        self._chk(self._lp_fn("lights_proto_config")(self.h, C.byref(cfg)))
+        self._chk(self._ext("lights_proto_config")(self.h, C.byref(cfg)))
 
     def lights_proto_info(self) -> dict:
         """{"protocol" (0: none), "min_green", "n_groups", "state_floats", "eps_min", "eps_decay", "calls", "device_bytes"}"""
         info = TsLightsProtoInfo()
-        self._chk(self._lp_fn("lights_proto_info")(self.h, C.byref(info)))
-        return {n: (float if t is C.c_double else int)(getattr(info, n)) for n, t in TsLightsProtoInfo._fields_}
+        self._chk(self._ext("lights_proto_info")(self.h, C.byref(info)))
+        return _info_dict(info)
 
     def lights_proto_observe(self, to_host: bool = True):
         """A2C: the state (G, 13) float32.  GAT: (features (G, 5, 9), mask (G, 5)) float32.  No side effects.
         to_host=False only runs it (nothing comes down; the results are in lights_proto_device()) and returns None."""
-        fn = self._lp_fn("lights_proto_observe")
+        fn = self._ext("lights_proto_observe")
         if not to_host:
             self._chk(fn(self.h, None, None))
             return None
@@ -1371,7 +1364,7 @@ class CApi:
         nothing, leaves epsilon alone.  Returns the rewards (G,) float64 under A2C, (rewards, next features) under GAT
         (want_next=False: the rewards only).  to_host=False: nothing comes down (the results are in lights_proto_device())
         and None is returned."""
-        fn = self._lp_fn("lights_proto_act")
+        fn = self._ext("lights_proto_act")
         ptr, on_dev, keep = self._le_bytes(actions, "actions")
         if not to_host:
             self._chk(fn(self.h, ptr, on_dev, None, None))
@@ -1390,15 +1383,10 @@ class CApi:
         the engine's global stream.  Returns (actions int8, rewards float64, next features); want_next=False leaves the next
         features on the device ((actions, rewards)); to_host=False brings nothing down (actions, rewards and next state are in
         lights_proto_device()) and returns None."""
-        fn = self._lp_fn("lights_proto_act_q")
+        fn = self._ext("lights_proto_act_q")
         keep, on_dev = q, 0
         if type(q).__module__.split(".")[0] == "torch" and q.is_cuda:
-            import torch
-            if q.dtype != torch.float32 or tuple(q.shape) != (self.n_groups, 2) or not q.is_contiguous():
-                raise ValueError(f"q: a torch tensor must be contiguous float32 of shape ({self.n_groups}, 2)")
-            if q.device.index != self.debug_batch_info()["device"]:
-                raise ValueError(f"q: the tensor is on {q.device}, not on the engine's device")
-            torch.cuda.current_stream(q.device).synchronize()
+            self._own_tensor(q, "q", "float32", (self.n_groups, 2))
             ptr, on_dev = q.data_ptr(), 1
         else:
             keep = np.ascontiguousarray(q.numpy() if hasattr(q, "numpy") else q, dtype=np.float32)
@@ -1419,50 +1407,29 @@ class CApi:
     def lights_proto_controller(self) -> np.ndarray:
         """(G,) float64: epsilon of every group (zeros under A2C); _rl_phase / rl_timer are lights_controller()."""
         out = np.zeros(max(self.n_groups, 1), dtype=np.float64)
-        self._chk(self._lp_fn("lights_proto_download")(self.h, out.ctypes.data))
+        self._chk(self._ext("lights_proto_download")(self.h, out.ctypes.data))
         return out[:self.n_groups]
 
     def lights_proto_device(self, device=None) -> dict:
         """{"state", "mask", "next_state", "reward", "actions", "epsilon"} as torch tensors over the engine's own device memory
         (entries the protocol does not have are left out); torch must have been imported before the engine library was loaded."""
-        import torch
         d = TsLightsProtoDevice()
-        self._chk(self._lp_fn("lights_proto_device")(self.h, C.byref(d)))
-        from .dist import ShardedReplans
-        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
+        self._chk(self._ext("lights_proto_device")(self.h, C.byref(d)))
         G = int(d.n_groups)
         gat = int(d.protocol) == LP_GAT
-        spec = {"state": (d.state, torch.float32, (G, 5, 9) if gat else (G, 13)), "reward": (d.reward, torch.float64, (G,)),
-                "actions": (d.actions, torch.int8, (G,))}
+        spec = {"state": (d.state, "float32", (G, 5, 9) if gat else (G, 13)), "reward": (d.reward, "float64", (G,)),
+                "actions": (d.actions, "int8", (G,))}
         if gat:
-            spec.update(mask=(d.mask, torch.float32, (G, 5)), next_state=(d.next_state, torch.float32, (G, 5, 9)),
-                        epsilon=(d.epsilon, torch.float64, (G,)))
-        out = {}
-        for k, (ptr, dt, shape) in spec.items():
-            n = int(np.prod(shape)) * torch.empty(0, dtype=dt).element_size()
-            out[k] = (ShardedReplans._wrap_device(ptr, n, device).view(dt).view(*shape) if G else torch.zeros(shape, dtype=dt, device=device))
-        return out
+            spec.update(mask=(d.mask, "float32", (G, 5)), next_state=(d.next_state, "float32", (G, 5, 9)),
+                        epsilon=(d.epsilon, "float64", (G,)))
+        return {k: self._device_view("lights_proto_device", "use lights_proto_observe / lights_proto_controller for host arrays",
+                                     ptr, dt, shape, device)
+                for k, (ptr, dt, shape) in spec.items()}
 
     # ---- device renderer (include/trafficsim_render.h) ------------------------------------------------
-    def _rn_fn(self, name: str):
-        """The render entries, bound on first use: the CPU oracle shares this class and has none of them."""
-        fn = getattr(self.lib, self.prefix + name, None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}{name}: this engine has no renderer")
-        fn.restype = C.c_int
-        fn.argtypes = {"render_set_cells": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
-                       "render_set_vehicle_palette": [C.c_void_p, C.c_void_p],
-                       "render_set_heat_lut": [C.c_void_p, C.c_void_p],
-                       "render_set_routes": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
-                       "render_size": [C.POINTER(TsRenderView), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
-                       "render": [C.c_void_p, C.POINTER(TsRenderView), C.c_void_p],
-                       "render_device": [C.c_void_p, C.POINTER(TsRenderView), C.POINTER(C.c_void_p)],
-                       "render_info": [C.c_void_p, C.POINTER(TsRenderInfo)]}[name]
-        return fn
-
     @property
     def has_render(self) -> bool:
-        return self.prefix == "ts_" and hasattr(self.lib, "ts_render")
+        return self._has("render")
 
     @staticmethod
     def _heat_plane(name) -> int:
@@ -1479,7 +1446,7 @@ class CApi:
     def render_set_cells(self, type_plane, cell_palette):
         """The static type code per cell ((H, W), every code < n_types) and the cell palette
         ((n_types, 2 pend, 2 stop, 2 rain, 4) RGBA; render.cell_palette builds the reference's)."""
-        fn = self._rn_fn("render_set_cells")
+        fn = self._ext("render_set_cells")
         pal = np.asarray(cell_palette)
         n_types = pal.shape[0] if pal.ndim == 5 else -1
         pal = self._u8(pal, (max(n_types, 0), 2, 2, 2, 4), "cell_palette")
@@ -1488,32 +1455,32 @@ class CApi:
 
     def render_set_vehicle_palette(self, pal):
         """(3 kind, 4 status, 2 flash, 4) RGBA; render.vehicle_palette builds the reference's."""
-        fn = self._rn_fn("render_set_vehicle_palette")
+        fn = self._ext("render_set_vehicle_palette")
         self._chk(fn(self.h, self._u8(pal, (3, 4, 2, 4), "vehicle palette").ctypes.data))
 
     def render_set_heat_lut(self, lut):
         """(256, 4) RGBA, A = blend weight."""
-        fn = self._rn_fn("render_set_heat_lut")
+        fn = self._ext("render_set_heat_lut")
         self._chk(fn(self.h, self._u8(lut, (256, 4), "heat LUT").ctypes.data))
 
     def render_set_routes(self, spawn_idx, rgba=(255, 0, 255, 160)):
         """The vehicles (spawn indices, at most RENDER_MAX_ROUTES; an empty list clears) whose remaining paths the routes
         layer draws, and the colour they are blended in with (A = blend weight)."""
-        fn = self._rn_fn("render_set_routes")
+        fn = self._ext("render_set_routes")
         ids = _i32(np.asarray(spawn_idx, dtype=np.int64).reshape(-1))
         col = self._u8(rgba, (4,), "route colour")
         self._chk(fn(self.h, len(ids), ids.ctypes.data if len(ids) else None, col.ctypes.data))
 
     def render_size(self, view: TsRenderView):
         """(width, height) in pixels of the frame a view gives."""
-        fn = self._rn_fn("render_size")
+        fn = self._ext("render_size")
         w, h = C.c_int32(), C.c_int32()
         self._chk(fn(C.byref(view), C.byref(w), C.byref(h)))
         return w.value, h.value
 
     def render(self, view: TsRenderView) -> np.ndarray:
         """One frame as an (h, w, 4) uint8 array (RGBA, alpha 255)."""
-        fn = self._rn_fn("render")
+        fn = self._ext("render")
         w, h = self.render_size(view)
         out = np.zeros((h, w, 4), dtype=np.uint8)
         self._chk(fn(self.h, C.byref(view), out.ctypes.data))
@@ -1522,27 +1489,16 @@ class CApi:
     def render_device(self, view: TsRenderView, device=None):
         """One frame as an (h, w, 4) uint8 torch tensor over the engine's own frame buffer (no copy; valid until the next
         render or close).  torch must have been imported before the engine library was loaded, as for observe_device."""
-        fn = self._rn_fn("render_device")
-        try:
-            import torch
-        except ImportError as ex:
-            raise RuntimeError("render_device needs torch (use render for a host array)") from ex
+        fn = self._ext("render_device")
         w, h = self.render_size(view)
         ptr = C.c_void_p()
         self._chk(fn(self.h, C.byref(view), C.byref(ptr)))
-        from .dist import ShardedReplans
-        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
-        try:
-            t = ShardedReplans._wrap_device(ptr.value, w * h * 4, device)
-        except RuntimeError as ex:
-            raise RuntimeError("render_device: torch cannot reach the engine's device - import torch before the engine "
-                               "library is loaded, or render to the host with render") from ex
-        return t.view(torch.uint8).view(h, w, 4)
+        return self._device_view("render_device", "use render for a host array", ptr.value, "uint8", (h, w, 4), device)
 
     def render_info(self) -> dict:
         """{"n_types", "has_vehicle_palette", "has_heat_lut", "n_routes", "last_w", "last_h", "frames", "device_bytes"}"""
         info = TsRenderInfo()
-        self._chk(self._rn_fn("render_info")(self.h, C.byref(info)))
+        self._chk(self._ext("render_info")(self.h, C.byref(info)))
         return {"n_types": int(info.n_types), "has_vehicle_palette": bool(info.has_vehicle_palette),
                 "has_heat_lut": bool(info.has_heat_lut), "n_routes": int(info.n_routes), "last_w": int(info.last_w),
                 "last_h": int(info.last_h), "frames": int(info.frames), "device_bytes": int(info.device_bytes)}
@@ -1554,11 +1510,7 @@ class CApi:
         """Debugging hook (ts_debug_batch_info, not part of the headers): the searcher slots as they are now (count, the side
         waves' share, whether the quads' tables alias the arena / hold it) and what the last query batch ran on (waves of its
         widest launch, slots it was allowed, whether the quads held the arena then, launches it took), and the engine's device."""
-        fn = getattr(self.lib, self.prefix + "debug_batch_info", None) if self.prefix == "ts_" else None
-        if fn is None:
-            raise EngineError(TS_E_UNSUPPORTED, f"{self.prefix}debug_batch_info: this engine has no batched pathfinder")
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        fn = self._ext("debug_batch_info")
         out = np.zeros(len(self.BATCH_INFO), dtype=np.int32)
         n = self._chk(fn(self.h, out.ctypes.data, len(out)))
         assert n == len(out), f"ts_debug_batch_info reports {n} words, this wrapper knows {len(out)}"
@@ -1569,21 +1521,8 @@ class CApi:
         result can be fetched).  `device`: default the device the engine was created on.  torch must have been imported before
         the engine library was loaded (as the torch-side callers in dist.py do): the two then share one HIP runtime; loaded the
         other way round torch finds no device, and this method says so."""
-        fn = self._batch_fn("astar_batch_device")
-        try:
-            import torch
-        except ImportError as ex:
-            raise RuntimeError("astar_batch_device needs torch (use astar_batch / astar_batch_fetch for host arrays)") from ex
         p_off, p_xy, n, total = C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int64()
-        self._chk(fn(self.h, C.byref(p_off), C.byref(p_xy), C.byref(n), C.byref(total)))
-        from .dist import ShardedReplans
-        device = torch.device(device) if device is not None else torch.device("cuda", self.debug_batch_info()["device"])
-        try:
-            off = ShardedReplans._wrap_device(p_off.value, (n.value + 1) * 8, device).view(torch.int64)
-        except RuntimeError as ex:
-            raise RuntimeError("astar_batch_device: torch cannot reach the engine's device - import torch before the engine "
-                               "library is loaded, or fetch to the host with astar_batch_fetch") from ex
-        if total.value == 0:
-            return off, torch.zeros((0, 2), dtype=torch.int32, device=device)
-        xy = ShardedReplans._wrap_device(p_xy.value, total.value * 8, device).view(torch.int32).view(-1, 2)
-        return off, xy
+        self._chk(self._ext("astar_batch_device")(self.h, C.byref(p_off), C.byref(p_xy), C.byref(n), C.byref(total)))
+        who, fallback = "astar_batch_device", "use astar_batch / astar_batch_fetch for host arrays"
+        return (self._device_view(who, fallback, p_off.value, "int64", (n.value + 1,), device),
+                self._device_view(who, fallback, p_xy.value, "int32", (total.value, 2), device))

@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import os
 
+from ._capi import EXCHANGE_FN, _wrap_device
+
 
 def env_rank():
     return int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -118,15 +120,6 @@ class ShardedReplans:
             return -1
 
     # ---- device-direct form ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _wrap_device(ptr, nbytes, device):
-        """A uint8 torch tensor over `nbytes` of device memory at `ptr` (no copy; the engine owns the memory)."""
-        import torch
-
-        class _Raw:
-            __cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-        return torch.as_tensor(_Raw(), device=device)
-
     def gather_device(self, send_ptr, nbytes):
         """all-gather of this rank's `nbytes` at device pointer `send_ptr`: -> (device tensor of world * stride bytes, sizes, stride)."""
         import torch
@@ -145,7 +138,7 @@ class ShardedReplans:
             self._recv_t = torch.empty(cap * self.world, dtype=torch.uint8, device=dev)
         send_t = self._send_t[:stride]
         if nbytes > 0:
-            send_t[:nbytes].copy_(self._wrap_device(send_ptr, nbytes, dev))
+            send_t[:nbytes].copy_(_wrap_device(send_ptr, nbytes, dev))
         recv_t = self._recv_t[:stride * self.world]
         if nccl:
             dist.all_gather_into_tensor(recv_t, send_t, group=self.group)
@@ -183,10 +176,9 @@ class ShardedReplans:
 
     def attach(self, api):
         """Switch `api`'s engine to sharded replans over this group (world 1 = plain single-GPU stepping)."""
-        from . import _capi as capi
         if self.world == 1:
             api.set_replan_sharding(0, 1, None)
             return self
-        self._cb = capi.EXCHANGE_FN(self._callback_dev if self.device_direct else self._callback)
+        self._cb = EXCHANGE_FN(self._callback_dev if self.device_direct else self._callback)
         api.set_replan_sharding(self.rank, self.world, self._cb, device_buffers=self.device_direct)
         return self
