@@ -66,6 +66,8 @@ if __name__ == "__main__":
     ap.add_argument("--trips", metavar="OUT.npy", default=None, help="write one record per finished trip (capi.TRIP_DTYPE) to this file")
     ap.add_argument("--trip-capacity", type=int, default=1 << 20, help="records the trip log holds (later ones are dropped and counted)")
     ap.add_argument("--demand", metavar="OUT.npy", default=None, help="write the planned load at the end of the run (remaining routes per cell, (H, W) uint32) to this file")
+    ap.add_argument("--isochrone", nargs=2, metavar=("X,Y", "OUT.npy"), default=None,
+                    help="write the travel cost from every cell to cell (X, Y) at the end of the run ((H, W) uint32, 0xFFFFFFFF: unreachable) to OUT.npy")
     ap.add_argument("--frames", metavar="DIR", default=None, help="write a frame of the whole city into DIR every --frame-every ticks (PNG with PIL, else PPM)")
     ap.add_argument("--frame-every", type=int, default=10)
     ap.add_argument("--zoom", type=int, default=1, help="pixels per cell of the frames (1..64)")
@@ -84,6 +86,14 @@ if __name__ == "__main__":
         np.save(a.demand, load["load"][0])
         y, x = divmod(int(load["load"][0].argmax()), m.width)
         print(f"planned load: {load['steps']} steps of {load['vehicles']} vehicles; busiest cell ({x}, {y}) with {int(load['load'][0, y, x])} planned entries")
+    if a.isochrone:
+        import numpy as np
+        x, y = (int(v) for v in a.isochrone[0].split(","))
+        thr = [50, 100, 200, 500, 1000, 5000]
+        iso = m.isochrones([(x, y)], thr)      # computed on the device (include/trafficsim_costfield.h): a soft TO field and its bands
+        np.save(a.isochrone[1], m.engine.costfield.plane("cost"))
+        print(f"cost to ({x}, {y}): {iso['reached']} cells reached in {iso['rounds']} rounds, farthest at {iso['max_value']}; road cells within "
+              + ", ".join(f"{t}: {int(n)}" for t, n in zip(thr, iso["road_cells"])))
     if a.trips:
         import numpy as np
         rec, info = m.trips(), m.engine.triplog_info()

@@ -1,0 +1,431 @@
+"""Cost fields (include/trafficsim_costfield.h) on the GPU: the value and owner planes against the definition
+(tests/costfield_expect.py) on the reference's KAT worlds under four sets of cost constants, on a ragged live world, on a
+serpentine that crosses tile borders far more often than there are tiles, against the engine's own A*, the device-side reads,
+a run that a compute does not change, and the refusals.  Every comparison is of exact integers."""
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import costfield_expect as ce
+from tests.test_gpu_observe import assert_same_state, engine_for, full_state
+from tests.test_oracle_kats import cost_kats
+from tests.trace_util import setup_from_trace, trace_path
+from trafficsimulation_amd import _capi as capi
+from trafficsimulation_amd import costfield as cf
+from trafficsimulation_amd._lib import new_engine
+from trafficsimulation_amd.world import load_trace
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TILES = (8, 16, 32)
+UNBOUNDED = 0x7FFFFFFF
+
+
+def set_tile(monkeypatch, tile):
+    if tile is None:
+        monkeypatch.delenv("TS_DEBUG_COSTFIELD_TILE", raising=False)
+    else:
+        monkeypatch.setenv("TS_DEBUG_COSTFIELD_TILE", str(tile))
+
+
+def rule_of(api, params, tables):
+    """The step rule on the engine's maps as they are now (the density map is download_density's)."""
+    return ce.Rule.from_params(params, tables["allowed_dirs_map"], tables["is_road_map"], tables["road_type_map"],
+                               api.map(capi.MAP_OCCUPANCY), api.map(capi.MAP_STOP), api.density())
+
+
+def check_field(api, rule, seeds, seed_cost=None, ctx="", tiles=TILES, monkeypatch=None, **q):
+    """Compute the field at every tile size and compare both planes, cell for cell, with the expectation; returns the last
+    info."""
+    want_v, want_o = ce.field(rule, seeds, seed_cost, mode=q.get("mode", "to"), soft=q.get("soft", True),
+                              ignore_flow=q.get("ignore_flow", False), free_flow=q.get("free_flow", False), max_cost=q.get("max_cost", 0))
+    info = None
+    for tile in tiles:
+        set_tile(monkeypatch, tile)
+        info = api.costfield.compute(seeds, seed_cost, **q)
+        got_v, got_o = api.costfield.plane("cost"), api.costfield.plane("owner")
+        where = f"{ctx} {q} tile {tile}"
+        assert np.array_equal(got_v, want_v), f"{where}: values differ at (y, x) {np.argwhere(got_v != want_v)[:4].tolist()}"
+        assert np.array_equal(got_o, want_o), f"{where}: owners differ at (y, x) {np.argwhere(got_o != want_o)[:4].tolist()}"
+        finite = want_v != ce.UNREACHABLE
+        assert info["tile"] == tile and info["reached"] == int(finite.sum())
+        assert info["max_value"] == (int(want_v[finite].max()) if finite.any() else 0)
+        assert info["headings"] == (4 if rule.turn_on and rule.turn > 0 else 1)
+        assert info["rounds"] >= 1 and info["tile_visits"] >= info["rounds"]
+    return info
+
+
+# ---- 1. the KAT worlds with their occupancy and stop planes, under four sets of cost constants --------------------------
+def kat_engine(golden_dir, name, tag, occupancy=None):
+    k = cost_kats(golden_dir)
+    api = new_engine()
+    p = api.default_params() if name == "default" else api.params_from_defaults(json.loads(str(k[f"{name}_params"])))
+    tables = {m: k[f"{tag}_{m}"] for m in ("allowed_dirs_map", "is_road_map", "road_type_map", "intersection_map")}
+    api.create(tables["allowed_dirs_map"], tables["is_road_map"], tables["road_type_map"], tables["intersection_map"], p)
+    occ = k[f"{tag}_occupancy_map_{'base' if name == 'default' else str(k[f'{name}_occupancy'])}"]
+    api.debug_set_occupancy(occ if occupancy is None else occupancy)
+    api.upload_map(capi.MAP_STOP, k[f"{tag}_stop_map"])
+    return api, p, tables
+
+
+def seed_sets(tables):
+    """name -> (seeds, seed_cost): one road seed; eight with duplicates and mixed costs; the cell where the tiles of every size
+    meet (the first cell of one, beside the last cells of three others); a cell that is no road."""
+    road = np.argwhere(tables["is_road_map"] == 1)[:, ::-1]
+    off_road = np.argwhere(tables["is_road_map"] != 1)[:, ::-1]
+    rng = np.random.default_rng(11)
+    pick = road[rng.choice(len(road), 6, replace=False)]
+    eight = np.concatenate([pick, pick[[1, 4]]])
+    # a non-road cell beside a road, so that its field is more than the cell itself where the flow bits allow
+    near = [c for c in off_road.tolist() if any(tables["is_road_map"][min(max(c[1] + dy, 0), len(tables["is_road_map"]) - 1),
+                                                                       min(max(c[0] + dx, 0), len(tables["is_road_map"][0]) - 1)] == 1
+                                                for dx, dy in zip(ce.DX, ce.DY))]
+    return {"one": (road[[len(road) // 3]], None),
+            "eight": (eight, [0, 7, 3, 0, 12, 1, 2, 12]),      # (seed 6 undercuts seed 1 on its own cell, seed 7 ties with seed 4)
+            "corner": (np.asarray([[32, 32]]), None),
+            "off_road": (np.asarray([near[len(near) // 2]]), [5])}
+
+
+# FROM / TO x soft / strict x flow / ignore_flow, and free_flow in both modes
+QUERIES = [dict(mode=m, soft=s, ignore_flow=i) for m in ("from", "to") for s in (True, False) for i in (False, True)] + [
+    dict(mode="to", soft=True, ignore_flow=False, free_flow=True), dict(mode="from", soft=False, ignore_flow=True, free_flow=True)]
+PARAM_SETS = ["default", "turn0", "flags_off", "ints"]
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("name", PARAM_SETS)
+def test_kat_worlds_equal_the_definition(golden_dir, name, tag, monkeypatch):
+    api, p, tables = kat_engine(golden_dir, name, tag)
+    rule = rule_of(api, p, tables)
+    sets = seed_sets(tables)
+    names = sorted(sets)
+    reached = []
+    for k, q in enumerate(QUERIES):
+        # every seed set meets every query over the four parameter sets
+        sname = names[(k + PARAM_SETS.index(name)) % len(names)]
+        seeds, cost = sets[sname]
+        info = check_field(api, rule, seeds, cost, ctx=f"{name}/{tag} seeds {sname}", monkeypatch=monkeypatch, **q)
+        assert info["n_seeds"] == len(seeds) and info["mode"] == q["mode"]
+        reached.append(info["reached"])
+    # the fields are not all small (reached equals the expectation's count, checked above: this is about the cases, and
+    # holds or fails with the fixture and the definition alone): one of them covers more than half of the road cells
+    assert max(reached) > int((tables["is_road_map"] == 1).sum()) // 2 >= 400
+    c = api.counters()
+    assert (c.astar_calls, c.astar_expansions, c.astar_relaxations) == (0, 0, 0)
+    api.close()
+
+
+@pytest.mark.parametrize("name,tag", [("default", "a"), ("turn0", "b")])
+def test_a_seed_walled_in_by_occupied_cells(golden_dir, name, tag, monkeypatch):
+    """Strict mode: nothing leaves a seed whose four neighbours are occupied, and only its neighbours can arrive."""
+    k = cost_kats(golden_dir)
+    road = k[f"{tag}_is_road_map"]
+    ys, xs = np.nonzero((road[1:-1, 1:-1] == 1) & (road[:-2, 1:-1] == 1) & (road[2:, 1:-1] == 1) & (road[1:-1, :-2] == 1) & (road[1:-1, 2:] == 1))
+    x, y = int(xs[len(xs) // 2]) + 1, int(ys[len(ys) // 2]) + 1
+    occ = k[f"{tag}_occupancy_map_base"].copy()
+    occ[y, x] = 0
+    for dx, dy in zip(ce.DX, ce.DY):
+        occ[y + dy, x + dx] = 1
+    api, p, tables = kat_engine(golden_dir, name, tag, occupancy=occ)
+    rule = rule_of(api, p, tables)
+    for mode in ("from", "to"):
+        info = check_field(api, rule, [(x, y)], ctx=f"walled {name}/{tag}", monkeypatch=monkeypatch, mode=mode, soft=False, ignore_flow=True)
+        assert info["reached"] == (1 if mode == "from" else 5)
+    soft = check_field(api, rule, [(x, y)], ctx="walled, soft", tiles=(16,), monkeypatch=monkeypatch, mode="from", soft=True, ignore_flow=True)
+    assert soft["reached"] > 5
+    api.close()
+
+
+# ---- 2. a ragged live world: neither side a multiple of any tile ---------------------------------------------------------
+@pytest.mark.parametrize("mode", ["from", "to"])
+def test_ragged_world_after_twenty_ticks(mode, monkeypatch):
+    api, tr = engine_for("ragged_100x75_s33")
+    assert (int(tr["width"]), int(tr["height"])) == (100, 75)
+    api.step(20)
+    rule = rule_of(api, api.params_from_defaults(tr["defaults_json"]), tr)
+    road = np.argwhere(tr["is_road_map"] == 1)[:, ::-1]
+    last = road[np.lexsort((road[:, 0], road[:, 1]))[-1]]          # a road cell of the topmost row that has one
+    seeds = np.stack([road[len(road) // 2], last, road[np.argmax(road[:, 0])]])
+    info = check_field(api, rule, seeds, [0, 3, 1], ctx="ragged", tiles=(8, 32), monkeypatch=monkeypatch, mode=mode, soft=True)
+    assert info["tick"] == 20 and (info["width"], info["height"]) == (100, 75)
+    check_field(api, rule, seeds, ctx="ragged, against the flow", tiles=(8, 32), monkeypatch=monkeypatch, mode=mode, soft=False, ignore_flow=True)
+    api.close()
+
+
+# ---- 3. a serpentine: the shortest path crosses tile borders far more often than there are tiles -----------------------------
+def serpentine(n=40):
+    """An n x n all-road map whose flow bits make one one-way road: east along the even rows, west along the odd ones, north at
+    the end of every row."""
+    allowed = np.zeros((n, n), dtype=np.uint8)
+    for y in range(n):
+        east = y % 2 == 0
+        allowed[y, :] = 1 << (1 if east else 3)
+        allowed[y, n - 1 if east else 0] = 1 << 0 if y < n - 1 else 0
+    return allowed
+
+
+@pytest.mark.parametrize("mode", ["from", "to"])
+def test_serpentine_takes_more_rounds_than_there_are_tiles(mode, monkeypatch):
+    n = 40
+    allowed = serpentine(n)
+    z = np.zeros((n, n), dtype=np.int8)
+    tables = {"allowed_dirs_map": allowed, "is_road_map": z + 1, "road_type_map": z, "intersection_map": z}
+    api = new_engine()
+    p = api.default_params()
+    api.create(allowed, z + 1, z, z, p)
+    rule = rule_of(api, p, tables)
+    seed = [(0, 0)] if mode == "from" else [(0, n - 1)]       # the road's first cell / its last (row 39 runs west)
+    info = check_field(api, rule, seed, ctx="serpentine", tiles=(8,), monkeypatch=monkeypatch, mode=mode)
+    tiles = (n // 8) ** 2
+    assert info["reached"] == n * n and info["rounds"] > tiles, info
+    # n * n - 1 steps and a turn penalty at both ends of every row but the path's own two ends
+    assert info["max_value"] == n * n - 1 + int(p.turn_penalty) * 2 * (n - 1)
+    api.close()
+
+
+# ---- 4. against the engine's own A* on a live state ------------------------------------------------------------------------
+@pytest.mark.parametrize("turn0", [False, True])
+def test_field_against_the_batched_astar(turn0, monkeypatch):
+    set_tile(monkeypatch, None)
+    tr = load_trace(trace_path("full_96_s8"))
+    if turn0:
+        tr = dict(tr, defaults_json=dict(tr["defaults_json"], VEHICLE_TURN_PENALTY=0))
+    api = new_engine()
+    setup_from_trace(api, tr)
+    api.step(30)
+    p = api.params_from_defaults(tr["defaults_json"])
+    assert int(p.turn_penalty) == (0 if turn0 else 10)
+    rule = rule_of(api, p, tr)
+    road = np.argwhere(tr["is_road_map"] == 1)[:, ::-1]
+    rng = np.random.default_rng(8)
+    starts = road[rng.choice(len(road), 6, replace=False)]
+    goals = road[rng.choice(len(road), 10, replace=False)]
+    queries = [(sx, sy, gx, gy, 1, 0, UNBOUNDED) for sx, sy in starts.tolist() for gx, gy in goals.tolist()]
+    off, xy = api.astar_batch(queries)                     # (TS_E_CAPACITY would raise)
+    assert len(off) == 61
+    found = 0
+    for s, (sx, sy) in enumerate(starts.tolist()):
+        api.costfield.compute([(sx, sy)], mode="from", soft=True)
+        at_goals = api.costfield.gather("cost", goals)
+        for g, (gx, gy) in enumerate(goals.tolist()):
+            i = s * len(goals) + g
+            path = [tuple(c) for c in xy[off[i]:off[i + 1]].tolist()]
+            if not path:
+                assert (sx, sy) == (gx, gy) or at_goals[g] == cf.CF_UNREACHABLE, (sx, sy, gx, gy)
+                continue
+            if path[0] != (sx, sy):
+                path = [(sx, sy)] + path
+            cost = rule.path_cost(path, soft=True)
+            assert cost is not None and path[-1] == (gx, gy)
+            assert at_goals[g] == cost if turn0 else at_goals[g] <= cost, (sx, sy, gx, gy, int(at_goals[g]), cost)
+            found += 1
+    assert found >= 30
+    api.close()
+
+
+# ---- 5. gather, bands, device pointers, max_cost ----------------------------------------------------------------------------
+def test_gather_bands_and_max_cost_equal_numpy(golden_dir, monkeypatch):
+    set_tile(monkeypatch, None)
+    api, p, tables = kat_engine(golden_dir, "default", "b")
+    c = api.costfield
+    seeds, cost = seed_sets(tables)["eight"]
+    info = c.compute(seeds, cost, mode="to", soft=True)
+    value, owner = c.plane("cost"), c.plane("owner")
+    assert value.dtype == np.uint32 and owner.dtype == np.int32 and info["device_bytes"] == value.nbytes + owner.nbytes
+    rng = np.random.default_rng(2)
+    xy = np.stack([rng.integers(0, api.W, 5000), rng.integers(0, api.H, 5000)], axis=1)
+    assert np.array_equal(c.gather("cost", xy), value[xy[:, 1], xy[:, 0]])
+    assert np.array_equal(c.gather("owner", xy), owner[xy[:, 1], xy[:, 0]])
+    assert c.gather(0, np.zeros((0, 2))).shape == (0,)
+    on_road = value[tables["is_road_map"] == 1]
+    finite = np.sort(np.unique(on_road[on_road != cf.CF_UNREACHABLE]))
+    thr = [0, 1, 1, int(finite[len(finite) // 3]), int(finite[len(finite) // 2]) + 1, int(finite[-1]), int(finite[-1]) + 1000, 0xFFFFFFFF]
+    want = [int((on_road <= t).sum()) for t in thr]
+    assert c.bands(thr).tolist() == want and want[-1] == len(on_road) and 0 < want[3] < want[5]
+    many = np.arange(cf.CF_MAX_BANDS, dtype=np.uint32) * 3
+    assert c.bands(many).tolist() == [int((on_road <= t).sum()) for t in many]
+    # max_cost clips exactly
+    cut = int(finite[len(finite) // 2])
+    clipped = c.compute(seeds, cost, mode="to", soft=True, max_cost=cut)
+    assert np.array_equal(c.plane("cost"), np.where(value <= cut, value, cf.CF_UNREACHABLE))
+    assert np.array_equal(c.plane("owner"), np.where(value <= cut, owner, -1))
+    assert clipped["max_cost"] == cut and clipped["max_value"] <= cut and clipped["reached"] == int((value <= cut).sum())
+    api.close()
+
+
+DEVICE_SCRIPT = r'''
+import sys
+sys.path.insert(0, %(root)r)
+import torch                     # (first: the engine library then shares torch's HIP runtime)
+torch.cuda.init()
+import numpy as np
+from trafficsimulation_amd._lib import new_engine
+from trafficsimulation_amd.world import load_trace
+from tests.trace_util import setup_from_trace, trace_path
+tr = load_trace(trace_path("full_96_s8"))
+api = new_engine()
+setup_from_trace(api, tr)
+api.step(5)
+c = api.costfield
+c.compute([(40, 40), (10, 70)], [0, 2], mode="to")
+for which, dt in (("cost", np.uint32), ("owner", np.int32)):
+    t = c.device(which)
+    assert t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (api.H, api.W)
+    assert np.array_equal(t.cpu().numpy().view(dt), c.plane(which))
+api.close()
+print("DEVICE_OK")
+'''
+
+
+def test_device_planes(tmp_path):
+    """costfield.device(), in a process of its own that imports torch before it loads the engine."""
+    script = tmp_path / "costfield_device.py"
+    script.write_text(DEVICE_SCRIPT % dict(root=ROOT))
+    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+# ---- 6. a compute changes nothing -----------------------------------------------------------------------------------------------
+def test_computing_before_every_tick_changes_nothing(monkeypatch):
+    set_tile(monkeypatch, None)
+    name, T = "full_96_s8", 40
+    plain, tr = engine_for(name)
+    plain.step(T)
+    busy, _ = engine_for(name)
+    seeds = tr["highway_exits_xy"] if "highway_exits_xy" in tr and len(tr["highway_exits_xy"]) else [(5, 5), (90, 40)]
+    blob_before = busy.checkpoint_save()
+    busy.costfield.compute(seeds, mode="to", soft=True)
+    assert busy.checkpoint_save() == blob_before, "a result changed the checkpoint's bytes"
+    for t in range(T):
+        info = busy.costfield.compute(seeds, mode="to", soft=True)
+        assert info["tick"] == t
+        busy.step(1)
+        assert busy.costfield.info() == info, "a tick touched the snapshot"
+    a, b = full_state(plain), full_state(busy)
+    assert_same_state(a, b, "with a soft TO field before every tick")
+    ca, cb = plain.counters(), busy.counters()
+    assert (ca.astar_calls, ca.astar_expansions, ca.astar_relaxations) == (cb.astar_calls, cb.astar_expansions, cb.astar_relaxations)
+    assert ca.astar_calls > 0
+    # a checkpoint load leaves the result alone
+    value, owner = busy.costfield.plane("cost"), busy.costfield.plane("owner")
+    info = busy.costfield.info()
+    busy.checkpoint_load(blob_before)
+    assert busy.counters().step_count == 0 and busy.costfield.info() == info
+    assert np.array_equal(busy.costfield.plane("cost"), value) and np.array_equal(busy.costfield.plane("owner"), owner)
+    plain.close()
+    busy.close()
+
+
+# ---- 7. the refusals ----------------------------------------------------------------------------------------------------------------
+def raw_compute(api, seeds=((3, 3),), cost=None, **kw):
+    xy = np.ascontiguousarray(np.asarray(seeds, dtype=np.int32).reshape(-1, 2))
+    q = cf.TsCostFieldQuery(mode=cf.CF_TO, soft_obstacles=1, n_seeds=len(xy), seed_xy=xy.ctypes.data)
+    c = None
+    if cost is not None:
+        c = np.ascontiguousarray(np.asarray(cost, dtype=np.int32))
+        q.seed_cost = c.ctypes.data
+    for k, v in kw.items():
+        setattr(q, k, v)
+    return api.costfield._ext("costfield_compute")(api.h, ctypes.byref(q), None)
+
+
+def test_refusals_leave_the_previous_result(golden_dir, monkeypatch):
+    set_tile(monkeypatch, None)
+    api, p, tables = kat_engine(golden_dir, "default", "a")
+    c = api.costfield
+    empty = c.info()
+    assert (empty["n_seeds"], empty["reached"], empty["device_bytes"], empty["rounds"]) == (0, 0, 0, 0)
+    assert (empty["width"], empty["height"]) == (api.W, api.H)
+    c.release()                                                # TS_OK without a result
+    reads = (lambda: c.plane("cost"), lambda: c.plane("owner"), lambda: c.gather("cost", [(1, 1)]), lambda: c.bands([5]), c.device)
+    for read in reads:
+        with pytest.raises(capi.EngineError) as ex:
+            read()
+        assert ex.value.code == capi.TS_E_STATE
+    two = seed_sets(tables)["eight"][0][:2]
+    info = c.compute(two, [1, 0], mode="from", soft=True, ignore_flow=True)
+    value, owner = c.plane("cost"), c.plane("owner")
+    assert info["reached"] > 100
+
+    def unchanged():
+        return c.info() == info and np.array_equal(c.plane("cost"), value) and np.array_equal(c.plane("owner"), owner)
+
+    W, H = api.W, api.H
+    for kw in (dict(mode=2), dict(mode=-1), dict(soft_obstacles=2), dict(ignore_flow=-1), dict(free_flow=4), dict(reserved=1),
+               dict(n_seeds=0), dict(n_seeds=-3), dict(n_seeds=cf.CF_MAX_SEEDS + 1), dict(seed_xy=None),
+               dict(seeds=[(W, 0)]), dict(seeds=[(0, H)]), dict(seeds=[(2, 2), (-1, 5)]), dict(seeds=[(2, 2), (5, -1)]),
+               dict(cost=[-1]), dict(cost=[cf.CF_INF]), dict(seeds=[(2, 2), (3, 3)], cost=[0, 0x7FFFFFFF])):
+        assert raw_compute(api, **kw) == capi.TS_E_INVALID, kw
+        assert unchanged(), kw
+    assert raw_compute(api, cost=[cf.CF_INF - 1]) == capi.TS_OK and not unchanged()        # (the largest cost there is: accepted)
+    info = c.compute(two, [1, 0], mode="from", soft=True, ignore_flow=True)
+    assert unchanged()
+    assert api.costfield._ext("costfield_compute")(api.h, None, None) == capi.TS_E_INVALID and unchanged()
+    buf = np.zeros((H, W), dtype=np.uint64)
+    dl, ga, ba, dev = (c._ext("costfield_" + n) for n in ("download", "gather", "bands", "device"))
+    ptr = ctypes.c_void_p()
+    xy = np.asarray([[1, 1], [W, 1]], dtype=np.int32)
+    thr = np.asarray([5, 4], dtype=np.uint32)
+    for which in (2, -1):
+        assert dl(api.h, which, buf.ctypes.data) == capi.TS_E_INVALID
+        assert ga(api.h, which, 1, xy.ctypes.data, buf.ctypes.data) == capi.TS_E_INVALID
+        assert dev(api.h, which, ctypes.byref(ptr)) == capi.TS_E_INVALID
+    assert dl(api.h, 0, None) == capi.TS_E_INVALID and dev(api.h, 0, None) == capi.TS_E_INVALID
+    assert ga(api.h, 0, 2, xy.ctypes.data, buf.ctypes.data) == capi.TS_E_INVALID          # the second cell is outside the map
+    assert ga(api.h, 0, -1, xy.ctypes.data, buf.ctypes.data) == capi.TS_E_INVALID
+    assert ga(api.h, 0, 1, None, buf.ctypes.data) == capi.TS_E_INVALID
+    assert ba(api.h, 2, thr.ctypes.data, buf.ctypes.data) == capi.TS_E_INVALID             # descending
+    assert ba(api.h, 0, thr.ctypes.data, buf.ctypes.data) == capi.TS_E_INVALID
+    assert ba(api.h, cf.CF_MAX_BANDS + 1, thr.ctypes.data, buf.ctypes.data) == capi.TS_E_INVALID
+    assert ba(api.h, 1, None, buf.ctypes.data) == capi.TS_E_INVALID and ba(api.h, 1, thr.ctypes.data, None) == capi.TS_E_INVALID
+    assert unchanged()
+    c.release()
+    assert c.info() == empty
+    for read in reads:
+        with pytest.raises(capi.EngineError) as ex:
+            read()
+        assert ex.value.code == capi.TS_E_STATE
+    c.release()
+    api.close()
+
+
+def test_unsupported_parameters_and_awareness(golden_dir, monkeypatch):
+    set_tile(monkeypatch, None)
+    api, p, tables = kat_engine(golden_dir, "default", "a")
+    info = api.costfield.compute([(20, 20)], mode="to")
+    value = api.costfield.plane("cost")
+    api.close()
+    # penalties that are no multiples of 0.5: the kernels do not carry them
+    quarter, _, _ = kat_engine(golden_dir, "quarter", "a")
+    with pytest.raises(capi.EngineError) as ex:
+        quarter.costfield.compute([(20, 20)], mode="to")
+    assert ex.value.code == capi.TS_E_UNSUPPORTED
+    with pytest.raises(capi.EngineError) as ex:
+        quarter.costfield.compute([(20, 20)], mode="to", free_flow=True)
+    assert ex.value.code == capi.TS_E_UNSUPPORTED and quarter.costfield.info()["n_seeds"] == 0
+    quarter.close()
+    # field-of-view masking: free-flow fields only, and those are the free-flow fields of an engine without it
+    k = cost_kats(golden_dir)
+    fov = new_engine()
+    pf = fov.default_params()
+    pf.respect_awareness = 1
+    fov.create(tables["allowed_dirs_map"], tables["is_road_map"], tables["road_type_map"], tables["intersection_map"], pf)
+    fov.debug_set_occupancy(k["a_occupancy_map_base"])
+    fov.upload_map(capi.MAP_STOP, k["a_stop_map"])
+    free = fov.costfield.compute([(20, 20)], mode="to", free_flow=True)
+    held = fov.costfield.plane("cost")
+    for kw in (dict(soft=True), dict(soft=False), dict(soft=True, ignore_flow=True)):
+        with pytest.raises(capi.EngineError) as ex:
+            fov.costfield.compute([(20, 20)], mode="to", **kw)
+        assert ex.value.code == capi.TS_E_UNSUPPORTED
+        assert fov.costfield.info() == free and np.array_equal(fov.costfield.plane("cost"), held)
+    rule = rule_of(fov, pf, tables)
+    assert np.array_equal(held, ce.field(rule, [(20, 20)], mode="to", free_flow=True)[0])
+    assert free["reached"] >= info["reached"] and (held <= value).all()        # (obstacles only ever add cost)
+    fov.close()

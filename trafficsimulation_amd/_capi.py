@@ -1156,6 +1156,14 @@ class CApi:
         """Free the planes; there is no result afterwards."""
         self._chk(self._ext("demand_release")(self.h))
 
+    # ---- cost fields (include/trafficsim_costfield.h): entries, structs and methods live in costfield.py ----------
+    @property
+    def costfield(self):
+        """The cost-field entries of this engine, as a costfield.CostField (a view: it keeps no state of its own, so none is
+        cached and the engine is not kept alive by a reference cycle)."""
+        from .costfield import CostField
+        return CostField(self)
+
     # ---- trip log (include/trafficsim_triplog.h) ----------------------------------------------------
     @property
     def has_triplog(self) -> bool:

@@ -1094,6 +1094,53 @@ class CityModel:
                         "planned_throughput_by_direction": by_dir})
         return out
 
+    # ---- cost fields (include/trafficsim_costfield.h) --------------------------------------------------
+    @staticmethod
+    def _seed_cells(seeds) -> np.ndarray:
+        """(n, 2) int32 (x, y) of `seeds`: (x, y) pairs, cells or vehicle agents (where they stand now), or a mix."""
+        out = []
+        for s in seeds:
+            pos = s.pos if hasattr(s, "pos") else s
+            if pos is None:
+                raise ValueError(f"cost field: {s!r} has no position (a vehicle that has left?)")
+            out.append((int(pos[0]), int(pos[1])))
+        return np.asarray(out, dtype=np.int32).reshape(-1, 2)
+
+    def cost_field(self, seeds, mode: str = "to", seed_cost=None, **modes) -> dict:
+        """What the network costs right now: the cheapest travel cost, under the pathfinder's own cost rule and the traffic as
+        it is, from every cell to its nearest seed (`mode="to"`) or from the seeds to every cell (`"from"`), computed on the
+        device.  `seeds`: (x, y) pairs, cells or vehicle agents; `modes`: soft (default True), ignore_flow, free_flow, max_cost.
+        Returns {"cost": (H, W) uint32 (0xFFFFFFFF: unreachable), "owner": (H, W) int32 index into "seeds" of the seed that
+        attains it (-1: unreachable), "seeds": (n, 2)} and the fields of `engine.costfield.info()`.  A snapshot of the state
+        between two steps: not updated by step() and not carried by save / load / deepcopy / pickle."""
+        self._flush_host_writes()
+        xy = self._seed_cells(seeds)
+        cf = self.engine.costfield
+        info = cf.compute(xy, seed_cost, mode=mode, **modes)
+        return dict(info, cost=cf.plane("cost"), owner=cf.plane("owner"), seeds=xy)
+
+    def catchments(self, kind="highway_exits", **modes) -> dict:
+        """Which exit, entrance or depot is the nearest one for every cell: the owner plane of the TO field seeded at the
+        highway exits (`kind="highway_exits"`), the block entrances (`"block_entrances"`) or the given cells.  Returns
+        {"zone": (H, W) int32, "n": the number of seeds, "seeds": (n, 2), "cost": the value plane}; with at most
+        capi.TRIPLOG_MAX_ZONES seeds, `engine.triplog_set_zones(zone, n)` takes the plane as it is."""
+        if isinstance(kind, str):
+            if kind not in ("highway_exits", "block_entrances"):
+                raise ValueError(f"catchments: unknown kind {kind!r} ('highway_exits', 'block_entrances' or a list of cells)")
+            kind = self.highway_exits if kind == "highway_exits" else self.block_entrances
+        f = self.cost_field(kind, mode="to", **modes)
+        return {"zone": f["owner"], "n": len(f["seeds"]), "seeds": f["seeds"], "cost": f["cost"]}
+
+    def isochrones(self, seeds, thresholds, mode: str = "to", **modes) -> dict:
+        """Isochrone areas of `seeds`: for every ascending threshold the number of road cells whose cost is at most it, counted
+        on the device.  Returns {"thresholds", "road_cells": uint64 per threshold} and the fields of `engine.costfield.info()`;
+        the planes stay on the device (engine.costfield.plane / gather / device read them)."""
+        self._flush_host_writes()
+        cf = self.engine.costfield
+        info = cf.compute(self._seed_cells(seeds), mode=mode, **modes)
+        thr = np.asarray(thresholds, dtype=np.uint32).reshape(-1)
+        return dict(info, thresholds=thr, road_cells=cf.bands(thr))
+
     # ---- getters used by the UI (city_model.py:1965-2149) ------------------------------------------
     # ---- device renderer (include/trafficsim_render.h) ---------------------------------------------------
     def _render_defaults(self):
