@@ -6,9 +6,9 @@ import os
 import re
 import subprocess
 
+from tests.procs import ROOT
 from trafficsimulation_amd import _capi as capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CTYPE = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
          "uint8_t": ctypes.c_uint8}
 

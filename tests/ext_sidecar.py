@@ -27,6 +27,13 @@ ROUTE_RGBA = (1, 2, 3, 255)            # weight 255: a route cell is exactly thi
 BG = (17, 34, 51, 0)
 CHECK_EVERY = 10
 GC_MIN_CELLS = 17                      # cells driven since a path was written: a collection has dropped its first word
+# config1_64_s11 (generator_ticks, pinned on the CPU by tests/test_ext_sidecar.py): by tick 260 the rows show 102 vehicles
+# spawned (50 were placed before tick 0) and a service vehicle parked after tick 225
+GENERATOR_TRACE, GENERATOR_T, GENERATOR_SPAWNED, GENERATOR_PARKED_AT = "config1_64_s11", 260, 102, 225
+# the fixtures of each light-control family in whose recorded runs searches run inside ticks (light_fixtures_with_searches,
+# pinned on the CPU by tests/test_ext_sidecar.py); the GAT one is driven through act_q, whose epsilon-greedy draws come from
+# the global stream on the host
+LIGHTS_EXT_FIXTURE, LIGHTS_PROTO_FIXTURE = "lights_ext_stuck_96_s43", "lights_gat_96_s49"
 
 
 def read_planes(api, n_bins):

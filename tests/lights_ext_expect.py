@@ -162,3 +162,30 @@ def request(ctrl, phases):
     for g, p in enumerate(phases):
         if int(p) >= 0:
             apply_phase(ctrl, g, int(p))
+
+
+# ---- for the GPU tests of both light-control families ----------------------------------------------------------------------
+FIXTURES = ["lights_ext_64_s45", "lights_ext_96_s42", "lights_ext_stuck_96_s43"]
+# replanning gated off
+GATED = {"PATHFINDING_COOLDOWN": 10 ** 9, "VEHICLE_STUCK_RECOMPUTE_THRESHOLD": 10 ** 9,
+         "VEHICLE_STUCK_RECOMPUTE_THRESHOLD_INTERSECTION": 10 ** 9, "VEHICLE_CONTRAFLOW_OVERTAKE_ACTIVE": False,
+         "VEHICLE_STUCK_CONTRAFLOW_ENABLED": False}
+
+
+class Stepper:
+    """An engine whose step(1) first does `before(tick)`; everything else is the engine's.  `groups` may be overridden."""
+
+    def __init__(self, api, before, groups=None):
+        self._api, self._before, self._groups, self.tick = api, before, groups, 0
+
+    def __getattr__(self, name):
+        return getattr(self._api, name)
+
+    def step(self, n=1):
+        for _ in range(n):
+            self._before(self.tick)
+            self._api.step(1)
+            self.tick += 1
+
+    def groups(self):
+        return self._groups(self.tick - 1, self._api.groups()) if self._groups else self._api.groups()

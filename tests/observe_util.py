@@ -26,6 +26,14 @@ V = {n: i for i, n in enumerate(capi.V_FIELDS)}
 DXY = ((0, 1), (1, 0), (0, -1), (-1, 0))     # N E S W as (dx, dy)
 MAX_MOVE = 5                                  # the most cells a vehicle moves per tick unless the trace's defaults say otherwise
 
+# The trace with replanning whose ENTER planes are reconstructed from the rows under the caps below.  The traces the work
+# started from - full_96_s8, default_200_s20 and the nobatch_* family - do not meet the caps (figures in
+# tests/test_observe_expect.py); of the golden traces in which a search runs only unopt_96_s21 does
+# (39 516 searches in 200 ticks), so it is the one chosen.  The others stay in the GPU test as extra ground
+# (UNCAPPED_REPLAN_TRACES): what is certain in them is checked all the same.
+REPLAN_TRACES = ["unopt_96_s21"]
+UNCAPPED_REPLAN_TRACES = ["full_96_s8", "default_200_s20", "nobatch_config1_64_s29"]
+
 
 def n_ticks(tr):
     return len(tr["veh_off"]) - 1

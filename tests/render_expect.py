@@ -11,7 +11,18 @@ every comparison against it is an equality.
              "heat": uint64 (H, W) (the plane, or the sum of the four ENTER planes), "step_count": int}
     view  = dict(x0, y0, cells_w, cells_h, zoom, shrink, layers, flip_y, heat_max, vehicle_radius_256, background)
 """
+import os
+
 import numpy as np
+
+from tests.trace_util import GOLDEN
+
+RENDER_FIXTURES = ["render_city_64_s56"]
+
+
+def fixture_path(name):
+    return os.path.join(GOLDEN, f"{name}.npz")
+
 
 SIGNALS, RAIN, VEHICLES, HEAT, ROUTES = 1, 2, 4, 8, 16
 ALL = 31

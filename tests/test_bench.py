@@ -1,17 +1,15 @@
 """bench.py's own pieces on the CPU: its threaded route walk against citygen.make_routes, and --dump-outputs' files written
 from the oracle (the GPU side of both: tests/test_gpu_bench.py)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import bench
+from tests import procs
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import citygen
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("size,vehicles,seed,lo,hi,carves,threads", [
@@ -64,6 +62,6 @@ def test_dump_outputs_sample_large_tables(oracle, tmp_path, monkeypatch):
 
 
 def test_steps_must_be_positive():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
-                         timeout=120, cwd=ROOT)
-    assert out.returncode == 2 and "--steps" in out.stderr
+    with pytest.raises(AssertionError) as ex:
+        procs.run([sys.executable, os.path.join(procs.ROOT, "bench.py"), "--steps", "0"], timeout=120)
+    assert ex.value.proc.returncode == 2 and "--steps" in ex.value.proc.stderr

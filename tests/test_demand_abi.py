@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests.abi_util import declared, header, hip_lib, oracle_api, struct_fields
+from tests.engine_util import refused
 from trafficsimulation_amd import _capi as capi
 
 ENTRIES = ["ts_demand_compute", "ts_demand_device", "ts_demand_download", "ts_demand_groups", "ts_demand_info",
@@ -68,6 +69,4 @@ def test_oracle_demand_is_unsupported(call):
     calls = {"compute": api.demand_compute, "compute_select": lambda: api.demand_compute(4, 16, False, np.ones(3, dtype=np.uint8)),
              "info": api.demand_info, "plane": lambda: api.demand_plane(0, "N"), "pooled": lambda: api.demand_pooled(2),
              "groups": api.demand_groups, "device": api.demand_device, "release": api.demand_release}
-    with pytest.raises(capi.EngineError) as ex:
-        calls[call]()
-    assert ex.value.code == capi.TS_E_UNSUPPORTED
+    refused(capi.TS_E_UNSUPPORTED, calls[call])

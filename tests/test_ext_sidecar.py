@@ -5,6 +5,7 @@ import pytest
 
 from tests import ext_sidecar as xs
 from tests import observe_util as ou
+from tests.ext_sidecar import GENERATOR_PARKED_AT, GENERATOR_SPAWNED, GENERATOR_T, GENERATOR_TRACE, LIGHTS_EXT_FIXTURE, LIGHTS_PROTO_FIXTURE
 from tests.trace_util import trace_path
 from trafficsimulation_amd.world import load_trace
 
@@ -35,7 +36,6 @@ def test_a_collection_per_tick_leaves_path_cur_inside_a_word(name):
 
 
 def test_generator_ticks():
-    from tests.test_gpu_ext_paths import GENERATOR_PARKED_AT, GENERATOR_SPAWNED, GENERATOR_T, GENERATOR_TRACE
     tr = load_trace(trace_path(GENERATOR_TRACE))
     assert xs.generator_ticks(tr) == (GENERATOR_T, GENERATOR_SPAWNED, GENERATOR_PARKED_AT) == (260, 102, 225)
     n0 = len(tr["v_start_xy"])
@@ -48,7 +48,6 @@ def test_generator_ticks():
 
 
 def test_light_fixtures_with_searches():
-    from tests.test_gpu_ext_paths import LIGHTS_EXT_FIXTURE, LIGHTS_PROTO_FIXTURE
     assert xs.light_fixtures_with_searches(["lights_ext_64_s45", "lights_ext_96_s42", "lights_ext_stuck_96_s43"]) == [LIGHTS_EXT_FIXTURE]
     assert xs.light_fixtures_with_searches(["lights_gat_64_s45", "lights_gat_96_s49"]) == [LIGHTS_PROTO_FIXTURE]
     assert "lp_q" in load_trace(trace_path(LIGHTS_PROTO_FIXTURE)), "the GAT fixture is not driven through act_q"

@@ -9,8 +9,9 @@ import pytest
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import _lib
 from trafficsimulation_amd.world import load_trace
-from tests import test_gpu_parity as P
-from tests.test_gpu_forced_paths import small_engine
+from tests import procs
+from tests import kats_util as K
+from tests.engine_util import city_model, pair_full, refused, same_state, small_engine
 from tests.trace_util import replay_and_compare, setup_from_trace, trace_path
 
 pytestmark = pytest.mark.gpu
@@ -92,11 +93,11 @@ def test_fov_kats_in_one_launch_per_range(golden_dir, tag):
     assert nonempty > 100
 
 
-@pytest.mark.parametrize("name,tag", P.K.COST_CASES)
+@pytest.mark.parametrize("name,tag", K.COST_CASES)
 def test_cost_kats_in_one_launch(hip, golden_dir, name, tag):
     """The reference's KATs under moved cost constants, one batch per set and world: the CSR equals the reference's paths and
     what ts_astar answers query by query on the same engine."""
-    q, off, xy = P.K.cost_kat_case(hip, golden_dir, name, tag)
+    q, off, xy = K.cost_kat_case(hip, golden_dir, name, tag)
     got_off, got_xy = assert_kat_batch(hip, q, off, xy, ctx=f"{name}/{tag}: ")
     for i, (sx, sy, gx, gy, soft, ign, maxs) in enumerate(q):
         one = hip.astar(int(sx), int(sy), int(gx), int(gy), bool(soft), bool(ign), int(maxs))
@@ -198,7 +199,7 @@ def random_queries(tables, n, seed, reach=(12, 70, 12, 8)):
 
 def test_3000_queries_against_the_oracle_at_512():
     import bench
-    h, c = P._pair_full(512, 12_000, 7)
+    h, c = pair_full(512, 12_000, 7)
     tables, routes, _ = bench.make_workload(512, 12_000, 7)
     h2 = bench.setup(_lib.new_engine(), tables, routes, 7, policy="full")
     try:
@@ -235,15 +236,6 @@ def state_of(api):
                 rng=[api.rng_fingerprint(capi.RNG_GLOBAL), api.rng_fingerprint(capi.RNG_SCHEDULER)])
 
 
-def assert_same_state(a, b, ctx):
-    sa, sb = state_of(a), state_of(b)
-    for i, (p, r) in enumerate(zip(sa["maps"], sb["maps"])):
-        assert np.array_equal(p, r), f"{ctx}: map {i}"
-    assert np.array_equal(sa["veh"], sb["veh"]), f"{ctx}: vehicle rows"
-    assert np.array_equal(sa["grp"], sb["grp"]), f"{ctx}: group rows"
-    assert sa["rng"] == sb["rng"], f"{ctx}: RNG states"
-
-
 def road_queries(api_or_road, n, seed):
     road = api_or_road
     rng = np.random.RandomState(seed)
@@ -269,7 +261,7 @@ def test_batches_between_ticks_leave_a_trace_replay_alone():
             assert len(off) == 201
             a.step(1)
             b.step(1)
-            assert_same_state(a, b, f"tick {t}")
+            same_state(a, b, f"tick {t}")
             ca, cb = counters_dict(a), counters_dict(b)
             assert cb["astar_calls"] - ca["astar_calls"] == 200 * (t + 1)
             assert {f: v for f, v in ca.items() if f not in ASTAR_FIELDS} == {f: v for f, v in cb.items() if f not in ASTAR_FIELDS}
@@ -277,7 +269,7 @@ def test_batches_between_ticks_leave_a_trace_replay_alone():
         try:      # ... and the undisturbed twin is the trace's run
             setup_from_trace(a2, tr, explicit_paths=False)
             assert replay_and_compare(a2, tr) == T
-            assert_same_state(a, a2, "end of trace")
+            same_state(a, a2, "end of trace")
         finally:
             a2.close()
     finally:
@@ -303,7 +295,7 @@ def test_batches_while_the_quads_hold_the_table_arena(monkeypatch):
         for t in range(8):
             a.step(1)
             b.step(1)
-            assert_same_state(a, b, f"tick {t}")
+            same_state(a, b, f"tick {t}")
             now = b.debug_batch_info()
             off, xy = b.astar_batch(q)
             info = b.debug_batch_info()
@@ -335,25 +327,21 @@ def test_refusals(hip):
     W, H = int(tr["width"]), int(tr["height"])
     assert (W, H) == (96, 96)
     q = road_queries(np.asarray(tr["is_road_map"]), 10, 4)
-    with pytest.raises(capi.EngineError) as ex:       # nothing has been run yet
-        hip.astar_batch_fetch()
-    assert ex.value.code == capi.TS_E_INVALID
+    refused(capi.TS_E_INVALID, hip.astar_batch_fetch)     # nothing has been run yet
     off0, xy0 = hip.astar_batch(q)
     assert off0[-1] > 0
     c0 = counters_dict(hip)
     bad = q.copy()
     bad[7, 2] = W
-    with pytest.raises(capi.EngineError) as ex:
-        hip.astar_batch(bad)
-    assert ex.value.code == capi.TS_E_INVALID and "7" in str(ex.value)
+    ex, = refused(capi.TS_E_INVALID, lambda: hip.astar_batch(bad))
+    assert "7" in str(ex)
     assert counters_dict(hip) == c0
     off1, xy1 = hip.astar_batch_fetch()
     assert np.array_equal(off0, off1) and np.array_equal(xy0, xy1)
     bad = q.copy()
     bad[4, 6] = 5000
-    with pytest.raises(capi.EngineError) as ex:
-        hip.astar_batch(bad)
-    assert ex.value.code == capi.TS_E_UNSUPPORTED and "4" in str(ex.value)
+    ex, = refused(capi.TS_E_UNSUPPORTED, lambda: hip.astar_batch(bad))
+    assert "4" in str(ex)
     assert counters_dict(hip) == c0
     off1, xy1 = hip.astar_batch_fetch()
     assert np.array_equal(off0, off1) and np.array_equal(xy0, xy1)
@@ -364,20 +352,12 @@ def test_refusals(hip):
     assert off.tolist() == [0] and xy.shape == (0, 2)
     hip.astar_batch(q)
     hip.step(1)
-    with pytest.raises(capi.EngineError) as ex:
-        hip.astar_batch_fetch()
-    assert ex.value.code == capi.TS_E_INVALID
-    with pytest.raises(capi.EngineError) as ex:
-        hip.astar_batch_device()
-    assert ex.value.code == capi.TS_E_INVALID
+    refused(capi.TS_E_INVALID, hip.astar_batch_fetch)
+    refused(capi.TS_E_INVALID, hip.astar_batch_device)
 
 
 # ---- 7. the device result and the facade ---------------------------------------------------------------------------------
 DEVICE_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
-import torch                     # (first: the engine library then shares torch's HIP runtime, as under torch.distributed.run)
-torch.cuda.init()
 import numpy as np
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd._lib import new_engine
@@ -395,29 +375,18 @@ assert np.array_equal(d_off.cpu().numpy(), off) and np.array_equal(d_xy.cpu().nu
 lens = d_off[1:] - d_off[:-1]          # the payload is usable where it lies
 assert int(lens.sum().item()) == xy.shape[0]
 api.close()
-print("DEVICE_OK")
 '''
 
 
-def test_device_tensors(golden_dir, tmp_path):
+def test_device_tensors(golden_dir):
     """astar_batch_device(): torch tensors over the engine's own memory, equal to the fetched arrays.  In a process of its
     own that imports torch before it loads the engine, the way the torch-side callers (dist.py) run."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = tmp_path / "device_tensors.py"
-    script.write_text(DEVICE_SCRIPT % dict(root=root, golden=golden_dir))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(DEVICE_SCRIPT, torch_first=True, timeout=300, golden=golden_dir)
 
 
 def test_facade_find_paths():
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
-    from run_city import TRAFFIC
     from trafficsimulation_amd import pathfinding
-    from trafficsimulation_amd.mesa_api import CityModel
-    m = CityModel(200, 200, seed=1, traffic=dict(TRAFFIC))
+    m = city_model(200, seed=1)
     try:
         for _ in range(30):
             m.step()

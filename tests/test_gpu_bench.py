@@ -2,24 +2,21 @@
 --dump-outputs files equal the CPU oracle's state after the same warm-up + timed ticks, and a --full run."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import bench
+from tests import procs
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--size", "512", "--vehicles", "12000"]
 
 
 def _run(*extra):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *SMALL, *extra],
-                         capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+    out = procs.run([sys.executable, os.path.join(procs.ROOT, "bench.py"), "--gpus", "1", *SMALL, *extra], timeout=600)
     return json.loads([line for line in out.stdout.splitlines() if line.startswith("{")][-1])
 
 

@@ -1,20 +1,17 @@
 """CityModel checkpoints: copy.deepcopy, pickle and save / CityModel.load give a second model with an engine of its own
 that continues the run exactly."""
 import copy
-import os
 import pickle
-import sys
 
 import numpy as np
 import pytest
 
+from tests.engine_util import city_model
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import worldgen
 from trafficsimulation_amd.mesa_api import CityModel, VehicleAgent
 
 pytestmark = pytest.mark.gpu
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 
 
 def snapshot(m):
@@ -41,8 +38,7 @@ def assert_same(a, b, ctx):
 
 @pytest.fixture(scope="module")
 def model():
-    from run_city import TRAFFIC
-    m = CityModel(200, 200, seed=1, traffic=dict(TRAFFIC))
+    m = city_model(200, seed=1)
     # one vehicle of the caller's own, so that the custom-id map has something to carry
     ents, exits = m.get_start_blocks(), m.get_exit_blocks()
     VehicleAgent("my_car", m, ents[0], exits[-1], population_type="internal")

@@ -4,16 +4,14 @@ serpentine that crosses tile borders far more often than there are tiles, agains
 a run that a compute does not change, and the refusals.  Every comparison is of exact integers."""
 import ctypes
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import costfield_expect as ce
-from tests.test_gpu_observe import assert_same_state, engine_for, full_state
-from tests.test_oracle_kats import cost_kats
+from tests import procs
+from tests.engine_util import assert_same_state, engine_for, full_state, refused
+from tests.kats_util import cost_kats
 from tests.trace_util import setup_from_trace, trace_path
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import costfield as cf
@@ -22,7 +20,6 @@ from trafficsimulation_amd.world import load_trace
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILES = (8, 16, 32)
 UNBOUNDED = 0x7FFFFFFF
 
@@ -260,17 +257,9 @@ def test_gather_bands_and_max_cost_equal_numpy(golden_dir, monkeypatch):
 
 
 DEVICE_SCRIPT = r'''
-import sys
-sys.path.insert(0, %(root)r)
-import torch                     # (first: the engine library then shares torch's HIP runtime)
-torch.cuda.init()
 import numpy as np
-from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
-from tests.trace_util import setup_from_trace, trace_path
-tr = load_trace(trace_path("full_96_s8"))
-api = new_engine()
-setup_from_trace(api, tr)
+from tests.engine_util import engine_for
+api, _ = engine_for("full_96_s8")
 api.step(5)
 c = api.costfield
 c.compute([(40, 40), (10, 70)], [0, 2], mode="to")
@@ -279,16 +268,12 @@ for which, dt in (("cost", np.uint32), ("owner", np.int32)):
     assert t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (api.H, api.W)
     assert np.array_equal(t.cpu().numpy().view(dt), c.plane(which))
 api.close()
-print("DEVICE_OK")
 '''
 
 
-def test_device_planes(tmp_path):
+def test_device_planes():
     """costfield.device(), in a process of its own that imports torch before it loads the engine."""
-    script = tmp_path / "costfield_device.py"
-    script.write_text(DEVICE_SCRIPT % dict(root=ROOT))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(DEVICE_SCRIPT, torch_first=True, timeout=300)
 
 
 # ---- 6. a compute changes nothing -----------------------------------------------------------------------------------------------
@@ -344,10 +329,7 @@ def test_refusals_leave_the_previous_result(golden_dir, monkeypatch):
     assert (empty["width"], empty["height"]) == (api.W, api.H)
     c.release()                                                # TS_OK without a result
     reads = (lambda: c.plane("cost"), lambda: c.plane("owner"), lambda: c.gather("cost", [(1, 1)]), lambda: c.bands([5]), c.device)
-    for read in reads:
-        with pytest.raises(capi.EngineError) as ex:
-            read()
-        assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, *reads)
     two = seed_sets(tables)["eight"][0][:2]
     info = c.compute(two, [1, 0], mode="from", soft=True, ignore_flow=True)
     value, owner = c.plane("cost"), c.plane("owner")
@@ -387,10 +369,7 @@ def test_refusals_leave_the_previous_result(golden_dir, monkeypatch):
     assert unchanged()
     c.release()
     assert c.info() == empty
-    for read in reads:
-        with pytest.raises(capi.EngineError) as ex:
-            read()
-        assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, *reads)
     c.release()
     api.close()
 
@@ -403,12 +382,9 @@ def test_unsupported_parameters_and_awareness(golden_dir, monkeypatch):
     api.close()
     # penalties that are no multiples of 0.5: the kernels do not carry them
     quarter, _, _ = kat_engine(golden_dir, "quarter", "a")
-    with pytest.raises(capi.EngineError) as ex:
-        quarter.costfield.compute([(20, 20)], mode="to")
-    assert ex.value.code == capi.TS_E_UNSUPPORTED
-    with pytest.raises(capi.EngineError) as ex:
-        quarter.costfield.compute([(20, 20)], mode="to", free_flow=True)
-    assert ex.value.code == capi.TS_E_UNSUPPORTED and quarter.costfield.info()["n_seeds"] == 0
+    refused(capi.TS_E_UNSUPPORTED, lambda: quarter.costfield.compute([(20, 20)], mode="to"),
+            lambda: quarter.costfield.compute([(20, 20)], mode="to", free_flow=True))
+    assert quarter.costfield.info()["n_seeds"] == 0
     quarter.close()
     # field-of-view masking: free-flow fields only, and those are the free-flow fields of an engine without it
     k = cost_kats(golden_dir)
@@ -421,9 +397,7 @@ def test_unsupported_parameters_and_awareness(golden_dir, monkeypatch):
     free = fov.costfield.compute([(20, 20)], mode="to", free_flow=True)
     held = fov.costfield.plane("cost")
     for kw in (dict(soft=True), dict(soft=False), dict(soft=True, ignore_flow=True)):
-        with pytest.raises(capi.EngineError) as ex:
-            fov.costfield.compute([(20, 20)], mode="to", **kw)
-        assert ex.value.code == capi.TS_E_UNSUPPORTED
+        refused(capi.TS_E_UNSUPPORTED, lambda: fov.costfield.compute([(20, 20)], mode="to", **kw))
         assert fov.costfield.info() == free and np.array_equal(fov.costfield.plane("cost"), held)
     rule = rule_of(fov, pf, tables)
     assert np.array_equal(held, ce.field(rule, [(20, 20)], mode="to", free_flow=True)[0])

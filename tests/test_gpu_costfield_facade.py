@@ -1,29 +1,24 @@
 """Cost fields through the Mesa-style facade: CityModel.cost_field(), catchments() and isochrones() on a seed-built city
 against the definition and against CApi, a catchment plane as the trip log's zones, and save / load / deepcopy."""
 import copy
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import costfield_expect as ce
+from tests.engine_util import city_model, refused, run_example
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import costfield as cf
 from trafficsimulation_amd.mesa_api import CityModel
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "examples"))
 TICKS = 20
 
 
 @pytest.fixture(scope="module")
 def city():
-    from run_city import TRAFFIC
-    m = CityModel(64, 64, seed=11, traffic=dict(TRAFFIC, P_int=200000, P_thr=60000), trip_log=4096)
+    m = city_model(64, seed=11, traffic=dict(P_int=200000, P_thr=60000), trip_log=4096)
     for _ in range(TICKS):
         m.step()
     yield m
@@ -97,9 +92,7 @@ def test_save_load_and_deepcopy_drop_the_result(city, tmp_path):
     m.save(path)
     for how, other in (("load", CityModel.load(path)), ("deepcopy", copy.deepcopy(m))):
         assert other.engine.costfield.info()["n_seeds"] == 0, f"{how}: a new engine starts without a result"
-        with pytest.raises(capi.EngineError) as ex:
-            other.engine.costfield.plane("cost")
-        assert ex.value.code == capi.TS_E_STATE
+        refused(capi.TS_E_STATE, lambda: other.engine.costfield.plane("cost"))
         got = other.cost_field([(30, 31)], mode="to")
         assert np.array_equal(got["cost"], want["cost"]) and np.array_equal(got["owner"], want["owner"]), how
         other.close()
@@ -108,8 +101,7 @@ def test_save_load_and_deepcopy_drop_the_result(city, tmp_path):
 
 def test_run_city_writes_the_cost_plane(tmp_path):
     out = tmp_path / "cost.npy"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "run_city.py"), "--size", "64", "--seed", "11", "--ticks", "20",
-                        "--isochrone", "30,31", str(out)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "cost to (30, 31):" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+    r = run_example("run_city.py", "--size", 64, "--seed", 11, "--ticks", 20, "--isochrone", "30,31", out)
+    assert "cost to (30, 31):" in r.stdout, r.stdout[-2000:]
     cost = np.load(out)
     assert cost.shape == (64, 64) and cost.dtype == np.uint32 and cost[31, 30] == 0 and (cost != cf.CF_UNREACHABLE).sum() > 100

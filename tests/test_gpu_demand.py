@@ -2,25 +2,20 @@
 (tests/demand_expect.py), against the observed ENTER planes, against download_path on traces that replan, vehicle selection,
 a run that a compute does not change, checkpoints, and the refusals."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import demand_expect as de
 from tests import observe_util as ou
+from tests import procs
+from tests.engine_util import assert_same_state, engine_for, full_state, refused
 from tests.ext_sidecar import check_query, read_planes
-from tests.test_gpu_observe import assert_same_state, engine_for, full_state
-from tests.trace_util import setup_from_trace, trace_path
+from tests.trace_util import setup_from_trace
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- 1. the fixture expectation, at the default chunk, the smallest and one above the longest path --------------------
@@ -121,25 +116,15 @@ def test_selection_by_a_host_mask():
     none = api.demand_compute(*q, select=np.zeros(n, dtype=np.uint8))
     assert none["vehicles"] == 0 and none["steps"] == 0 and none["bin_steps"] == [0] * 4 and not read_planes(api, 4).any()
     for bad in (n - 1, n + 1, 0):
-        with pytest.raises(capi.EngineError) as ex:
-            api.demand_compute(*q, select=np.ones(bad, dtype=np.uint8))
-        assert ex.value.code == capi.TS_E_INVALID
+        refused(capi.TS_E_INVALID, lambda: api.demand_compute(*q, select=np.ones(bad, dtype=np.uint8)))
         assert api.demand_info() == none and not read_planes(api, 4).any()          # the refused compute left the result alone
     api.close()
 
 
 DEVICE_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
-import torch                     # (first: the engine library then shares torch's HIP runtime)
-torch.cuda.init()
 import numpy as np
-from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
-from tests.trace_util import setup_from_trace, trace_path
-tr = load_trace(trace_path("full_96_s8"))
-api = new_engine()
-setup_from_trace(api, tr)
+from tests.engine_util import engine_for
+api, _ = engine_for("full_96_s8")
 api.step(25)
 n = api.num_spawned()
 mask = (np.arange(n) %% 3 != 0).astype(np.uint8)
@@ -161,17 +146,13 @@ for bad in (torch.ones(n + 1, dtype=torch.uint8, device=dev), torch.ones(n - 1, 
         assert getattr(ex, "code", None) == -1, ex
 assert api.demand_info() == host
 api.close()
-print("DEVICE_OK")
 '''
 
 
-def test_selection_by_a_device_mask_and_device_planes(tmp_path):
+def test_selection_by_a_device_mask_and_device_planes():
     """demand_compute(select=torch tensor) and demand_device(), in a process of its own that imports torch before it loads the
     engine."""
-    script = tmp_path / "demand_device.py"
-    script.write_text(DEVICE_SCRIPT % dict(root=ROOT))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(DEVICE_SCRIPT, torch_first=True, timeout=300)
 
 
 # ---- 5. a compute changes nothing; checkpoints ----------------------------------------------------------------------------
@@ -211,9 +192,7 @@ def test_checkpoints_carry_no_result_and_loads_leave_it_alone():
     setup_from_trace(c, tr)
     c.checkpoint_load(blob)
     assert c.demand_info()["n_bins"] == 0
-    with pytest.raises(capi.EngineError) as ex:
-        c.demand_plane()
-    assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, c.demand_plane)
     for e in (a, b, c):
         e.close()
 
@@ -234,10 +213,7 @@ def test_refusals_leave_the_previous_result_alone():
     assert (empty["n_bins"], empty["steps"], empty["vehicles"], empty["device_bytes"], empty["bin_steps"]) == (0, 0, 0, 0, [])
     assert (empty["width"], empty["height"]) == (W, H)
     api.demand_release()                                       # TS_OK without a result
-    for read in (api.demand_plane, lambda: api.demand_plane(0, 2), lambda: api.demand_pooled(4), api.demand_groups, api.demand_device):
-        with pytest.raises(capi.EngineError) as ex:
-            read()
-        assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, api.demand_plane, lambda: api.demand_plane(0, 2), lambda: api.demand_pooled(4), api.demand_groups, api.demand_device)
     api.step(7)
     info = api.demand_compute(3, 5, False)
     planes = read_planes(api, 3)
@@ -272,9 +248,7 @@ def test_refusals_leave_the_previous_result_alone():
     assert big["steps"] == de.remaining_steps(veh) and np.array_equal(read_planes(api, 1), de.planes(H, W, veh))
     api.demand_release()
     assert api.demand_info() == empty
-    with pytest.raises(capi.EngineError) as ex:
-        api.demand_plane()
-    assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, api.demand_plane)
     api.demand_release()
     api.step(1)
     api.close()

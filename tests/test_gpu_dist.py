@@ -4,30 +4,21 @@ every rank plans half of each tick's searches, the results are exchanged, and BO
 recorded state at every tick - i.e. the N-rank result equals the 1-GPU result bit for bit."""
 import json
 import os
-import re
-import subprocess
 import sys
-import tempfile
 
 import pytest
 
+from tests import procs
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 WORKER = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
-from trafficsimulation_amd import dist as tdist
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd._lib import new_engine
 from trafficsimulation_amd.world import load_trace
 from tests.trace_util import setup_from_trace, check_initial, replay_and_compare, trace_path
-rank, local, world = tdist.env_rank()
 os.environ.update(%(rank_env)r.get(rank, {}))      # (this rank's own engine settings, read when its engine plans)
-d = tdist.init("gloo", rank, world)
-res = {}
 for name in %(traces)r:
     tr = load_trace(trace_path(name))
     api = new_engine()
@@ -44,9 +35,6 @@ for name in %(traces)r:
                      exchanges=sr.calls, bytes=sr.bytes_sent, fp=list(api.rng_fingerprint(capi.RNG_GLOBAL)),
                      quad_jobs=api.debug_quad_stats()["jobs"])
     api.close()
-with open(os.path.join(%(outdir)r, "rank%%d.json" %% rank), "w") as f:      # (one file per rank: lines printed to the
-    json.dump(dict(rank=rank, res=res), f)                                  # shared stdout of the ranks can interleave)
-d.destroy_process_group()
 '''
 
 
@@ -58,13 +46,12 @@ def test_ranks_sharded_replans_match_the_reference(world, device_direct, tight_p
     # closed populations, then the agents that step on the host inside the shuffled order (traffic generator spawning and
     # planning mid-tick, service vehicles with their arrival records, rain): every rank runs those redundantly
     traces = TRACES_2 if world == 2 else TRACES_N
-    port = str(29541 + world + (10 if device_direct else 0) + (20 if tight_pool else 0) + (40 if quads else 0))
     env = {}
     if quads:           # (every rank's share of every queue on k_replan_quad, its hand-backs on k_replan beside it)
         env["TS_QUAD"], env["TS_QUAD_MIN"] = "1", "1"
     if tight_pool:      # (almost no room reserved in the path pool: planners find it full, the pool is garbage-collected / grown INSIDE the
         env["TS_DEBUG_POOL_PER_ENTRY"] = "2"      # sharded tick, and the export must not rely on the pool's growth to size its buffer)
-    _run_ranks_and_check(world, device_direct, traces, port, env, {})
+    _run_ranks_and_check(world, device_direct, traces, env, {})
 
 
 TRACES_2 = ["full_64_s1", "full_96_s8", "faults_64_s9", "carve_96_s10", "dta_64_s12", "rain_96_s14", "config1_64_s11", "despawn_96_s25", "startgoal_96_s27"]
@@ -82,51 +69,38 @@ def test_ranks_that_plan_on_different_searchers_match_the_reference(rank0_classe
     rank_env = {0: {"TS_QUAD": "1", "TS_QUAD_MIN": "1"}, 1: {"TS_QUAD": "0"}}
     if rank0_classes:
         rank_env[0]["TS_QUAD_CLASSES"] = rank0_classes
-    port = str(29661 + (1 if rank0_classes else 0))
-    rows = _run_ranks_and_check(2, True, TRACES_2, port, {}, rank_env)
-    assert sum(rows[0]["res"][name]["quad_jobs"] for name in TRACES_2) > 0          # rank 0 did plan on the quads ...
-    assert all(rows[1]["res"][name]["quad_jobs"] == 0 for name in TRACES_2)         # ... and rank 1 never
+    rows = _run_ranks_and_check(2, True, TRACES_2, {}, rank_env)
+    assert sum(rows[0][name]["quad_jobs"] for name in TRACES_2) > 0          # rank 0 did plan on the quads ...
+    assert all(rows[1][name]["quad_jobs"] == 0 for name in TRACES_2)         # ... and rank 1 never
 
 
-def _run_ranks_and_check(world, device_direct, traces, port, env_all, rank_env):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0", **env_all)
-    with tempfile.TemporaryDirectory() as outdir:
-        path = os.path.join(outdir, "worker.py")
-        with open(path, "w") as f:
-            f.write(WORKER % dict(root=ROOT, traces=traces, device_direct=device_direct, outdir=outdir, rank_env=rank_env))
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-               "--master-addr", "127.0.0.1", "--master-port", port, path]
-        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
-        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
-        rows = [json.load(open(os.path.join(outdir, n))) for n in sorted(os.listdir(outdir)) if n.startswith("rank")]
-    assert sorted(r["rank"] for r in rows) == list(range(world))
-    rows = sorted(rows, key=lambda r: r["rank"])
+def _run_ranks_and_check(world, device_direct, traces, env_all, rank_env):
+    rows, _, _ = procs.run_ranks(WORKER, world, env=dict(os.environ, **env_all), timeout=900, traces=traces, device_direct=device_direct,
+                                 rank_env=rank_env)
     r0 = rows[0]
     for name in traces:
-        a = r0["res"][name]
+        a = r0[name]
         for rb in rows[1:]:
-            b = rb["res"][name]
+            b = rb[name]
             assert a["ticks"] == b["ticks"] > 0
             if name != "config1_64_s11":     # (service vehicles plan inside the generator's step too: not in the fixture's per-tick count)
                 assert a["astar_calls"] == b["astar_calls"] == a["want_calls"]     # the searches of all ranks add up to the reference's
             assert a["astar_calls"] == b["astar_calls"]
             assert a["fp"] == b["fp"]
             assert a["exchanges"] == b["exchanges"] > 0
-        assert sum(rb["res"][name]["bytes"] for rb in rows) > 0
+        assert sum(rb[name]["bytes"] for rb in rows) > 0
         if world == 2:
-            assert all(rb["res"][name]["bytes"] > 0 for rb in rows)       # both ranks planned something
+            assert all(rb[name]["bytes"] > 0 for rb in rows)       # both ranks planned something
     return rows
 
 
 NCCL_WORKER = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
 import torch
 import torch.distributed as dist
 from trafficsimulation_amd import dist as tdist
 torch.cuda.set_device(0)
-dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%(port)d", rank=0, world_size=1, device_id=torch.device("cuda", 0))
 sr = tdist.ShardedReplans(device=torch.device("cuda", 0))
 ok = True
 for n in (0, 1, 4097, 3_000_000):
@@ -149,26 +123,18 @@ def test_exchange_collective_over_rccl():
     """The same exchange object on a real RCCL process group (backend "nccl", buffers staged through the GPU).  One rank
     only - this box has one GPU and RCCL refuses two ranks on a device - so this checks the device staging, the padded
     all_gather and the callback plumbing, not the wire."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29543", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    with tempfile.NamedTemporaryFile("w", suffix=".py", delete=False) as f:
-        f.write(NCCL_WORKER % dict(root=ROOT))
-        path = f.name
-    out = subprocess.run([sys.executable, path], env=env, capture_output=True, text=True, timeout=600)
-    os.unlink(path)
-    assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+    out = procs.run_python(NCCL_WORKER, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), timeout=600, port=procs.free_port())
     row = json.loads([line for line in out.stdout.splitlines() if line.startswith("{")][-1])
     assert row["ok"] and row["backend"] == "nccl" and row["calls"] == 5
-
 
 
 def test_bench_two_ranks_over_gloo_smoke():
     """`python bench.py --gpus 2` end to end on this box's one GPU (gloo, sharded replans, device-direct exchange): the line
     reports the process group's size and that both ranks ended in the same state."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "512", "--vehicles", "12000",
+    cmd = [sys.executable, os.path.join(procs.ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "512", "--vehicles", "12000",
            "--steps", "4", "--warmup", "4", "--full", "--no-cpu-baseline", "--no-secondary"]
-    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+    out = procs.run(cmd, env=env, timeout=600)
     row = json.loads([line for line in out.stdout.splitlines() if line.startswith("{")][-1])
     assert row["n_gpus"] == 2 and row["scaling"] == "strong"
     assert row["config"]["ranks_hold_identical_state"] is True

@@ -12,17 +12,17 @@ PATHFINDING_BATCHING=False, the traffic generator, two sharded ranks.
 import ctypes
 import json
 import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
 from tests import demand_expect as de
 from tests import ext_sidecar as xs
+from tests import lights_ext_expect as lx
+from tests import procs
 from tests import test_gpu_lights_ext as LE
-from tests.test_gpu_forced_paths import SMALL, small_engine
+from tests.engine_util import SMALL, refused, small_engine
+from tests.ext_sidecar import GENERATOR_PARKED_AT, GENERATOR_SPAWNED, GENERATOR_T, GENERATOR_TRACE, LIGHTS_EXT_FIXTURE, LIGHTS_PROTO_FIXTURE
 from tests.trace_util import setup_from_trace, trace_path
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd._lib import new_engine
@@ -30,12 +30,8 @@ from trafficsimulation_amd.world import load_trace
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWITCHES = ("TS_QUAD", "TS_QUAD_MIN", "TS_DEBUG_POOL_PER_ENTRY", "TS_DEBUG_POOL_GC")
 EXPLICIT = {"carfollow_128_s3"}                       # replayed on its recorded spawn-time paths: the exact fixture expectation
-# config1_64_s11 (ext_sidecar.generator_ticks, pinned on the CPU by tests/test_ext_sidecar.py): by tick 260 the rows show 102
-# vehicles spawned (50 were placed before tick 0) and a service vehicle parked after tick 225
-GENERATOR_TRACE, GENERATOR_T, GENERATOR_SPAWNED, GENERATOR_PARKED_AT = "config1_64_s11", 260, 102, 225
 SHARDED_TRACES = ["full_96_s8", "startgoal_96_s27"]
 
 
@@ -177,62 +173,26 @@ def test_generator(default_mode):
     planes = xs.read_planes(api, 4)
     assert np.array_equal(planes, de.planes(H, W, picked, 4, 16, True))
     assert info["selected"] and info["vehicles"] == len(picked) and info["steps"] == de.remaining_steps(picked) > 0
-    with pytest.raises(capi.EngineError) as ex:            # the length the mask had before the generator's spawns
-        api.demand_compute(*q, select=np.ones(n0, dtype=np.uint8))
-    assert ex.value.code == capi.TS_E_INVALID
+    refused(capi.TS_E_INVALID, lambda: api.demand_compute(*q, select=np.ones(n0, dtype=np.uint8)))     # the length the mask had before the generator's spawns
     assert api.demand_info() == info and np.array_equal(xs.read_planes(api, 4), planes), "the refused compute touched the result"
 
 
 SHARDED_WORKER = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
 import torch
-from trafficsimulation_amd import dist as tdist
-from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
 from tests import ext_sidecar as xs
-from tests.trace_util import setup_from_trace, trace_path
-rank, local, world = tdist.env_rank()
-d = tdist.init("gloo", rank, world)
-res = {}
+from tests.engine_util import engine_for
 for name in %(traces)r:
-    tr = load_trace(trace_path(name))
-    api = new_engine()
-    setup_from_trace(api, tr, explicit_paths=False)
+    api, tr = engine_for(name)
     sr = tdist.ShardedReplans(device=torch.device("cuda", 0), device_direct=True).attach(api)
     api.profile_enable(True)
     sc = xs.Sidecar(api, tr)
     flat = xs.flatten(xs.run_trace(api, tr, xs.ticks_of(tr), sc))      # (every rank runs the in-mode rules on imported paths)
-    np.savez(os.path.join(%(outdir)r, "bundles_%%s_%%d.npz" %% (name, rank)), **flat)
+    np.savez(os.path.join(OUTDIR, "bundles_%%s_%%d.npz" %% (name, rank)), **flat)
     res[name] = dict(exchanges=sr.calls, bytes=sr.bytes_sent, check_ticks=sc.stats["checks"], paths_compared=sc.stats["paths"],
                      pool_gc=int(api.profile()["pool_gc"][1]), astar_calls=int(api.counters().astar_calls))
     api.close()
-with open(os.path.join(%(outdir)r, "rank%%d.json" %% rank), "w") as f:
-    json.dump(res, f)
-d.destroy_process_group()
 '''
-
-
-def run_ranks(worker, port, env_more, **fmt):
-    """Two ranks of `worker` over gloo on this box's one GPU: ([rank 0's JSON, rank 1's], {file name: arrays} of the .npz
-    files they left)."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0", **env_more)
-    with tempfile.TemporaryDirectory() as outdir:
-        path = os.path.join(outdir, "worker.py")
-        with open(path, "w") as f:
-            f.write(worker % dict(root=ROOT, outdir=outdir, **fmt))
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-               "--master-addr", "127.0.0.1", "--master-port", port, path]
-        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
-        ranks = [json.load(open(os.path.join(outdir, f"rank{r}.json"))) for r in range(2)]
-        saved = {}
-        for n in sorted(os.listdir(outdir)):
-            if n.endswith(".npz"):
-                with np.load(os.path.join(outdir, n)) as z:
-                    saved[n] = {k: z[k] for k in z.files}
-    return ranks, saved
 
 
 @pytest.mark.parametrize("gc", [False, True])
@@ -240,7 +200,7 @@ def test_sharded2(default_mode, gc):
     """Two ranks, records exchanged between device buffers: each rank plans half of every queue and imports the other half
     (k_replan_import: re-allocated words, path_cur = 0); with gc the pool is also collected at every tick and replan."""
     traces = ["full_96_s8"] if gc else SHARDED_TRACES
-    ranks, saved = run_ranks(SHARDED_WORKER, "29772" if gc else "29771", {"TS_DEBUG_POOL_GC": "1"} if gc else {}, traces=traces)
+    ranks, saved, _ = procs.run_ranks(SHARDED_WORKER, 2, env=dict(os.environ, **({"TS_DEBUG_POOL_GC": "1"} if gc else {})), timeout=600, traces=traces)
     for name in traces:
         want = default_mode(name)[3]
         tr = default_mode(name)[1]
@@ -254,20 +214,9 @@ def test_sharded2(default_mode, gc):
 
 
 # ---- 2. external light control and the protocols on the other paths -------------------------------------------------------
-# the fixtures of each family in whose recorded runs searches run inside ticks (ext_sidecar.light_fixtures_with_searches,
-# pinned on the CPU by tests/test_ext_sidecar.py); the GAT one is driven through act_q, whose epsilon-greedy draws come from
-# the global stream on the host
-LIGHTS_EXT_FIXTURE, LIGHTS_PROTO_FIXTURE = "lights_ext_stuck_96_s43", "lights_gat_96_s49"
-
 LIGHTS_WORKER = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
 import torch
-from trafficsimulation_amd import dist as tdist
 from tests import test_gpu_lights_ext as LE, test_gpu_lights_proto as LP
-rank, local, world = tdist.env_rank()
-d = tdist.init("gloo", rank, world)
-res = {}
 for mod, name in ((LE, %(ext)r), (LP, %(proto)r)):
     made = []
     plain = mod.new_engine
@@ -292,16 +241,13 @@ for mod, name in ((LE, %(ext)r), (LP, %(proto)r)):
     mod.new_engine = plain
     (api, sr), calls = made
     res[name] = dict(exchanges=sr.calls, bytes=sr.bytes_sent, astar_calls=calls)
-with open(os.path.join(%(outdir)r, "rank%%d.json" %% rank), "w") as f:
-    json.dump(res, f)
-d.destroy_process_group()
 '''
 
 
 def test_light_control_fixtures_on_two_sharded_ranks():
-    chosen = xs.light_fixtures_with_searches(LE.FIXTURES), xs.light_fixtures_with_searches(["lights_gat_64_s45", "lights_gat_96_s49"])
+    chosen = xs.light_fixtures_with_searches(lx.FIXTURES), xs.light_fixtures_with_searches(["lights_gat_64_s45", "lights_gat_96_s49"])
     assert chosen == ([LIGHTS_EXT_FIXTURE], [LIGHTS_PROTO_FIXTURE])
-    ranks, _ = run_ranks(LIGHTS_WORKER, "29773", {}, ext=LIGHTS_EXT_FIXTURE, proto=LIGHTS_PROTO_FIXTURE)
+    ranks, _, _ = procs.run_ranks(LIGHTS_WORKER, 2, timeout=600, ext=LIGHTS_EXT_FIXTURE, proto=LIGHTS_PROTO_FIXTURE)
     for name in (LIGHTS_EXT_FIXTURE, LIGHTS_PROTO_FIXTURE):
         tr = load_trace(trace_path(name))
         for r in range(2):

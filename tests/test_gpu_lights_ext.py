@@ -7,13 +7,14 @@
 4. observe is idempotent, act without observe equals observe then act;
 5. checkpoints carry the controller state; 6. device tensors; 7. refusals."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import lights_ext_expect as lx
+from tests.lights_ext_expect import FIXTURES, GATED, Stepper
+from tests import procs
+from tests.engine_util import refused
 from tests.trace_util import check_initial, replay_and_compare, setup_from_trace, trace_path
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd._lib import new_engine
@@ -21,37 +22,11 @@ from trafficsimulation_amd.world import build_engine, load_trace
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURES = ["lights_ext_64_s45", "lights_ext_96_s42", "lights_ext_stuck_96_s43"]
-GATED = {"PATHFINDING_COOLDOWN": 10 ** 9, "VEHICLE_STUCK_RECOMPUTE_THRESHOLD": 10 ** 9,
-         "VEHICLE_STUCK_RECOMPUTE_THRESHOLD_INTERSECTION": 10 ** 9, "VEHICLE_CONTRAFLOW_OVERTAKE_ACTIVE": False,
-         "VEHICLE_STUCK_CONTRAFLOW_ENABLED": False}
-
-
 STUCK_SOON = {"PATHFINDING_COOLDOWN": 5, "VEHICLE_STUCK_RECOMPUTE_THRESHOLD": 2, "VEHICLE_STUCK_RECOMPUTE_THRESHOLD_INTERSECTION": 1}
 
 
 def same_bits(a, b):
     return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-class Stepper:
-    """An engine whose step(1) first does `before(tick)`; everything else is the engine's.  `groups` may be overridden."""
-
-    def __init__(self, api, before, groups=None):
-        self._api, self._before, self._groups, self.tick = api, before, groups, 0
-
-    def __getattr__(self, name):
-        return getattr(self._api, name)
-
-    def step(self, n=1):
-        for _ in range(n):
-            self._before(self.tick)
-            self._api.step(1)
-            self.tick += 1
-
-    def groups(self):
-        return self._groups(self.tick - 1, self._api.groups()) if self._groups else self._api.groups()
 
 
 # ---- 1. the reference's own controller runs ------------------------------------------------------------------------------
@@ -260,9 +235,8 @@ def test_checkpoint_refuses_another_configuration():
             b.lights_act(tr["rl_action"][t])
             b.step(1)
         before = b.checkpoint_save()
-        with pytest.raises(capi.EngineError) as ex:
-            b.checkpoint_load(blob)
-        assert ex.value.code == capi.TS_E_INVALID and "min-green" in str(ex.value)
+        ex, = refused(capi.TS_E_INVALID, lambda: b.checkpoint_load(blob))
+        assert "min-green" in str(ex)
         assert b.checkpoint_save() == before, "a refused load changed the target"
         b.close()
     a.close()
@@ -298,10 +272,6 @@ def test_blob_sizes_follow_the_format():
 
 # ---- 6. device tensors -----------------------------------------------------------------------------------------------------
 DEVICE_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
-import torch                     # (first: the engine library then shares torch's HIP runtime)
-torch.cuda.init()
 import numpy as np
 from trafficsimulation_amd._lib import new_engine
 from trafficsimulation_amd.world import load_trace
@@ -339,16 +309,12 @@ except Exception as ex:
     assert getattr(ex, "code", None) == -1, ex
 assert a.checkpoint_save() == before
 a.close(); b.close()
-print("DEVICE_OK")
 '''
 
 
-def test_device_tensors_and_device_actions(tmp_path):
+def test_device_tensors_and_device_actions():
     """lights_device() and lights_act(torch tensor), in a process of its own that imports torch before it loads the engine."""
-    script = tmp_path / "lights_device.py"
-    script.write_text(DEVICE_SCRIPT % dict(root=ROOT))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(DEVICE_SCRIPT, torch_first=True, timeout=300)
 
 
 # ---- 7. refusals -----------------------------------------------------------------------------------------------------------
@@ -356,11 +322,8 @@ def test_every_entry_is_unsupported_under_another_algorithm():
     api = new_engine()
     setup_from_trace(api, load_trace(trace_path("lights_qa_96_s2")))
     z = np.zeros(api.n_groups, np.int8)
-    for call in (lambda: api.lights_config(13, 5), lambda: api.lights_set_static(np.zeros(api.n_groups), None), api.lights_info,
-                 api.lights_observe, lambda: api.lights_act(z), lambda: api.lights_request(z), api.lights_controller):
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_UNSUPPORTED
+    refused(capi.TS_E_UNSUPPORTED, lambda: api.lights_config(13, 5), lambda: api.lights_set_static(np.zeros(api.n_groups), None), api.lights_info,
+            api.lights_observe, lambda: api.lights_act(z), lambda: api.lights_request(z), api.lights_controller)
     api.step(2)
     api.close()
 
@@ -374,19 +337,11 @@ def test_bad_arguments_change_nothing():
     before = api.checkpoint_save()
     bad_actions = [np.full(G, 2, np.int8), np.concatenate([np.zeros(G - 1, np.int8), [-1]]).astype(np.int8)]
     for v in bad_actions:
-        with pytest.raises(capi.EngineError) as ex:
-            api.lights_act(v)
-        assert ex.value.code == capi.TS_E_INVALID
-    with pytest.raises(capi.EngineError) as ex:
-        api.lights_request(np.full(G, -2, np.int8))
-    assert ex.value.code == capi.TS_E_INVALID
+        refused(capi.TS_E_INVALID, lambda: api.lights_act(v))
+    refused(capi.TS_E_INVALID, lambda: api.lights_request(np.full(G, -2, np.int8)))
     for dim, mg in ((12, 5), (19, -1)):
-        with pytest.raises(capi.EngineError) as ex:
-            api.lights_config(dim, mg)
-        assert ex.value.code == capi.TS_E_INVALID
-    with pytest.raises(capi.EngineError) as ex:         # a valid configuration, but control calls have been made
-        api.lights_config(13, 5)
-    assert ex.value.code == capi.TS_E_STATE
+        refused(capi.TS_E_INVALID, lambda: api.lights_config(dim, mg))
+    refused(capi.TS_E_STATE, lambda: api.lights_config(13, 5))     # a valid configuration, but control calls have been made
     with pytest.raises(ValueError):
         api.lights_act(np.zeros(G + 1, np.int8))
     assert api.checkpoint_save() == before and api.lights_info()["observed"] == 0

@@ -1,29 +1,24 @@
 """External light control through the Mesa-style facade: light_states / control_lights / request_phases, the controller
 columns on the group views, save / load / deepcopy / pickle in the middle of a controlled run, and examples/train_lights.py."""
 import copy
-import os
 import pickle
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import lights_ext_expect as lx
+from tests.engine_util import city_model, run_example
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd.mesa_api import CityModel
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "examples"))
 DIM = 17
 
 
 def make_model():
-    from run_city import TRAFFIC
-    return CityModel(96, 96, seed=42, traffic=dict(TRAFFIC, P_int=30000, P_thr=8000),
-                     defaults={"TRAFFIC_LIGHT_AGENT_ALGORITHM": "NEIGHBOR_RL_BATCHED", "SRL_INPUT_DIMENSIONS": DIM, "RAIN_ENABLED": False})
+    return city_model(96, seed=42, traffic=dict(P_int=30000, P_thr=8000),
+                      defaults={"TRAFFIC_LIGHT_AGENT_ALGORITHM": "NEIGHBOR_RL_BATCHED", "SRL_INPUT_DIMENSIONS": DIM, "RAIN_ENABLED": False})
 
 
 def actions_for(t, G):
@@ -122,6 +117,5 @@ def test_pickle_and_save_load(model, tmp_path):
 
 
 def test_training_example_runs():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "train_lights.py"), "--size", "64", "--ticks", "20", "--every", "10"],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "TRAIN_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    r = run_example("train_lights.py", "--size", 64, "--ticks", 20, "--every", 10)
+    assert "TRAIN_OK" in r.stdout, r.stdout[-2000:]

@@ -10,17 +10,16 @@
 3. API behaviour: act draws nothing, observe is idempotent, the protocols are exclusive, checkpoints, refusals, device tensors.
 
 Rewards are compared bit for bit: the cached-stats comparison of tests/trace_util.py is exact, so the global term is too."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import lights_ext_expect as lx
 from tests import lights_proto_expect as lp
-from tests.test_gpu_lights_ext import GATED, Stepper
+from tests import procs
+from tests.engine_util import proto_engine, refused, setup_proto
+from tests.lights_ext_expect import GATED, Stepper
 from tests.trace_util import check_initial, replay_and_compare, trace_path
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd._lib import new_engine
@@ -28,7 +27,6 @@ from trafficsimulation_amd.world import build_engine, load_trace
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = ["lights_a2c_64_s45", "lights_a2c_96_s47", "lights_gat_64_s45", "lights_gat_96_s49"]
 STAT_KEYS = ("avg_duration_internal", "avg_duration_through", "avg_time_per_unit_internal", "avg_time_per_unit_through")
 
@@ -37,27 +35,8 @@ def same_bits(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
-def setup_proto(api, tr, defaults=None):
-    """Like trace_util.setup_from_trace, with the traffic generator always armed: the reference's model has one under a closed
-    population too, and its cached_stats (over the vehicles placed by hand) feed the GAT reward."""
-    dta = json.loads(str(tr["dta_params"]))
-    build_engine(api, tr, defaults=defaults or tr["defaults_json"], global_state=tr["global_rng_before_day0"],
-                 sched_state=tr["sched_rng_initial"])
-    api.set_traffic_generator(tr, internal_per_day=dta["P_int"], passing_per_day=dta["P_thr"],
-                              start_offset_seconds=dta["start_offset"], service=dta)
-    want = np.asarray(tr["global_rng_after_worldgen"], dtype=np.uint64)
-    got = api.rng_state(capi.RNG_GLOBAL)
-    assert got[1] == int(want[624]) and np.array_equal(got[0], want[:624].astype(np.uint32)), "day-0 trip generation"
-    n = len(tr["v_start_xy"])
-    api.add_vehicles(tr["v_start_xy"], tr["v_goal_xy"], np.full(n, capi.POP["through"], dtype=np.int32))
-    return api
-
-
 def fixture_engine(name, **over):
-    tr = load_trace(trace_path(name))
-    api = new_engine()
-    setup_proto(api, tr, {**tr["defaults_json"], **over} if over else None)
-    return api, tr
+    return proto_engine(name, new_engine, **over)      # (this module's new_engine: the sharded-rank worker replaces it)
 
 
 # ---- 1. the reference's own controller runs ------------------------------------------------------------------------------
@@ -189,11 +168,8 @@ def test_act_under_gat_draws_nothing_and_observe_is_idempotent():
 def test_the_protocols_are_exclusive():
     api, tr = fixture_engine("lights_a2c_64_s45")
     z = np.zeros(api.n_groups, np.int8)
-    for call in (lambda: api.lights_config(13, 5), api.lights_observe, lambda: api.lights_act(z),
-                 lambda: api.lights_proto_config("GAT_DQN_BATCHED"), lambda: api.lights_proto_act_q(np.zeros((api.n_groups, 2), np.float32))):
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, lambda: api.lights_config(13, 5), api.lights_observe, lambda: api.lights_act(z),
+            lambda: api.lights_proto_config("GAT_DQN_BATCHED"), lambda: api.lights_proto_act_q(np.zeros((api.n_groups, 2), np.float32)))
     api.lights_request(z)      # the shared entries keep working
     assert api.lights_info()["n_groups"] == api.n_groups and api.lights_controller().shape == (api.n_groups, 2)
     api.close()
@@ -201,14 +177,9 @@ def test_the_protocols_are_exclusive():
     b = new_engine()
     setup_proto(b, tr, {**tr["defaults_json"], "TRAFFIC_LIGHT_AGENT_ALGORITHM": "EXTERNAL"})
     assert b.lights_proto_info()["protocol"] == 0
-    for call in (b.lights_proto_observe, lambda: b.lights_proto_act(z)):      # no protocol configured
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, b.lights_proto_observe, lambda: b.lights_proto_act(z))      # no protocol configured
     b.lights_observe()
-    with pytest.raises(capi.EngineError) as ex:
-        b.lights_proto_config("RL_A2C_BATCHED")
-    assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, lambda: b.lights_proto_config("RL_A2C_BATCHED"))
     b.close()
 
 
@@ -245,13 +216,9 @@ def test_checkpoint_refuses_another_configuration():
     for over in others:
         b, _ = fixture_engine("lights_gat_64_s45", **over)
         before = b.checkpoint_save()
-        with pytest.raises(capi.EngineError) as ex:
-            b.checkpoint_load(blob)
-        assert ex.value.code == capi.TS_E_INVALID, over
+        refused(capi.TS_E_INVALID, lambda: b.checkpoint_load(blob))
         assert b.checkpoint_save() == before, "a refused load changed the target"
-        with pytest.raises(capi.EngineError) as ex:      # and the plain blob does not load onto the protocol's handle
-            a.checkpoint_load(before)
-        assert ex.value.code == capi.TS_E_INVALID, over
+        refused(capi.TS_E_INVALID, lambda: a.checkpoint_load(before))     # and the plain blob does not load onto the protocol's handle
         b.close()
     assert a.checkpoint_save() == blob
     a.close()
@@ -291,9 +258,8 @@ def test_checkpoint_refuses_a_bad_epsilon():
     for bad in (float("nan"), 1.5, -0.25):
         b = bytearray(blob)
         b[len(b) - 8:] = np.float64(bad).tobytes()
-        with pytest.raises(capi.EngineError) as ex:
-            a.checkpoint_load(bytes(b))
-        assert ex.value.code == capi.TS_E_INVALID and "epsilon" in str(ex.value)
+        ex, = refused(capi.TS_E_INVALID, lambda: a.checkpoint_load(bytes(b)))
+        assert "epsilon" in str(ex)
         assert a.checkpoint_save() == blob, "a refused load changed the target"
     a.close()
 
@@ -304,9 +270,7 @@ def test_static_features_are_fixed_once_a_protocol_has_acted():
     api.lights_set_static(penalty_score=np.full(G, 2.0))      # before the first call: allowed
     assert (api.lights_proto_observe()[0][:, 0, 8] == 2.0).all()
     api.lights_proto_act(np.zeros(G, np.int8))
-    with pytest.raises(capi.EngineError) as ex:
-        api.lights_set_static(penalty_score=np.full(G, 3.0))
-    assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, lambda: api.lights_set_static(penalty_score=np.full(G, 3.0)))
     assert (api.lights_proto_observe()[0][:, 0, 8] == 2.0).all()
     api.close()
 
@@ -320,9 +284,7 @@ def test_explicit_params_honour_or_refuse_a_protocol_name():
     api.close()
     other = new_engine()
     p = other.params_from_defaults({**tr["defaults_json"], "TRAFFIC_LIGHT_AGENT_ALGORITHM": "FIXED_TIME"})
-    with pytest.raises(capi.EngineError) as ex:
-        build_engine(other, tr, defaults=tr["defaults_json"], params=p, global_seed=1, sched_seed=2)
-    assert ex.value.code == capi.TS_E_INVALID
+    refused(capi.TS_E_INVALID, lambda: build_engine(other, tr, defaults=tr["defaults_json"], params=p, global_seed=1, sched_seed=2))
     other.close()
 
 
@@ -338,24 +300,20 @@ def test_bad_arguments_change_nothing():
     bad = [lambda: api.lights_proto_act(np.full(G, 2, np.int8)), lambda: api.lights_proto_act_q(q),
            lambda: api.lights_proto_act_q(np.full((G, 2), np.inf, np.float32))]
     for call in bad:
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_INVALID
+        refused(capi.TS_E_INVALID, call)
     with pytest.raises(ValueError):
         api.lights_proto_act_q(np.zeros((G + 1, 2), np.float32))
     assert api.checkpoint_save() == before      # (nothing applied, nothing drawn: the blob holds the global stream)
     api.close()
     a2c, tr2 = fixture_engine("lights_a2c_64_s45")
     before = a2c.checkpoint_save()
-    with pytest.raises(capi.EngineError) as ex:      # a non-NULL next state under A2C
-        a2c.lights_proto_act(tr2["lp_action"][0], want_next=True)
-    assert ex.value.code == capi.TS_E_INVALID and a2c.checkpoint_save() == before
+    refused(capi.TS_E_INVALID, lambda: a2c.lights_proto_act(tr2["lp_action"][0], want_next=True))      # a non-NULL next state under A2C
+    assert a2c.checkpoint_save() == before
     for cfg in (dict(protocol=3), dict(protocol=2, min_green=-1), dict(protocol=2, eps_min=1.5), dict(protocol=2, eps_decay=float("nan"))):
         c = new_engine()
         setup_proto(c, tr2, {**tr2["defaults_json"], "TRAFFIC_LIGHT_AGENT_ALGORITHM": "EXTERNAL"})
-        with pytest.raises(capi.EngineError) as ex:
-            c.lights_proto_config(**cfg)
-        assert ex.value.code == capi.TS_E_INVALID and c.lights_proto_info()["protocol"] == 0
+        refused(capi.TS_E_INVALID, lambda: c.lights_proto_config(**cfg))
+        assert c.lights_proto_info()["protocol"] == 0
         c.close()
     a2c.close()
 
@@ -365,24 +323,17 @@ def test_every_entry_is_unsupported_under_another_algorithm():
     api = new_engine()
     setup_from_trace(api, load_trace(trace_path("lights_qa_96_s2")))
     z = np.zeros(api.n_groups, np.int8)
-    for call in (lambda: api.lights_proto_config("RL_A2C_BATCHED"), api.lights_proto_info, api.lights_proto_observe,
-                 lambda: api.lights_proto_act(z), lambda: api.lights_proto_act_q(np.zeros((api.n_groups, 2), np.float32)),
-                 api.lights_proto_controller, api.lights_proto_device):
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_UNSUPPORTED
+    refused(capi.TS_E_UNSUPPORTED, lambda: api.lights_proto_config("RL_A2C_BATCHED"), api.lights_proto_info, api.lights_proto_observe,
+            lambda: api.lights_proto_act(z), lambda: api.lights_proto_act_q(np.zeros((api.n_groups, 2), np.float32)),
+            api.lights_proto_controller, api.lights_proto_device)
     api.step(2)
     api.close()
 
 
 DEVICE_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
-import torch                     # (first: the engine library then shares torch's HIP runtime)
-torch.cuda.init()
 import numpy as np
 from trafficsimulation_amd._lib import new_engine
-from tests.test_gpu_lights_proto import fixture_engine
+from tests.engine_util import proto_engine as fixture_engine
 bits = lambda a: np.ascontiguousarray(a).tobytes()
 a, tr = fixture_engine("lights_gat_64_s45")
 b, _ = fixture_engine("lights_gat_64_s45")
@@ -434,13 +385,9 @@ except Exception as ex:
     assert getattr(ex, "code", None) == -1, ex
 assert a.checkpoint_save() == before
 a.close(); b.close()
-print("DEVICE_OK")
 '''
 
 
-def test_device_tensors_device_actions_and_device_q(tmp_path):
+def test_device_tensors_device_actions_and_device_q():
     """lights_proto_device(), act(torch tensor) and act_q(torch tensor), in a process of its own that imports torch first."""
-    script = tmp_path / "lights_proto_device.py"
-    script.write_text(DEVICE_SCRIPT % dict(root=ROOT))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(DEVICE_SCRIPT, torch_first=True, timeout=300)

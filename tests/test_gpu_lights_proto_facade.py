@@ -2,30 +2,26 @@
 control_lights_q follow the numpy model, epsilon shows on the group views, and save / load, deepcopy and pickle carry the
 protocol in the middle of a run.  The non-batched names stay refused."""
 import copy
-import os
 import pickle
-import sys
 
 import numpy as np
 import pytest
 
 from tests import lights_ext_expect as lx
 from tests import lights_proto_expect as lp
+from tests.engine_util import city_model, refused
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd.mesa_api import CityModel
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "examples"))
 DECAY = 0.1
 STAT_KEYS = ("avg_duration_internal", "avg_duration_through", "avg_time_per_unit_internal", "avg_time_per_unit_through")
 
 
 def make_model(algo):
-    from run_city import TRAFFIC
-    return CityModel(64, 64, seed=45, traffic=dict(TRAFFIC, P_int=30000, P_thr=8000),
-                     defaults={"TRAFFIC_LIGHT_AGENT_ALGORITHM": algo, "RAIN_ENABLED": False, "EPS_DECAY_RATE": DECAY})
+    return city_model(64, seed=45, traffic=dict(P_int=30000, P_thr=8000),
+                      defaults={"TRAFFIC_LIGHT_AGENT_ALGORITHM": algo, "RAIN_ENABLED": False, "EPS_DECAY_RATE": DECAY})
 
 
 def q_for(t, G):
@@ -112,6 +108,4 @@ def test_gat_name_round_trips_save_load_copy_and_pickle(tmp_path):
 
 @pytest.mark.parametrize("name", ["GAT_DQN", "NEIGHBOR_RL"])
 def test_the_non_batched_names_stay_refused(name):
-    with pytest.raises(capi.EngineError) as ex:
-        CityModel(64, 64, seed=45, defaults={"TRAFFIC_LIGHT_AGENT_ALGORITHM": name, "RAIN_ENABLED": False})
-    assert ex.value.code == capi.TS_E_UNSUPPORTED
+    refused(capi.TS_E_UNSUPPORTED, lambda: CityModel(64, 64, seed=45, defaults={"TRAFFIC_LIGHT_AGENT_ALGORITHM": name, "RAIN_ENABLED": False}))

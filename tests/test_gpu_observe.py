@@ -2,51 +2,22 @@
 hold (tests/observe_util.py), a run that observation does not change, the device-side reductions, a large world's
 invariants, the life cycle of the planes and the sharded mode."""
 import copy
-import json
 import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
 from tests import observe_util as ou
-from tests.test_observe_expect import REPLAN_TRACES, UNCAPPED_REPLAN_TRACES
-from tests.trace_util import NO_ASTAR_TRACES, replay_and_compare, setup_from_trace, trace_path
+from tests import procs
+from tests.engine_util import assert_same_state, city_model, engine_for, full_state, refused
+from tests.observe_util import REPLAN_TRACES, UNCAPPED_REPLAN_TRACES
+from tests.trace_util import NO_ASTAR_TRACES, replay_and_compare
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAMPLED, ENTER = slice(0, 3), slice(3, 7)
-
-
-def engine_for(name, explicit_paths=False):
-    tr = load_trace(trace_path(name))
-    api = new_engine()
-    setup_from_trace(api, tr, explicit_paths=explicit_paths)
-    return api, tr
-
-
-def full_state(api):
-    c = api.counters()
-    return {"maps": [api.map(w) for w in (capi.MAP_OCCUPANCY, capi.MAP_STOP, capi.MAP_STUCK, capi.MAP_RAIN)],
-            "veh": api.vehicles(), "groups": api.groups(),
-            "rng": [api.rng_fingerprint(capi.RNG_GLOBAL), api.rng_fingerprint(capi.RNG_SCHEDULER)],
-            "counters": [getattr(c, f) for f, _ in capi.TsCounters._fields_], "blob": api.checkpoint_save()}
-
-
-def assert_same_state(a, b, ctx):
-    for i, (p, q) in enumerate(zip(a["maps"], b["maps"])):
-        assert np.array_equal(p, q), f"{ctx}: map {i}"
-    assert np.array_equal(a["veh"], b["veh"]), f"{ctx}: vehicle rows"
-    assert np.array_equal(a["groups"], b["groups"]), f"{ctx}: groups"
-    assert a["rng"] == b["rng"], f"{ctx}: RNG streams"
-    assert a["counters"] == b["counters"], f"{ctx}: counters"
-    assert a["blob"] == b["blob"], f"{ctx}: checkpoint bytes"
 
 
 # ---- 1. exact planes on the traces that only replay their spawn-time paths -------------------------------------
@@ -170,17 +141,10 @@ def test_groups(observed_rect):
 
 
 DEVICE_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
-import torch                     # (first: the engine library then shares torch's HIP runtime, as under torch.distributed.run)
-torch.cuda.init()
 import numpy as np
 from trafficsimulation_amd import _capi as capi
-from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
-from tests.trace_util import setup_from_trace, trace_path
-api = new_engine()
-setup_from_trace(api, load_trace(trace_path("full_96_s8")), explicit_paths=False)
+from tests.engine_util import engine_for
+api, _ = engine_for("full_96_s8")
 api.observe_start()
 api.step(12)
 for name in capi.OBS_PLANES:
@@ -191,17 +155,13 @@ for name in capi.OBS_PLANES:
 flow = sum(api.observe_device(n).to(torch.int64) for n in capi.OBS_ENTER)      # (consumed on the device, no copy to the host)
 assert int(flow.sum()) == sum(int(api.observe_plane(n).sum()) for n in capi.OBS_ENTER) > 0
 api.close()
-print("DEVICE_OK")
 '''
 
 
-def test_device_pointer_is_the_plane(tmp_path):
+def test_device_pointer_is_the_plane():
     """observe_device(): a torch tensor over the engine's own plane.  In a process of its own that imports torch before it
     loads the engine, the way the torch-side callers (dist.py) run."""
-    script = tmp_path / "observe_device.py"
-    script.write_text(DEVICE_SCRIPT % dict(root=ROOT))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(DEVICE_SCRIPT, torch_first=True, timeout=300)
 
 
 # ---- 5. a 512 x 512 world through a replanning wave: invariants ----------------------------------------------------------
@@ -239,30 +199,18 @@ def test_lifecycle_and_errors():
     api, tr = engine_for("lights_qa_96_s2", explicit_paths=True)
     H, W = int(tr["height"]), int(tr["width"])
     assert api.has_observe and api.observe_info() == {"planes": [], "mask": 0, "ticks": 0, "width": W, "height": H, "device_bytes": 0}
-    for call in (lambda: api.observe_plane("present"), api.observe_reset, api.observe_groups, lambda: api.observe_pooled("present", 4),
-                 lambda: api.observe_regions("present", [(0, 0, 1, 1)]), lambda: api.observe_device("present")):
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, lambda: api.observe_plane("present"), api.observe_reset, api.observe_groups, lambda: api.observe_pooled("present", 4),
+            lambda: api.observe_regions("present", [(0, 0, 1, 1)]), lambda: api.observe_device("present"))
     api.observe_stop()                       # (off already: fine)
-    for bad in (0, 1 << 7, 0xFFFFFFFF):
-        with pytest.raises(capi.EngineError) as ex:
-            api.observe_start(bad)
-        assert ex.value.code == capi.TS_E_INVALID
+    refused(capi.TS_E_INVALID, *(lambda bad=bad: api.observe_start(bad) for bad in (0, 1 << 7, 0xFFFFFFFF)))
     api.observe_start(["present", "enter_n"])
     info = api.observe_info()
     assert info["planes"] == ["present", "enter_n"] and info["device_bytes"] == 2 * 4 * W * H and info["ticks"] == 0
     api.step(3)
     assert api.observe_info()["ticks"] == 3 and api.observe_plane("present").sum() == sum(len(ou.rows_at(tr, t)) for t in range(3))
-    for call in (lambda: api.observe_plane("waiting"), api.observe_groups, lambda: api.observe_pooled("speed", 2)):
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_STATE
-    for call in (lambda: api.observe_plane(7), lambda: api.observe_plane(-1), lambda: api.observe_pooled("present", 0),
-                 lambda: api.observe_pooled("present", -3)):
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_INVALID
+    refused(capi.TS_E_STATE, lambda: api.observe_plane("waiting"), api.observe_groups, lambda: api.observe_pooled("speed", 2))
+    refused(capi.TS_E_INVALID, lambda: api.observe_plane(7), lambda: api.observe_plane(-1), lambda: api.observe_pooled("present", 0),
+            lambda: api.observe_pooled("present", -3))
     api.observe_reset()
     assert api.observe_info()["ticks"] == 0 and api.observe_plane("present").sum() == 0 and api.observe_plane("enter_n").sum() == 0
     # a checkpoint load rewinds the run, not what was observed of it
@@ -293,11 +241,9 @@ def test_one_step_of_five_adds_what_five_steps_of_one_add():
     a.close(), b.close()
 
 
-def test_facade_observes_and_copies_come_without():
+def test_facade_observes_and_copies_come_without(tmp_path):
     from trafficsimulation_amd.mesa_api import CityModel
-    sys.path.insert(0, os.path.join(ROOT, "examples"))
-    from run_city import TRAFFIC
-    m = CityModel(200, 200, seed=1, traffic=dict(TRAFFIC))
+    m = city_model(200, seed=1)
     m.observe()
     for _ in range(30):
         m.step()
@@ -313,7 +259,7 @@ def test_facade_observes_and_copies_come_without():
         assert (r["waiting_ns"], r["waiting_ew"]) == (int(rows[g, 0]), int(rows[g, 2])) and r["throughput"] == int(rows[g, 4:].sum())
     twin = copy.deepcopy(m)
     assert twin.engine.observe_info()["mask"] == 0 and m.engine.observe_info()["ticks"] == 30
-    path = os.path.join(tempfile.mkdtemp(), "m.npz")
+    path = os.path.join(tmp_path, "m.npz")
     m.save(path)
     loaded = CityModel.load(path)
     assert loaded.engine.observe_info()["mask"] == 0
@@ -325,41 +271,24 @@ def test_facade_observes_and_copies_come_without():
 
 # ---- 7. sharded mode: every rank holds the same planes --------------------------------------------------------------------
 WORKER = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
-from trafficsimulation_amd import dist as tdist
-from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
-from tests.trace_util import setup_from_trace, replay_and_compare, trace_path
+from tests.engine_util import engine_for
+from tests.trace_util import replay_and_compare
 from tests import observe_util as ou
-rank, local, world = tdist.env_rank()
-d = tdist.init("gloo", rank, world)
-tr = load_trace(trace_path(%(trace)r))
-api = new_engine()
-setup_from_trace(api, tr, explicit_paths=False)
+api, tr = engine_for(%(trace)r)
 sr = tdist.ShardedReplans().attach(api)
 api.observe_start()
 n = replay_and_compare(api, tr)
 assert sr.calls > 0
-np.save(os.path.join(%(outdir)r, "planes%%d.npy" %% rank), ou.read_planes(api))
+np.save(os.path.join(OUTDIR, "planes%%d.npy" %% rank), ou.read_planes(api))
 api.close()
-d.destroy_process_group()
 '''
 
 
 def test_sharded_ranks_hold_equal_planes():
-    name, port = "full_96_s8", "29713"
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    with tempfile.TemporaryDirectory() as outdir:
-        path = os.path.join(outdir, "worker.py")
-        with open(path, "w") as f:
-            f.write(WORKER % dict(root=ROOT, trace=name, outdir=outdir))
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-               "--master-addr", "127.0.0.1", "--master-port", port, path]
-        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
-        ranks = [np.load(os.path.join(outdir, f"planes{r}.npy")) for r in range(2)]
+    name = "full_96_s8"
+    _, saved, _ = procs.run_ranks(WORKER, 2, timeout=600, trace=name)
+    ranks = [saved[f"planes{r}.npy"] for r in range(2)]
     api, tr = engine_for(name)
     api.observe_start()
     api.step(ou.n_ticks(tr))

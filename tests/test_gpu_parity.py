@@ -7,7 +7,9 @@ import pytest
 
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd.world import load_trace
-from tests import test_oracle_kats as K
+from tests import procs
+from tests import kats_util as K
+from tests.engine_util import compare, compare_full, pair, pair_full
 from tests.trace_util import CLOSED_TRACES, DEFAULT_TRACES, DTA_TRACES, RAIN_TRACES, RAGGED_TRACES, RECT_TRACES, SERVICE_TRACES, VARIANT_TRACES, DESPAWN_TRACES, NOBATCH_TRACES, COST_TRACES, check_initial, replay_and_compare, setup_from_trace, trace_path
 
 pytestmark = pytest.mark.gpu
@@ -92,9 +94,8 @@ def test_hip_astar_kats(hip, golden_dir, tag):
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_hip_astar_fov_kats(golden_dir, tag):
     """ts_astar with VEHICLE_RESPECT_AWARENESS (field-of-view masking) against the reference's astar_numba."""
-    from tests.test_oracle_kats import run_astar_fov_kats
     from trafficsimulation_amd._lib import new_engine
-    run_astar_fov_kats(new_engine, golden_dir, tag)
+    K.run_astar_fov_kats(new_engine, golden_dir, tag)
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
@@ -148,52 +149,16 @@ def test_hip_astar_cost_kats(hip, golden_dir, name, tag):
     K.run_astar_cost_kats(hip, golden_dir, name, tag)
 
 
-def _pair(size, vehicles, seed, policy):
-    """HIP engine and CPU oracle on the same synthetic world / routes / seeds."""
-    import bench
-    from oracle import pyoracle
-    from trafficsimulation_amd._lib import new_engine
-    tables, routes, _ = bench.make_workload(size, vehicles, seed)
-    hip_api, cpu_api = new_engine(), pyoracle.load()
-    bench.setup(hip_api, tables, routes, seed, extra=policy)
-    bench.setup(cpu_api, tables, routes, seed, extra=policy)
-    return hip_api, cpu_api
-
-
-def _compare(hip_api, cpu_api, ticks, every=1):
-    for t in range(ticks):
-        hip_api.step(1)
-        cpu_api.step(1)
-        if (t + 1) % every and t != ticks - 1:
-            continue
-        for which in (capi.MAP_OCCUPANCY, capi.MAP_STOP, capi.MAP_STUCK):
-            assert np.array_equal(hip_api.map(which), cpu_api.map(which)), f"tick {t}: map {which}"
-        a, b = hip_api.vehicles(), cpu_api.vehicles()
-        assert a.shape == b.shape, f"tick {t}: live vehicles {a.shape} vs {b.shape}"
-        if not np.array_equal(a, b):
-            r, c = np.argwhere(a != b)[0]
-            raise AssertionError(f"tick {t}: vehicle row {r} field {capi.V_FIELDS[c]}: hip {a[r, c]} cpu {b[r, c]}")
-        assert np.array_equal(hip_api.groups(), cpu_api.groups()), f"tick {t}: light groups"
-        assert hip_api.rng_fingerprint(capi.RNG_GLOBAL) == cpu_api.rng_fingerprint(capi.RNG_GLOBAL), f"tick {t}: RNG"
-        assert hip_api.rng_fingerprint(capi.RNG_SCHEDULER) == cpu_api.rng_fingerprint(capi.RNG_SCHEDULER)
-    ch, cc = hip_api.counters(), cpu_api.counters()
-    for f in ("stuck", "live_through", "count_completed_through", "total_distance_through", "agent_steps",
-              "total_duration_through", "elapsed", "step_count"):
-        assert getattr(ch, f) == getattr(cc, f), f
-    hip_api.close()
-    cpu_api.close()
-
-
 def test_hip_vs_oracle_carfollow_512():
     """Config 2 of BASELINE.json: 512x512, 50k vehicles, lights fixed green (disabled), car-following only."""
-    h, c = _pair(512, 50_000, 3, {})
-    _compare(h, c, 40)
+    h, c = pair(512, 50_000, 3, {})
+    compare(h, c, 40)
 
 
 def test_hip_vs_oracle_lights_512():
     """Same world with QUEUE_ACTUATED lights interleaved in the shuffled order (replans still gated off)."""
-    h, c = _pair(512, 20_000, 4, {"TRAFFIC_LIGHT_AGENT_ALGORITHM": "QUEUE_ACTUATED"})
-    _compare(h, c, 60)
+    h, c = pair(512, 20_000, 4, {"TRAFFIC_LIGHT_AGENT_ALGORITHM": "QUEUE_ACTUATED"})
+    compare(h, c, 60)
 
 
 def test_hip_vs_oracle_full_policy_256():
@@ -204,7 +169,7 @@ def test_hip_vs_oracle_full_policy_256():
            "VEHICLE_CONTRAFLOW_OVERTAKE_ACTIVE": True, "VEHICLE_STUCK_CONTRAFLOW_ENABLED": True,
            "VEHICLE_SIDESWIPE_COLLISION_CHANCE": 0.05, "VEHICLE_SIDESWIPE_COLLISION_DURATION": 30,
            "VEHICLE_MALFUNCTION_CHANCE": 0.001, "VEHICLE_MALFUNCTION_DURATION": 25}
-    h, c = _pair(256, 2_000, 5, pol)
+    h, c = pair(256, 2_000, 5, pol)
     hc = None
     for t in range(40):
         h.step(1)
@@ -227,52 +192,12 @@ def test_hip_vs_oracle_full_policy_256():
     c.close()
 
 
-def _pair_full(size, vehicles, seed, extra=None, carves=False):
-    """HIP engine and CPU oracle under the reference's default policy (bench.py --policy full: QUEUE_ACTUATED lights,
-    replanning, contraflow, malfunctions / sideswipes) on the same synthetic world / routes / seeds."""
-    import bench
-    from oracle import pyoracle
-    from trafficsimulation_amd._lib import new_engine
-    tables, routes, _ = bench.make_workload(size, vehicles, seed, carves=carves)
-    hip_api, cpu_api = new_engine(), pyoracle.load()
-    bench.setup(hip_api, tables, routes, seed, extra=extra, policy="full")
-    bench.setup(cpu_api, tables, routes, seed, extra=extra, policy="full")
-    return hip_api, cpu_api
-
-
-def _compare_full(h, c, ticks, every=1, close=True):
-    for t in range(ticks):
-        h.step(1)
-        c.step(1)
-        if (t + 1) % every and t != ticks - 1:
-            continue
-        for which in (capi.MAP_OCCUPANCY, capi.MAP_STOP, capi.MAP_STUCK):
-            assert np.array_equal(h.map(which), c.map(which)), f"tick {t}: map {which}"
-        a, b = h.vehicles(), c.vehicles()
-        assert a.shape == b.shape, f"tick {t}: live vehicles {a.shape} vs {b.shape}"
-        if not np.array_equal(a, b):
-            r, col = np.argwhere(a != b)[0]
-            raise AssertionError(f"tick {t}: vehicle row {r} field {capi.V_FIELDS[col]}: hip {a[r, col]} cpu {b[r, col]}")
-        assert np.array_equal(h.groups(), c.groups()), f"tick {t}: light groups"
-        assert h.rng_fingerprint(capi.RNG_GLOBAL) == c.rng_fingerprint(capi.RNG_GLOBAL), f"tick {t}: RNG"
-        assert h.rng_fingerprint(capi.RNG_SCHEDULER) == c.rng_fingerprint(capi.RNG_SCHEDULER)
-        assert h.counters().astar_calls == c.counters().astar_calls, f"tick {t}: A* calls"
-    ch, cc = h.counters(), c.counters()
-    for f in ("stuck", "live_through", "count_completed_through", "total_distance_through", "agent_steps", "overtaking",
-              "in_stuck_detour", "collisions", "malfunctions", "astar_calls", "elapsed", "step_count"):
-        assert getattr(ch, f) == getattr(cc, f), f
-    if close:
-        h.close()
-        c.close()
-    return ch
-
-
 def test_hip_vs_oracle_full_policy_512_with_carved_blocks():
     """The default policy on a synthetic world with sub-block roads / L-shaped carves (BASELINE config 5's kind of world; the
     reference's own carved city is the trace carve_96_s10): the searches route through the one-lane roads inside the blocks,
     through a replanning wave."""
-    h, c = _pair_full(512, 12_000, 9, carves=True)
-    ch = _compare_full(h, c, 9)
+    h, c = pair_full(512, 12_000, 9, carves=True)
+    ch = compare_full(h, c, 9)
     assert ch.astar_calls > 5_000
 
 
@@ -280,16 +205,16 @@ def test_hip_vs_oracle_full_policy_512_through_a_replanning_wave():
     """Reference defaults on 512 x 512 / 12 000 vehicles across the tick in which every vehicle's path-retry cooldown
     runs out at once (thousands of searches in one tick: the work queue is far longer than the searcher slots, the
     path pool is garbage-collected / grown under it).  State for state against the oracle, every tick."""
-    h, c = _pair_full(512, 12_000, 7)
-    ch = _compare_full(h, c, 9)
+    h, c = pair_full(512, 12_000, 7)
+    ch = compare_full(h, c, 9)
     assert ch.astar_calls > 5_000 and ch.astar_expansions > 1_000_000
 
 
 def test_hip_vs_oracle_full_policy_1024():
     """Reference defaults at 1024 x 1024 / 60 000 vehicles (searches of 10^4 - 10^5 expansions: the direct-indexed tables
     of a megacell map, searcher slots in the tens of MB), four ticks, every tick."""
-    h, c = _pair_full(1024, 60_000, 1)
-    ch = _compare_full(h, c, 4)
+    h, c = pair_full(1024, 60_000, 1)
+    ch = compare_full(h, c, 4)
     assert ch.astar_calls > 1_000 and ch.astar_expansions > 5_000_000
 
 
@@ -297,24 +222,24 @@ def test_hip_vs_oracle_replanning_wave_with_a_full_path_pool(monkeypatch):
     """The same wave with (almost) no room reserved in the path pool: planners find it full, their entries go to the retry
     list, the host garbage-collects / grows the pool and the searches run again - state for state against the oracle."""
     monkeypatch.setenv("TS_DEBUG_POOL_PER_ENTRY", "2")
-    h, c = _pair_full(512, 12_000, 9)
-    ch = _compare_full(h, c, 8)
+    h, c = pair_full(512, 12_000, 9)
+    ch = compare_full(h, c, 8)
     assert ch.astar_calls > 5_000
 
 
 def test_hip_vs_oracle_full_policy_768_through_a_replanning_wave():
     """The same wave one size up (768 x 768 / 30 000 vehicles: tens of thousands of searches of ~10^4 expansions in one
     tick), compared after every second tick."""
-    h, c = _pair_full(768, 30_000, 3)
-    ch = _compare_full(h, c, 7, every=2)
+    h, c = pair_full(768, 30_000, 3)
+    ch = compare_full(h, c, 7, every=2)
     assert ch.astar_calls > 20_000
 
 
 def test_hip_vs_oracle_config3_2048_500k():
     """BASELINE config 3 at its own size: 2048 x 2048, 500 000 vehicles, QUEUE_ACTUATED light groups AND replanning
     (reference defaults), three ticks, compared state for state after the third."""
-    h, c = _pair_full(2048, 500_000, 1)
-    ch = _compare_full(h, c, 3, every=3)
+    h, c = pair_full(2048, 500_000, 1)
+    ch = compare_full(h, c, 3, every=3)
     assert ch.astar_calls > 1_000
 
 
@@ -323,15 +248,15 @@ def test_hip_vs_oracle_full_policy_4096_1m_first_ticks():
     ticks (the replans start with the third: some 2.5 x 10^4 searches on 4096 searcher slots with 32 MB tables each),
     state for state after the second and the fourth.  (A
     replanning wave of this size is hours of oracle time; waves are compared at 512^2 .. 1024^2 above.)"""
-    h, c = _pair_full(4096, 1_000_000, 1)
-    ch = _compare_full(h, c, 4, every=2)
+    h, c = pair_full(4096, 1_000_000, 1)
+    ch = compare_full(h, c, 4, every=2)
     assert ch.astar_calls > 5_000
 
 
 def test_hip_vs_oracle_full_size_4096_1m():
     """BASELINE.json's headline size (4096x4096, 10^6 vehicles), 6 ticks, compared state for state."""
-    h, c = _pair(4096, 1_000_000, 1, {})
-    _compare(h, c, 6, every=3)
+    h, c = pair(4096, 1_000_000, 1, {})
+    compare(h, c, 6, every=3)
 
 
 def test_hip_vs_oracle_config5_size_8192_4m():
@@ -348,19 +273,19 @@ def test_hip_vs_oracle_config5_size_8192_4m():
     bench.setup(h, tables, routes, 1, policy="lights")
     bench.setup(c, tables, routes, 1, policy="lights")
     assert h.num_scheduled() > (1 << 22)
-    _compare(h, c, 3, every=3)
+    compare(h, c, 3, every=3)
 
 
 def test_facade_on_hip(hip):
     """The Mesa-shaped facade (CityModel / VehicleAgent / grid / schedule) over the HIP engine."""
-    from tests.test_mesa_facade import run_facade_against_trace
+    from tests.facade_runs import run_facade_against_trace
     run_facade_against_trace(hip)
 
 
 def test_facade_with_generator_on_hip(hip):
     """The same facade with the engine's traffic generator armed: generator-spawned vehicles, service vehicles and
     CityBlock views read from the HIP engine."""
-    from tests.test_mesa_facade import run_facade_with_generator
+    from tests.facade_runs import run_facade_with_generator
     run_facade_with_generator(hip)
 
 
@@ -422,35 +347,30 @@ def test_hip_vs_oracle_service_stress():
     c.close()
 
 
+MULTI_PASS = """
+from tests.engine_util import compare, pair
+pol = {'TRAFFIC_LIGHT_AGENT_ALGORITHM': 'QUEUE_ACTUATED', 'VEHICLE_MALFUNCTION_CHANCE': 0.002,
+       'VEHICLE_MALFUNCTION_DURATION': 12, 'VEHICLE_SIDESWIPE_COLLISION_CHANCE': 0.05,
+       'VEHICLE_SIDESWIPE_COLLISION_DURATION': 9, 'PATHFINDING_COOLDOWN': 4}
+h, c = pair(256, 6000, 11, pol)
+compare(h, c, 30)
+"""
+
+
 def test_hip_multi_pass_decide_in_a_subprocess():
     """More vehicles than one RNG pass covers (2^20) split the decide phase into several passes, each resuming the
     stream bookkeeping where the previous one stopped.  TS_DEBUG_SEG shrinks the pass size so that a 256x256 world
     walks that path (dozens of passes per tick, with strandings firing inside them); the knob is read once per
     process, hence the subprocess."""
-    import subprocess
-    import sys
-    code = (
-        "import numpy as np, sys\n"
-        "sys.path.insert(0, '.')\n"
-        "from tests.test_gpu_parity import _pair, _compare\n"
-        "pol = {'TRAFFIC_LIGHT_AGENT_ALGORITHM': 'QUEUE_ACTUATED', 'VEHICLE_MALFUNCTION_CHANCE': 0.002,\n"
-        "       'VEHICLE_MALFUNCTION_DURATION': 12, 'VEHICLE_SIDESWIPE_COLLISION_CHANCE': 0.05,\n"
-        "       'VEHICLE_SIDESWIPE_COLLISION_DURATION': 9, 'PATHFINDING_COOLDOWN': 4}\n"
-        "h, c = _pair(256, 6000, 11, pol)\n"
-        "_compare(h, c, 30)\n"
-        "print('multi-pass ok')\n")
-    env = dict(os.environ, TS_DEBUG_SEG="777")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600,
-                         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    assert out.returncode == 0 and "multi-pass ok" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+    procs.run_python(MULTI_PASS, env=dict(os.environ, TS_DEBUG_SEG="777"), timeout=600)
 
 
 def test_hip_vs_oracle_long_run_word_ring_wraps():
     """400 ticks at 512x512 / 50k vehicles consume ~50M words of the global stream and ~20M of the scheduler stream:
     both pre-generated word rings (8M words each) and the device mirror wrap several times, the move-phase claim
     epochs wrap too."""
-    h, c = _pair(512, 50_000, 21, {"TRAFFIC_LIGHT_AGENT_ALGORITHM": "QUEUE_ACTUATED"})
-    _compare(h, c, 400, every=25)
+    h, c = pair(512, 50_000, 21, {"TRAFFIC_LIGHT_AGENT_ALGORITHM": "QUEUE_ACTUATED"})
+    compare(h, c, 400, every=25)
 
 
 
@@ -498,8 +418,8 @@ def test_hip_quad_searcher_vs_oracle_512_through_a_replanning_wave(monkeypatch):
     LDS share, hand-backs to k_replan while both kernels run, the direction window moving), state for state every tick."""
     monkeypatch.setenv("TS_QUAD", "1")
     monkeypatch.setenv("TS_QUAD_MIN", "1")
-    h, c = _pair_full(512, 12_000, 7)
-    ch = _compare_full(h, c, 9)
+    h, c = pair_full(512, 12_000, 7)
+    ch = compare_full(h, c, 9)
     assert ch.astar_calls > 5_000 and ch.astar_expansions > 1_000_000
 
 
@@ -510,8 +430,8 @@ def test_hip_quad_and_wave_searchers_share_the_table_arena(monkeypatch):
     monkeypatch.setenv("TS_QUAD", "1")
     monkeypatch.setenv("TS_QUAD_MIN", "5000")
     monkeypatch.setenv("TS_QUAD_SLOTS", "1024")
-    h, c = _pair_full(768, 30_000, 3)
-    ch = _compare_full(h, c, 9, every=1)
+    h, c = pair_full(768, 30_000, 3)
+    ch = compare_full(h, c, 9, every=1)
     assert ch.astar_calls > 20_000
 
 
@@ -531,6 +451,6 @@ def test_hip_quad_searcher_with_a_full_path_pool(monkeypatch):
     monkeypatch.setenv("TS_QUAD", "1")
     monkeypatch.setenv("TS_QUAD_MIN", "1")
     monkeypatch.setenv("TS_DEBUG_POOL_PER_ENTRY", "2")
-    h, c = _pair_full(512, 12_000, 9)
-    ch = _compare_full(h, c, 8)
+    h, c = pair_full(512, 12_000, 9)
+    ch = compare_full(h, c, 8)
     assert ch.astar_calls > 5_000

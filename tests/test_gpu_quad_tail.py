@@ -15,37 +15,21 @@ hardly produce.  Two test builds bring both to the 64^2-200^2 reference traces (
 Every test replays a captured run with every replanning queue on the quads and compares it with the reference tick for tick,
 or runs a 512^2 world against the oracle, and reads the quads' counters (ts_debug_quad_stats) to prove that it reached the
 steps it is about."""
-import ctypes
 import json
-import os
 
 import pytest
 
-from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import _lib
 from trafficsimulation_amd.world import load_trace
-from tests import test_gpu_parity as P
+from tests.engine_util import compare_full, engine_of, pair_full
 from tests.trace_util import replay_and_compare, setup_from_trace, trace_path
 
 pytestmark = pytest.mark.gpu
 
-CSRC = os.path.dirname(_lib.LIB_PATH)
-BUILDS = {"quadtail": os.path.join(CSRC, "libtrafficsim_hip_quadtail.so"), "quadwin": os.path.join(CSRC, "libtrafficsim_hip_quadwin.so")}
 REASONS = ("window", "heap", "budget", "path_buffer", "policy_bail", "policy_overflow")
 # the traces tests/test_gpu_quad_window.py replays
 TRACES = ["full_64_s1", "faults_64_s9", "config1_64_s11", "full_96_s8", "startgoal_96_s27", "carve_96_s10", "ring_r1_112_s22",
           "default_200_s20", "rect_64x112_s19", "rect_96x64_s18", "costs_int_96_s31"]
-
-
-def engine_of(build):
-    if build == "shipped":
-        return _lib.new_engine
-
-    def make():
-        if not os.path.exists(BUILDS[build]):
-            raise _lib.EngineUnavailable(f"{BUILDS[build]} is missing - `make -C trafficsimulation_amd/csrc` builds it")
-        return capi.CApi(ctypes.CDLL(BUILDS[build]), "ts_")
-    return make
 
 
 @pytest.fixture(autouse=True)
@@ -100,9 +84,9 @@ def test_quad_tail_vs_oracle_512_through_a_replanning_wave(monkeypatch, build):
     slots: the step fetched ahead starts on level 6) reaches its third level with heaps beyond 511 entries - once on this
     workload, which the seed fixes; its blocking levels need more than 1 022 entries and are not asserted here."""
     monkeypatch.setattr(_lib, "new_engine", engine_of(build))
-    h, c = P._pair_full(512, 12_000, 7)
+    h, c = pair_full(512, 12_000, 7)
     try:
-        P._compare_full(h, c, 9, close=False)
+        compare_full(h, c, 9, close=False)
         st = check_stats(h.debug_quad_stats())
     finally:
         h.close()

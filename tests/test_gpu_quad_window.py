@@ -9,46 +9,25 @@ other quad tests run at 768^2 and smaller with the shipped limits, where none of
 slots are in LDS, and a 96-cell path buffer (csrc/Makefile): every hand-back reason fires on small maps, and the replays and
 oracle comparisons below check that nothing a hand-back leaves behind shows in the results.  Every test reads the quads'
 own counters (ts_debug_quad_stats) to prove it reached the paths it is about."""
-import ctypes
 import json
-import os
 
 import pytest
 
-from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import _lib
 from trafficsimulation_amd.world import load_trace
-from tests import test_gpu_parity as P
+from tests.engine_util import QUADWIN_WINDOW, check_quad_stats, compare_full, pair_full, quadwin_engine
 from tests.trace_util import replay_and_compare, setup_from_trace, trace_path
 
 pytestmark = pytest.mark.gpu
 
-QUADWIN = os.path.join(os.path.dirname(_lib.LIB_PATH), "libtrafficsim_hip_quadwin.so")
-WINDOW = 72                 # TS_QUAD_WINDOW of the quadwin build
+WINDOW = QUADWIN_WINDOW     # TS_QUAD_WINDOW of the quadwin build
 SHIPPED_WINDOW = 1152       # ... and of the shipped one
-REASONS = ("window", "heap", "budget", "path_buffer", "policy_bail", "policy_overflow")
-
-
-def quadwin_engine():
-    if not os.path.exists(QUADWIN):
-        raise _lib.EngineUnavailable(f"{QUADWIN} is missing - `make -C trafficsimulation_amd/csrc` builds it")
-    return capi.CApi(ctypes.CDLL(QUADWIN), "ts_")
 
 
 @pytest.fixture(autouse=True)
 def quads_on_every_queue(monkeypatch):
     monkeypatch.setenv("TS_QUAD", "1")
     monkeypatch.setenv("TS_QUAD_MIN", "1")
-
-
-def check_stats(st):
-    """What the counters must say about any run in which the quads took work: every hand-back has exactly one reason, and
-    only a search that was started can be abandoned."""
-    assert st["passes"] > 0 and st["jobs"] > 0, st
-    assert sum(st[r] for r in REASONS) == st["handbacks"], st
-    assert st["handbacks"] <= st["jobs"], st
-    assert st["window"] + st["heap"] + st["budget"] + st["path_buffer"] <= st["searches"], st
-    return st
 
 
 # What the quads of the quadwin build do on each trace.  A trace fixes every search the engine makes (the replay must match the
@@ -94,7 +73,7 @@ def test_quadwin_reproduces_reference_trace(name, wx, wy):
         n = replay_and_compare(api, tr)
         assert n == len(tr["veh_off"]) - 1
         assert api.counters().astar_calls == int(tr["astar_calls_spawn"]) + int(tr["astar_per_tick"].sum())
-        st = check_stats(api.debug_quad_stats())
+        st = check_quad_stats(api.debug_quad_stats())
         print("QSTATS", json.dumps(dict(name=name, **st)))
         assert {k: st[k] for k in PINNED_KEYS} == dict(zip(PINNED_KEYS, PINNED[name])), st
         if wx or wy:
@@ -107,13 +86,13 @@ def test_quadwin_reproduces_reference_trace(name, wx, wy):
 
 def _oracle_pair_on(monkeypatch, engine, size, vehicles, seed):
     monkeypatch.setattr(_lib, "new_engine", engine)
-    return P._pair_full(size, vehicles, seed)
+    return pair_full(size, vehicles, seed)
 
 
 def _compare_and_stats(h, c, ticks, every=1):
     try:
-        P._compare_full(h, c, ticks, every=every, close=False)
-        return check_stats(h.debug_quad_stats())
+        compare_full(h, c, ticks, every=every, close=False)
+        return check_quad_stats(h.debug_quad_stats())
     finally:
         h.close()
         c.close()

@@ -20,12 +20,8 @@ from trafficsimulation_amd import _lib
 from trafficsimulation_amd import citygen
 from trafficsimulation_amd.world import build_engine, load_trace
 from tests import observe_util as ou
-from tests import test_gpu_checkpoint as CK
-from tests import test_gpu_parity as P
-from tests import test_gpu_quad_window as QW
-from tests.test_gpu_edge_cases import same_state
-from tests.test_gpu_forced_paths import small_engine
-from tests.test_gpu_random_configs import run_case
+from tests.engine_util import QUADWIN_WINDOW, assert_same_deep_state, check_quad_stats, compare_full, deep_state, quadwin_engine, same_state, small_engine
+from tests.random_cases import run_case
 from tests.trace_util import replay_and_compare, setup_from_trace, trace_path
 
 pytestmark = pytest.mark.gpu
@@ -142,7 +138,7 @@ def tick_parity(shape, kind="plain", engine=None, ticks=TICKS):
         same_state(h, c, f"{shape} spawn")
         for t in range(ticks):
             try:
-                P._compare_full(h, c, 1, close=False)      # (one tick: maps, vehicle rows, groups, RNG streams, A* calls, counters)
+                compare_full(h, c, 1, close=False)      # (one tick: maps, vehicle rows, groups, RNG streams, A* calls, counters)
             except AssertionError as ex:
                 raise AssertionError(f"{shape} tick {t}: {ex}") from None
             same_state(h, c, f"{shape} tick {t}")
@@ -173,10 +169,10 @@ def test_quad_searcher(monkeypatch, shape, build):
     monkeypatch.setenv("TS_QUAD", "1")
     monkeypatch.setenv("TS_QUAD_MIN", "1")
     if build == "quadwin":      # windowed on both axes, or one window over the whole map rounded up to its nine tiles
-        assert min(shape) > QW.WINDOW or [(v + 7) // 8 * 8 for v in shape] == [QW.WINDOW, QW.WINDOW]
-    h = tick_parity(shape, engine=QW.quadwin_engine if build == "quadwin" else None)
+        assert min(shape) > QUADWIN_WINDOW or [(v + 7) // 8 * 8 for v in shape] == [QUADWIN_WINDOW, QUADWIN_WINDOW]
+    h = tick_parity(shape, engine=quadwin_engine if build == "quadwin" else None)
     try:
-        st = QW.check_stats(h.debug_quad_stats())
+        st = check_quad_stats(h.debug_quad_stats())
         print(build, shape, st)
         assert st["searches"] > 0 and st["jobs"] > st["handbacks"], st      # (the quads served searches of their own)
         if build == "quadwin" and shape == (100, 75):
@@ -361,14 +357,14 @@ def test_checkpoint_fresh_and_same_handle():
         for t in range(k, k + more):
             h.step(1), c.step(1)
             same_state(h, c, f"tick {t}")
-            straight.append(CK.full_state(h))
+            straight.append(deep_state(h))
         assert h.counters().astar_calls == c.counters().astar_calls > 0
         fresh.checkpoint_load(blob)
         h.checkpoint_load(blob)
         for t in range(more):
             fresh.step(1), h.step(1)
-            CK.assert_same_state(straight[t], CK.full_state(fresh), f"tick {k + t} on a fresh handle")
-            CK.assert_same_state(straight[t], CK.full_state(h), f"tick {k + t} after the rewind")
+            assert_same_deep_state(straight[t], deep_state(fresh), f"tick {k + t} on a fresh handle")
+            assert_same_deep_state(straight[t], deep_state(h), f"tick {k + t} after the rewind")
         same_state(fresh, c, "the fresh handle at the end"), same_state(h, c, "the rewound handle at the end")
     finally:
         h.close(), c.close(), fresh.close()

@@ -1,15 +1,14 @@
 """The device renderer (include/trafficsim_render.h) on the GPU: frames against the reference's own portrayal colours
 (tests/golden/render_*.npz), against the numpy statement of the pixel rule (tests/render_expect.py) over many views, the heat
 and route layers, the device-side frame buffer, a run that rendering does not change, and every refusal."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests import render_expect as rx
-from tests.test_render_expect import RENDER_FIXTURES, fixture_path
+from tests import procs
+from tests.engine_util import assert_same_state, full_state, refused
+from tests.render_expect import RENDER_FIXTURES, fixture_path
+from tests.render_scene import BG, Scene, to_view
 from tests.trace_util import replay_and_compare, setup_from_trace, trace_path
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import render as rn
@@ -17,114 +16,6 @@ from trafficsimulation_amd._lib import new_engine
 from trafficsimulation_amd.world import load_trace
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ROUTE_RGBA = (250, 10, 200, 140)
-BG = (17, 34, 51, 0)   # (the alpha byte of a background is ignored: a frame's alpha is 255)
-
-
-def to_view(v):
-    return rn.make_view(**{k: v[k] for k in v})
-
-
-class Scene:
-    """An engine replaying a trace one tick at a time, with everything the numpy model needs kept alongside: the order in
-    which vehicles entered their cells (rx.TopTracker), the tables that were uploaded, the routes that were listed."""
-
-    def __init__(self, path, ticks, configure=True):
-        self.tr = load_trace(path)
-        self.api = new_engine()
-        setup_from_trace(self.api, self.tr)
-        self.H, self.W = int(self.tr["height"]), int(self.tr["width"])
-        self.type = rn.type_plane(self.tr["cell_type_map"], self.tr.get("cell_base_type_map"))
-        self.cell_pal, self.veh_pal, self.lut = rn.cell_palette(), rn.vehicle_palette(), rn.heat_lut()
-        self.tracker = rx.TopTracker()
-        self.routes, self.route_mask = [], np.zeros((self.H, self.W), dtype=bool)
-        self._track()
-        if configure:
-            self.api.render_set_cells(self.type, self.cell_pal)
-            self.api.render_set_vehicle_palette(self.veh_pal)
-            self.api.render_set_heat_lut(self.lut)
-            self.api.observe_start()
-        for _ in range(ticks):
-            self.step()
-
-    @classmethod
-    def wrap(cls, api, tables, type_plane, cell_pal):
-        """A scene over an engine somebody else built (the facade's): the caller configures the renderer and steps through
-        `step` or calls `_track` after every tick of its own."""
-        s = cls.__new__(cls)
-        s.tr, s.api = tables, api
-        s.H, s.W = int(tables["height"]), int(tables["width"])
-        s.type, s.cell_pal, s.veh_pal, s.lut = np.asarray(type_plane).astype(np.uint8), cell_pal, rn.vehicle_palette(), rn.heat_lut()
-        s.tracker, s.routes = rx.TopTracker(), []
-        s._track()
-        return s
-
-    def _track(self):
-        rows = self.api.vehicles()
-        self.tracker.update(rows[:, 0], rows[:, 1], rows[:, 2])
-
-    def step(self):
-        self.api.step(1)
-        self._track()
-
-    def rows(self):
-        return self.api.vehicles()
-
-    def set_routes(self, ids, rgba=ROUTE_RGBA):
-        self.api.render_set_routes(ids, rgba)
-        self.routes = list(ids)
-
-    def path_mask(self, ids):
-        """Union of the ts_download_path cells of the listed vehicles that are alive."""
-        rows = self.rows()
-        pos_of = {int(s): i for i, s in enumerate(rows[:, 0])}
-        m = np.zeros((self.H, self.W), dtype=bool)
-        for v in ids:
-            if v in pos_of:
-                m |= rx.mask_of(self.api.path(pos_of[v]), self.H, self.W)
-        return m
-
-    def state(self, heat="present"):
-        api = self.api
-        rows, meta = self.rows(), api.vehicle_meta()
-        assert np.array_equal(rows[:, 0], meta[:, 0])
-        codes = rx.vehicle_code(rows[:, capi.V_FIELDS.index("flags")], meta[:, capi.M_FIELDS.index("service_phase")] >= 0)
-        top, tied = self.tracker.top(rows[:, 0], codes, self.H, self.W)
-        if tied:
-            # vehicles that entered one cell in the same tick: the host cannot know which is the tail of the list.  Take the
-            # engine's own choice from a vehicles-only frame, insist that it is one of the candidates, and hold every other
-            # view to it.
-            vp = self.veh_pal.reshape(12, 2, 4)
-            flash = 1 if api.counters().step_count % 2 == 0 else 0
-            f = api.render(rn.make_view(cells_w=self.W, cells_h=self.H, layers=capi.RL_VEHICLES))
-            for (x, y), cs in tied.items():
-                match = [c for c in sorted(cs) if tuple(f[y, x]) == tuple(vp[c, flash])]
-                assert match, f"cell {(x, y)}: the frame shows {f[y, x]}, none of the vehicles {sorted(cs)} of that cell"
-                top[y, x] = match[0]
-        if heat == "flow":
-            hv = sum(api.observe_plane(p).astype(np.uint64) for p in capi.OBS_ENTER)
-        else:
-            hv = api.observe_plane(heat).astype(np.uint64)
-        return {"W": self.W, "H": self.H, "type": self.type, "cell_pal": self.cell_pal, "veh_pal": self.veh_pal, "lut": self.lut,
-                "stop": api.map(capi.MAP_STOP), "rain": api.map(capi.MAP_RAIN),
-                "pend": rx.pending_mask(self.tr, api.groups()[:, capi.G_FIELDS.index("pending_phase")], self.H, self.W),
-                "top": top, "route": self.path_mask(self.routes), "route_rgba": ROUTE_RGBA, "heat": hv,
-                "step_count": int(api.counters().step_count)}
-
-    def check(self, view, state=None, ctx=""):
-        v = dict(background=BG, **view)
-        st = state if state is not None else self.state(v.get("heat_plane", "present"))
-        want = rx.render(st, {**v, "layers": capi.render_layer_mask(v.get("layers"))})
-        got = self.api.render(to_view(v))
-        assert got.shape == want.shape, f"{ctx} {view}: frame is {got.shape}, the rule gives {want.shape}"
-        if not np.array_equal(got, want):
-            bad = np.argwhere((got != want).any(axis=2))
-            r, p = bad[0]
-            raise AssertionError(f"{ctx} {view}: {len(bad)} pixels differ, first at row {r} column {p}: got {got[r, p]} want {want[r, p]}")
-        return got
-
 
 WORLDS = {"render": (fixture_path(RENDER_FIXTURES[0]), None), "ragged": (trace_path("ragged_100x75_s33"), 40)}
 
@@ -236,9 +127,7 @@ def test_routes_are_the_downloaded_paths(scene):
             if what in ("empty path", "only a removed vehicle", "cleared"):
                 assert not want.any()
         assert len(long_ones) or scene.W != 100, "the ragged world is expected to hold a path longer than 64 steps"
-        with pytest.raises(capi.EngineError) as ex:
-            api.render_set_routes([api.num_spawned()], colour)
-        assert ex.value.code == capi.TS_E_INVALID
+        refused(capi.TS_E_INVALID, lambda: api.render_set_routes([api.num_spawned()], colour))
     finally:
         scene.set_routes(old)
 
@@ -285,10 +174,6 @@ def replay_and_compare_from(api, tr, t0, t1):
 
 # ---- the frame buffer on the device ----------------------------------------------------------------------------------------
 DEVICE_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
-import torch                     # (first: the engine library then shares torch's HIP runtime)
-torch.cuda.init()
 import numpy as np
 from trafficsimulation_amd import _capi as capi, render as rn
 from trafficsimulation_amd._lib import new_engine
@@ -319,28 +204,16 @@ assert d.data_ptr() == c.data_ptr() and np.array_equal(d.cpu().numpy(), api.rend
 info = api.render_info()
 assert info["frames"] == 8 and (info["last_w"], info["last_h"]) == (100, 75)
 api.close()
-print("DEVICE_OK")
 '''
 
 
-def test_device_output(tmp_path):
+def test_device_output():
     """render_device(): a torch tensor over the engine's own frame buffer.  In a process of its own that imports torch before
     it loads the engine, like the observe_device test."""
-    script = tmp_path / "render_device.py"
-    script.write_text(DEVICE_SCRIPT % dict(root=ROOT))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(DEVICE_SCRIPT, torch_first=True, timeout=300)
 
 
 # ---- rendering changes nothing --------------------------------------------------------------------------------------------
-def full_state(api):
-    c = api.counters()
-    return {"maps": [api.map(w) for w in (capi.MAP_OCCUPANCY, capi.MAP_STOP, capi.MAP_STUCK, capi.MAP_RAIN)],
-            "veh": api.vehicles(), "groups": api.groups(),
-            "rng": [api.rng_fingerprint(capi.RNG_GLOBAL), api.rng_fingerprint(capi.RNG_SCHEDULER)],
-            "counters": [getattr(c, f) for f, _ in capi.TsCounters._fields_], "blob": api.checkpoint_save()}
-
-
 def test_purity():
     """One run renders every tick with all layers, the other never configures the renderer: identical state, identical
     checkpoint bytes.  (Observation, which the heat layer needs, is not simulation state either: both runs observe.)"""
@@ -357,19 +230,14 @@ def test_purity():
         rows = a.api.vehicles()
         a.api.render_set_routes(rows[:8, 0])
         a.api.render(view)
-    sa, sb = full_state(a.api), full_state(b.api)
-    for i, (p, q) in enumerate(zip(sa["maps"], sb["maps"])):
-        assert np.array_equal(p, q), f"map {i}"
-    assert np.array_equal(sa["veh"], sb["veh"]) and np.array_equal(sa["groups"], sb["groups"])
-    assert sa["rng"] == sb["rng"] and sa["counters"] == sb["counters"]
-    assert sa["blob"] == sb["blob"], "checkpoint bytes differ"
+    assert_same_state(full_state(a.api), full_state(b.api), "rendered every tick")
     assert a.api.render_info()["frames"] == 60
     a.api.close()
     b.api.close()
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------
-def test_refusals_leave_the_frame_buffer_alone(tmp_path):
+def test_refusals_leave_the_frame_buffer_alone():
     s = Scene(trace_path("ragged_100x75_s33"), 5, configure=False)
     api, W, H = s.api, s.W, s.H
     ok = dict(x0=0, y0=0, cells_w=W, cells_h=H, layers=0, background=BG)
@@ -379,29 +247,26 @@ def test_refusals_leave_the_frame_buffer_alone(tmp_path):
     frame = api.render(to_view(ok))
     frames0 = api.render_info()["frames"]
 
-    def refused(code, view=None, call=None):
-        with pytest.raises(capi.EngineError) as ex:
-            call() if call else api.render(to_view(dict(ok, **view)))
-        assert ex.value.code == code, (view, ex.value)
+    def refused_views(code, *views):
+        refused(code, *(lambda view=view: api.render(to_view(dict(ok, **view))) for view in views))
 
-    for bad in (dict(zoom=0), dict(zoom=65), dict(shrink=0), dict(shrink=65), dict(zoom=2, shrink=2), dict(cells_w=0), dict(cells_h=-1),
-                dict(layers=32), dict(vehicle_radius_256=-1), dict(layers=capi.RL_HEAT, heat_plane=8), dict(layers=capi.RL_HEAT, heat_plane=-1),
-                dict(layers=capi.RL_HEAT, heat_plane=0, heat_max=0)):
-        refused(capi.TS_E_INVALID, bad)
-    refused(capi.TS_E_CAPACITY, dict(cells_w=8193))
-    refused(capi.TS_E_CAPACITY, dict(cells_h=129, zoom=64))
-    refused(capi.TS_E_CAPACITY, dict(cells_w=8192 * 64 + 1, shrink=64))
-    refused(capi.TS_E_STATE, dict(layers=capi.RL_VEHICLES))                       # no vehicle palette
-    refused(capi.TS_E_STATE, dict(layers=capi.RL_HEAT, heat_plane=0, heat_max=1))  # no LUT
+    refused_views(capi.TS_E_INVALID, dict(zoom=0), dict(zoom=65), dict(shrink=0), dict(shrink=65), dict(zoom=2, shrink=2), dict(cells_w=0), dict(cells_h=-1),
+                  dict(layers=32), dict(vehicle_radius_256=-1), dict(layers=capi.RL_HEAT, heat_plane=8), dict(layers=capi.RL_HEAT, heat_plane=-1),
+                  dict(layers=capi.RL_HEAT, heat_plane=0, heat_max=0))
+    refused_views(capi.TS_E_CAPACITY, dict(cells_w=8193))
+    refused_views(capi.TS_E_CAPACITY, dict(cells_h=129, zoom=64))
+    refused_views(capi.TS_E_CAPACITY, dict(cells_w=8192 * 64 + 1, shrink=64))
+    refused_views(capi.TS_E_STATE, dict(layers=capi.RL_VEHICLES))                       # no vehicle palette
+    refused_views(capi.TS_E_STATE, dict(layers=capi.RL_HEAT, heat_plane=0, heat_max=1))  # no LUT
     api.render_set_heat_lut(s.lut)
-    refused(capi.TS_E_STATE, dict(layers=capi.RL_HEAT, heat_plane=0, heat_max=1))  # not observed
+    refused_views(capi.TS_E_STATE, dict(layers=capi.RL_HEAT, heat_plane=0, heat_max=1))  # not observed
     api.observe_start(["present", "enter_n"])
-    refused(capi.TS_E_STATE, dict(layers=capi.RL_HEAT, heat_plane="waiting", heat_max=1))
-    refused(capi.TS_E_STATE, dict(layers=capi.RL_HEAT, heat_plane="flow", heat_max=1))   # flow needs all four ENTER planes
-    refused(capi.TS_E_INVALID, call=lambda: api.render_set_routes([-1]))
-    refused(capi.TS_E_INVALID, call=lambda: api.render_set_routes([api.num_spawned()]))
-    refused(capi.TS_E_INVALID, call=lambda: api.render_set_routes(list(range(1)) * 4097))
-    refused(capi.TS_E_INVALID, call=lambda: api.render_set_cells(np.full((H, W), len(rn.RENDER_TYPE_NAMES), dtype=np.uint8), s.cell_pal))
+    refused_views(capi.TS_E_STATE, dict(layers=capi.RL_HEAT, heat_plane="waiting", heat_max=1))
+    refused_views(capi.TS_E_STATE, dict(layers=capi.RL_HEAT, heat_plane="flow", heat_max=1))   # flow needs all four ENTER planes
+    refused(capi.TS_E_INVALID, lambda: api.render_set_routes([-1]))
+    refused(capi.TS_E_INVALID, lambda: api.render_set_routes([api.num_spawned()]))
+    refused(capi.TS_E_INVALID, lambda: api.render_set_routes(list(range(1)) * 4097))
+    refused(capi.TS_E_INVALID, lambda: api.render_set_cells(np.full((H, W), len(rn.RENDER_TYPE_NAMES), dtype=np.uint8), s.cell_pal))
     # null pointers, straight at the C entries
     lib, h = api.lib, api.h
     v = to_view(ok)
@@ -417,18 +282,11 @@ def test_refusals_leave_the_frame_buffer_alone(tmp_path):
     assert info["frames"] == frames0 and (info["last_w"], info["last_h"]) == (W, H)
     # the frame buffer still holds the last good frame: a device-side copy of it, read through a second good frame's pointer
     # being the same buffer is what test_device_output shows; here the bytes, through the one entry that hands them out
-    script = tmp_path / "buffer_after_refusal.py"
-    script.write_text(REFUSAL_SCRIPT % dict(root=ROOT))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "REFUSAL_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(REFUSAL_SCRIPT, torch_first=True, timeout=300)
     api.close()
 
 
 REFUSAL_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
-import torch
-torch.cuda.init()
 import numpy as np
 from trafficsimulation_amd import _capi as capi, render as rn
 from trafficsimulation_amd._lib import new_engine
@@ -455,5 +313,4 @@ for bad in (rn.make_view(cells_w=100, cells_h=75, zoom=65), rn.make_view(cells_w
     assert np.array_equal(t.cpu().numpy(), before), "a refused call wrote to the frame buffer"
 assert api.render_info()["frames"] == 1
 api.close()
-print("REFUSAL_OK")
 '''

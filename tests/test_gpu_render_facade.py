@@ -4,22 +4,19 @@ pickle, and examples/run_city.py --frames."""
 import copy
 import os
 import pickle
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import render_expect as rx
-from tests.test_gpu_render import BG, Scene
+from tests.engine_util import city_model, run_example
+from tests.render_scene import BG, Scene
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import render as rn
 from trafficsimulation_amd.mesa_api import CityModel
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "examples"))
 TICKS = 40
 
 
@@ -27,9 +24,8 @@ TICKS = 40
 def city():
     """CityModel() as the reference ships it (200 x 200) with a busier day, stepped TICKS ticks with the entering order of
     the vehicles tracked for the model."""
-    from run_city import TRAFFIC
-    m = CityModel(200, 200, seed=5, traffic=dict(TRAFFIC, P_int=200000, P_thr=60000, service_food=400, service_waste=400),
-                  defaults={"RAIN_SPAWN_CHANCE": 0.3, "RAIN_RADIUS_MIN": 10, "RAIN_RADIUS_MAX": 30})
+    m = city_model(200, seed=5, traffic=dict(P_int=200000, P_thr=60000, service_food=400, service_waste=400),
+                   defaults={"RAIN_SPAWN_CHANCE": 0.3, "RAIN_RADIUS_MIN": 10, "RAIN_RADIUS_MAX": 30})
     m.observe()
     plane, names = m.render_type_plane()
     assert names == rn.RENDER_TYPE_NAMES and (plane >= 18).any() and plane.shape == (200, 200)
@@ -107,9 +103,7 @@ def test_save_load_copy_and_pickle_render_again(city, tmp_path):
 
 def test_run_city_writes_frames(tmp_path):
     out = tmp_path / "frames"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "run_city.py"), "--size", "96", "--ticks", "30", "--frames", str(out),
-                        "--frame-every", "10", "--zoom", "2"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    run_example("run_city.py", "--size", 96, "--ticks", 30, "--frames", out, "--frame-every", 10, "--zoom", 2)
     files = sorted(os.listdir(out))
     assert len(files) == 3 and files[0].startswith("frame_000010."), files
     path = os.path.join(out, files[0])

@@ -15,7 +15,7 @@ from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import _lib
 from trafficsimulation_amd import citygen
 from trafficsimulation_amd.world import build_engine, load_trace
-from tests.test_gpu_forced_paths import small_engine
+from tests.engine_util import small_engine
 from tests.trace_util import setup_from_trace, trace_path
 
 pytestmark = pytest.mark.gpu

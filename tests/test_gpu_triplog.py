@@ -3,24 +3,21 @@ they must be (tests/triplog_util.py), a run the log does not change, capacity, a
 removals, checkpoints, the sharded mode, the life cycle and the facade."""
 import copy
 import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
 from tests import observe_util as ou
+from tests import engine_util as eu
+from tests import procs
 from tests import triplog_util as tu
-from tests.test_gpu_observe import assert_same_state, full_state
-from tests.trace_util import replay_and_compare, setup_from_trace, trace_path
+from tests.engine_util import assert_same_state, full_state, refused
+from tests.trace_util import replay_and_compare
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 V = ou.V
 M = {n: i for i, n in enumerate(capi.M_FIELDS)}
 ARRIVED, DESPAWNED, REMOVED = tu.ARRIVED, tu.DESPAWNED, tu.REMOVED
@@ -29,18 +26,7 @@ CAP = 1 << 14
 
 def engine_for(name, log=CAP):
     """An engine set up from a trace; the log (if any) is on before the first vehicle is placed."""
-    tr = load_trace(trace_path(name))
-    api = new_engine()
-    start = api.create
-
-    def create(*a, **k):
-        r = start(*a, **k)
-        if log:
-            api.triplog_start(log)
-        return r
-    api.create = create
-    setup_from_trace(api, tr, explicit_paths=False)
-    return api, tr
+    return eu.engine_for(name, after_create=(lambda api: api.triplog_start(log)) if log else None)
 
 
 def seq_of(rec):
@@ -295,9 +281,7 @@ def grid_zones(H, W, cell=16, stripe=(40, 44)):
 
 def test_od_matrices(closed_logs):
     api, tr, _, rec, _ = closed_logs("full_96_s8")
-    with pytest.raises(capi.EngineError) as ex:      # no plane yet
-        api.triplog_od()
-    assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, api.triplog_od)     # no plane yet
     zone, nz = grid_zones(96, 96)
     assert nz == 36
     api.triplog_set_zones(zone, nz)
@@ -310,16 +294,10 @@ def test_od_matrices(closed_logs):
     assert set(only) == {"count", "unzoned"} and np.array_equal(only["count"], cnt)
     assert api.triplog_od(["arrived"], count=False, duration=False, distance=False) == {"unzoned": unz}
     for bad in (1025, -1):
-        with pytest.raises(capi.EngineError) as ex:
-            api.triplog_set_zones(zone, bad)
-        assert ex.value.code == capi.TS_E_INVALID
-    with pytest.raises(capi.EngineError) as ex:
-        api.triplog_od(8)
-    assert ex.value.code == capi.TS_E_INVALID
+        refused(capi.TS_E_INVALID, lambda: api.triplog_set_zones(zone, bad))
+    refused(capi.TS_E_INVALID, lambda: api.triplog_od(8))
     api.triplog_set_zones(None, 0)                    # drops the plane
-    with pytest.raises(capi.EngineError) as ex:
-        api.triplog_od()
-    assert ex.value.code == capi.TS_E_STATE
+    refused(capi.TS_E_STATE, api.triplog_od)
 
 
 def test_od_of_the_despawned(closed_logs):
@@ -390,41 +368,22 @@ def test_checkpoint_load_keeps_the_log_and_forgets_origins():
 
 # ---- 10. sharded mode: every rank holds the same log ---------------------------------------------------------------------
 WORKER = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
-from trafficsimulation_amd import dist as tdist
-from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
-from tests.trace_util import setup_from_trace, replay_and_compare, trace_path
-rank, local, world = tdist.env_rank()
-d = tdist.init("gloo", rank, world)
-tr = load_trace(trace_path(%(trace)r))
-api = new_engine()
-start = api.create
-api.create = lambda *a, **k: (start(*a, **k), api.triplog_start(%(cap)d))[0]
-setup_from_trace(api, tr, explicit_paths=False)
+from tests.engine_util import engine_for
+from tests.trace_util import replay_and_compare
+api, tr = engine_for(%(trace)r, after_create=lambda api: api.triplog_start(%(cap)d))
 sr = tdist.ShardedReplans().attach(api)
 n = replay_and_compare(api, tr)
 assert sr.calls > 0
-np.save(os.path.join(%(outdir)r, "trips%%d.npy" %% rank), api.trips())
+np.save(os.path.join(OUTDIR, "trips%%d.npy" %% rank), api.trips())
 api.close()
-d.destroy_process_group()
 '''
 
 
 def test_sharded_ranks_hold_equal_logs(closed_logs):
-    name, port = "full_96_s8", "29731"
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    with tempfile.TemporaryDirectory() as outdir:
-        path = os.path.join(outdir, "worker.py")
-        with open(path, "w") as f:
-            f.write(WORKER % dict(root=ROOT, trace=name, outdir=outdir, cap=CAP))
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-               "--master-addr", "127.0.0.1", "--master-port", port, path]
-        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
-        ranks = [np.load(os.path.join(outdir, f"trips{r}.npy")) for r in range(2)]
+    name = "full_96_s8"
+    _, saved, _ = procs.run_ranks(WORKER, 2, timeout=600, trace=name, cap=CAP)
+    ranks = [saved[f"trips{r}.npy"] for r in range(2)]
     single = closed_logs(name)[3]
     assert len(single) > 0 and ranks[0].dtype == capi.TRIP_DTYPE
     assert ranks[0].tobytes() == ranks[1].tobytes() == single.tobytes()
@@ -436,24 +395,15 @@ def test_lifecycle_and_errors():
     zero = {"capacity": 0, "count": 0, "dropped": 0, "groups": 0, "device_bytes": 0}
     assert api.has_triplog and api.triplog_info() == zero
     zone = np.zeros((64, 64), dtype=np.int32)
-    for call in (api.triplog_stop, api.triplog_clear, api.trips, lambda: api.trips(0, 4), api.triplog_device,
-                 lambda: api.triplog_set_zones(zone, 1), api.triplog_od):
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_STATE
-    for bad in (0, -5):
-        with pytest.raises(capi.EngineError) as ex:
-            api.triplog_start(bad)
-        assert ex.value.code == capi.TS_E_INVALID
+    refused(capi.TS_E_STATE, api.triplog_stop, api.triplog_clear, api.trips, lambda: api.trips(0, 4), api.triplog_device,
+            lambda: api.triplog_set_zones(zone, 1), api.triplog_od)
+    refused(capi.TS_E_INVALID, lambda: api.triplog_start(0), lambda: api.triplog_start(-5))
     assert api.triplog_info() == zero
     api.triplog_start(100)
     info = api.triplog_info()
     assert info["capacity"] == 100 and info["count"] == 0 and info["device_bytes"] >= 100 * 72
-    for call in (lambda: api.trips(-1, 2), lambda: api.trips(0, -2), lambda: api.triplog_set_zones(None, 3),
-                 lambda: api.triplog_set_zones(zone, 1025), lambda: api.triplog_set_zones(zone, -1)):
-        with pytest.raises(capi.EngineError) as ex:
-            call()
-        assert ex.value.code == capi.TS_E_INVALID
+    refused(capi.TS_E_INVALID, lambda: api.trips(-1, 2), lambda: api.trips(0, -2), lambda: api.triplog_set_zones(None, 3),
+            lambda: api.triplog_set_zones(zone, 1025), lambda: api.triplog_set_zones(zone, -1))
     fn = api._ext("triplog_info")
     assert fn(api.h, None) == capi.TS_E_INVALID
     assert api._ext("triplog_device")(api.h, None, None) == capi.TS_E_INVALID
@@ -469,11 +419,9 @@ def test_lifecycle_and_errors():
 
 
 # ---- 12. the facade ------------------------------------------------------------------------------------------------------
-def test_facade_trips_and_od_matrix():
+def test_facade_trips_and_od_matrix(tmp_path):
     from trafficsimulation_amd.mesa_api import CityModel
-    sys.path.insert(0, os.path.join(ROOT, "examples"))
-    from run_city import TRAFFIC
-    m = CityModel(width=64, height=64, seed=3, traffic=dict(TRAFFIC), trip_log=4096)
+    m = eu.city_model(64, seed=3, trip_log=4096)
     for _ in range(400):
         m.step()
         if len(m.trips()) > 0 and (m.trips()["end_reason"] == ARRIVED).any():
@@ -491,7 +439,7 @@ def test_facade_trips_and_od_matrix():
     assert np.array_equal(od["mean_distance"][some], dist[some] / cnt[some])
     twin = copy.deepcopy(m)
     assert twin.engine.triplog_info()["capacity"] == 0 and m.engine.triplog_info()["capacity"] == 4096
-    path = os.path.join(tempfile.mkdtemp(), "m.npz")
+    path = os.path.join(tmp_path, "m.npz")
     m.save(path)
     loaded = CityModel.load(path)
     assert loaded.engine.triplog_info()["capacity"] == 0
@@ -500,17 +448,8 @@ def test_facade_trips_and_od_matrix():
 
 
 DEVICE_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, %(root)r)
-import torch                     # (first: the engine library then shares torch's HIP runtime)
-torch.cuda.init()
-import numpy as np
-from trafficsimulation_amd import _capi as capi
-from trafficsimulation_amd._lib import new_engine
-from trafficsimulation_amd.world import load_trace
-from tests.trace_util import setup_from_trace, trace_path
-api = new_engine()
-setup_from_trace(api, load_trace(trace_path("carve_96_s10")), explicit_paths=False)
+from tests.engine_util import engine_for
+api, _ = engine_for("carve_96_s10")
 api.triplog_start(1000)
 api.step(60)
 host = api.trips()
@@ -519,14 +458,10 @@ assert t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (len(host), 18
 assert t.cpu().numpy().tobytes() == host.tobytes()
 assert int(t[:, 12].sum()) == int(host["distance"].sum())      # (consumed on the device)
 api.close()
-print("DEVICE_OK")
 '''
 
 
-def test_device_pointer_is_the_log(tmp_path):
+def test_device_pointer_is_the_log():
     """triplog_device(): a torch tensor over the engine's own records.  In a process of its own that imports torch before it
     loads the engine, the way the torch-side callers (dist.py) run."""
-    script = tmp_path / "triplog_device.py"
-    script.write_text(DEVICE_SCRIPT % dict(root=ROOT))
-    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DEVICE_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    procs.run_python(DEVICE_SCRIPT, torch_first=True, timeout=300)

@@ -3,8 +3,7 @@ the expected results (the CPU-oracle twin of this test is tests/test_worldgen.py
 import pytest
 
 from trafficsimulation_amd.world import load_trace
-from tests.test_worldgen import _seed_only
-from tests.trace_util import check_initial, replay_and_compare, setup_from_trace, trace_path
+from tests.trace_util import check_initial, replay_and_compare, seed_only, setup_from_trace, trace_path
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +18,7 @@ def hip():
 
 @pytest.mark.parametrize("name,ticks", [("config1_64_s11", 300), ("config5_96_s17", 150), ("rain_96_s14", 120), ("rect_96x64_s18", 150), ("default_200_s20", 160)])
 def test_seed_only_run_reproduces_reference_trace(hip, name, ticks):
-    tr = _seed_only(load_trace(trace_path(name)))
+    tr = seed_only(load_trace(trace_path(name)))
     setup_from_trace(hip, tr)
     check_initial(hip, tr)
     assert replay_and_compare(hip, tr, ticks=ticks) == ticks

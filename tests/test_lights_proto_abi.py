@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests.abi_util import ROOT, c_layout, declared, header, hip_lib, oracle_api
+from tests.engine_util import refused
 from trafficsimulation_amd import _capi as capi
 
 ENTRIES = ["ts_lights_proto_act", "ts_lights_proto_act_q", "ts_lights_proto_config", "ts_lights_proto_device",
@@ -60,18 +61,14 @@ def test_oracle_protocols_are_unsupported(call):
              "observe": api.lights_proto_observe, "act": lambda: api.lights_proto_act(z),
              "act_q": lambda: api.lights_proto_act_q(np.zeros((3, 2), np.float32)), "controller": api.lights_proto_controller,
              "device": api.lights_proto_device}
-    with pytest.raises(capi.EngineError) as ex:
-        calls[call]()
-    assert ex.value.code == capi.TS_E_UNSUPPORTED
+    refused(capi.TS_E_UNSUPPORTED, calls[call])
 
 
 def test_params_still_refuse_the_names():
     """The translation to EXTERNAL plus a protocol is world.build_engine's; params_from_defaults knows light algorithms only."""
     api = oracle_api()
     for name in ("RL_A2C_BATCHED", "GAT_DQN_BATCHED", "GAT_DQN", "NEIGHBOR_RL"):
-        with pytest.raises(capi.EngineError) as ex:
-            api.params_from_defaults({"TRAFFIC_LIGHT_AGENT_ALGORITHM": name})
-        assert ex.value.code == capi.TS_E_UNSUPPORTED
+        refused(capi.TS_E_UNSUPPORTED, lambda: api.params_from_defaults({"TRAFFIC_LIGHT_AGENT_ALGORITHM": name}))
 
 
 def test_recorded_kernel_resources_of_the_hot_kernels_equal_the_parents():

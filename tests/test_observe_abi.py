@@ -6,6 +6,7 @@ import re
 import pytest
 
 from tests.abi_util import declared, header, hip_lib, oracle_api
+from tests.engine_util import refused
 from trafficsimulation_amd import _capi as capi
 
 ENTRIES = ["ts_observe_device", "ts_observe_download", "ts_observe_groups", "ts_observe_info", "ts_observe_pooled",
@@ -49,6 +50,4 @@ def test_oracle_observation_is_unsupported(call):
              "plane": lambda: api.observe_plane("present"), "pooled": lambda: api.observe_pooled("present", 2),
              "regions": lambda: api.observe_regions("present", [(0, 0, 1, 1)]), "groups": api.observe_groups,
              "device": lambda: api.observe_device("present")}
-    with pytest.raises(capi.EngineError) as ex:
-        calls[call]()
-    assert ex.value.code == capi.TS_E_UNSUPPORTED
+    refused(capi.TS_E_UNSUPPORTED, calls[call])

@@ -4,16 +4,10 @@ import numpy as np
 import pytest
 
 from tests import observe_util as ou
+from tests.observe_util import REPLAN_TRACES
 from tests.trace_util import NO_ASTAR_TRACES, trace_path
 from trafficsimulation_amd.world import load_trace
 
-# The trace with replanning whose ENTER planes are reconstructed from the rows under the caps below.  The traces the work
-# started from - full_96_s8, default_200_s20 and the nobatch_* family - do not meet the caps (figures in
-# test_reconstructed_traces_are_mostly_certain); of the golden traces in which a search runs only unopt_96_s21 does
-# (39 516 searches in 200 ticks), so it is the one chosen.  The others stay in the GPU test as extra ground
-# (UNCAPPED_REPLAN_TRACES): what is certain in them is checked all the same.
-REPLAN_TRACES = ["unopt_96_s21"]
-UNCAPPED_REPLAN_TRACES = ["full_96_s8", "default_200_s20", "nobatch_config1_64_s29"]
 MAX_UNCERTAIN_SHARE = 0.02      # uncertain moved cells / all moved cells of a trace
 MIN_CLEAN_TICKS = 0.5           # share of ticks without an uncertain cell
 

@@ -3,25 +3,19 @@
 reference's get_portrayal() gave; render.py's name table and desaturate agree with matplotlib and the reference on every colour
 the fixture holds."""
 import json
-import os
 
 import numpy as np
 import pytest
 
 from tests import render_expect as rx
-from tests.trace_util import GOLDEN, _unpack
+from tests.render_expect import RENDER_FIXTURES, fixture_path
+from tests.engine_util import refused
+from tests.trace_util import _unpack, world_options
 from trafficsimulation_amd import _capi as capi
 from trafficsimulation_amd import render as rn
 from trafficsimulation_amd.mesa_api import Defaults
 from trafficsimulation_amd.world import load_trace
 from trafficsimulation_amd.worldgen import CELL_TYPE_NAMES
-
-RENDER_FIXTURES = ["render_city_64_s56"]
-
-
-def fixture_path(name):
-    return os.path.join(GOLDEN, f"{name}.npz")
-
 
 _cache = {}
 
@@ -156,9 +150,7 @@ def test_palettes_shapes_and_rules():
 def test_assigned_cell_colour_on_stop_is_refused():
     class D(Defaults):
         CHANGE_ASSIGNED_CELL_COLOR_ON_STOP = True
-    with pytest.raises(capi.EngineError) as ex:
-        rn.cell_palette(D)
-    assert ex.value.code == capi.TS_E_UNSUPPORTED
+    refused(capi.TS_E_UNSUPPORTED, lambda: rn.cell_palette(D))
 
 
 def test_model_scaling_rules_on_a_hand_made_state():
@@ -194,12 +186,11 @@ def test_model_scaling_rules_on_a_hand_made_state():
 @pytest.mark.parametrize("name", RENDER_FIXTURES)
 def test_worldgen_knows_the_base_type_of_controlled_roads(name):
     """cell_base_type_map from (size, seed) alone is the reference's: CellAgent.road_type under every ControlledRoad."""
-    from tests.test_worldgen import _options
     from trafficsimulation_amd.worldgen import generate_world
     tr = fixture(name)
     sc = tr["scenario"]
     w = generate_world(sc["size"], sc.get("height", sc["size"]), seed=sc["seed"], cell_base_types=True,
-                       **_options(sc.get("model_kwargs", {}), tr["defaults_json"]))
+                       **world_options(sc.get("model_kwargs", {}), tr["defaults_json"]))
     assert np.array_equal(w["cell_type_map"], tr["cell_type_map"]) and np.array_equal(w["cell_base_type_map"], tr["cell_base_type_map"])
     ctrl = np.asarray(tr["cell_type_map"]) == CELL_TYPE_NAMES.index("ControlledRoad")
     assert ctrl.any() and (np.asarray(tr["cell_base_type_map"])[~ctrl] == np.asarray(tr["cell_type_map"])[~ctrl]).all()

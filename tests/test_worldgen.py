@@ -6,27 +6,17 @@ Every table is compared bit for bit, and so is the MT19937 state the generator l
 import glob
 import json
 import os
-import random
 
 import numpy as np
 import pytest
 
 from trafficsimulation_amd.world import load_trace
 from trafficsimulation_amd.worldgen import generate_world
-from tests.trace_util import GOLDEN, check_initial, replay_and_compare, setup_from_trace, trace_path
+from tests.trace_util import GOLDEN, check_initial, replay_and_compare, seed_only as _seed_only, setup_from_trace, trace_path, world_options as _options
 
 _WORLDS = np.load(os.path.join(GOLDEN, "worlds.npz"), allow_pickle=False)
 _INDEX = json.loads(str(_WORLDS["index"]))
 _EXC = {"ZeroDivisionError": ZeroDivisionError, "IndexError": IndexError, "ValueError": ValueError, "KeyError": KeyError}
-
-
-def _options(kwargs, defaults):
-    opts = dict(kwargs)
-    opts["rain_enabled"] = defaults.get("RAIN_ENABLED", True)
-    opts["enable_traffic"] = defaults.get("ENABLE_TRAFFIC", True)
-    if "BLOCK_ENTRANCE_ROAD_LEVEL" in defaults:
-        opts["block_entrance_road_level"] = defaults["BLOCK_ENTRANCE_ROAD_LEVEL"]
-    return opts
 
 
 @pytest.mark.parametrize("entry", _INDEX, ids=[e["tag"] for e in _INDEX])
@@ -57,19 +47,6 @@ def test_trace_world_matches_reference(path):
                 assert np.array_equal(w[k], tr["global_rng_before_day0"])
         elif k in tr:                              # older fixtures hold fewer block tables
             assert np.asarray(w[k]).shape == tr[k].shape and np.array_equal(w[k], tr[k]), f"table {k} differs"
-
-
-def _seed_only(tr):
-    """The fixture with every world table, and both stream states, replaced by what (size, seed) alone yields."""
-    sc = tr["scenario"]
-    w = generate_world(sc["size"], sc.get("height", sc["size"]), seed=sc["seed"], **_options(sc.get("model_kwargs", {}), tr["defaults_json"]))
-    out = dict(tr)
-    for k, v in w.items():
-        if k != "global_rng_state":
-            out[k] = v
-    out["global_rng_before_day0"] = w["global_rng_state"]
-    out["sched_rng_initial"] = np.asarray(random.Random(sc["seed"]).getstate()[1], dtype=np.uint32)   # Model(seed=seed).random
-    return out
 
 
 @pytest.mark.parametrize("name,ticks", [("config1_64_s11", 200), ("service_64_s15", 120), ("default_200_s20", 160)])
