@@ -38,18 +38,6 @@ void cf_launch_finish(const CostFieldArgs& a, uint32_t* val, int32_t* own, unsig
     else { if (to) fn<1, true>(__VA_ARGS__); else fn<1, false>(__VA_ARGS__); }           \
   } while (0)
 
-// what a compute holds on the device besides the result: freed on every way out
-struct CfScratch {
-  void* p[8] = {};
-  int n = 0;
-  template <typename T> hipError_t get(T** out, size_t count) {
-    hipError_t r = hipMalloc((void**)out, std::max<size_t>(count, 1) * sizeof(T));
-    if (r == hipSuccess) p[n++] = (void*)*out;
-    return r;
-  }
-  ~CfScratch() { for (int k = 0; k < n; k++) (void)hipFree(p[k]); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -84,7 +72,7 @@ int ts_costfield_compute(ts_handle e, const TsCostFieldQuery* q, TsCostFieldInfo
   hipStream_t st = e->stream;
   // Everything is allocated before anything is computed, the new planes beside the ones held (the spare pair of the previous
   // compute when there is one): whatever refuses this call from here on leaves the previous result as it is.
-  CfScratch S;
+  Scratch S;   // what the call holds on the device besides the result
   uint32_t* cw = nullptr; u64 *lab = nullptr, *seed = nullptr;
   uint32_t* ctl = nullptr;           // [0, 2) list lengths by parity, [2, 2 + 2 n_tiles) flags by parity
   int32_t *lists = nullptr, *d_xy = nullptr, *d_cost = nullptr;
@@ -187,9 +175,7 @@ int ts_costfield_download(ts_handle e, int32_t which, void* dst) {
   if (!dst) return fail(e, TS_E_INVALID, "cost field: null pointer");
   const uint32_t* src = nullptr;
   TRY(cf_plane(e, which, &src));
-  HIPOK(hipMemcpyAsync(dst, src, (size_t)e->N * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  return TS_OK;
+  return read_back(e, dst, src, (size_t)e->N * sizeof(uint32_t));
 }
 
 int ts_costfield_gather(ts_handle e, int32_t which, int32_t n, const int32_t* xy, void* out) {
@@ -201,7 +187,7 @@ int ts_costfield_gather(ts_handle e, int32_t which, int32_t n, const int32_t* xy
     if (xy[2 * i] < 0 || xy[2 * i] >= e->W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= e->H)
       return fail(e, TS_E_INVALID, "cost field: cell " + std::to_string(i) + " is outside the map");
   if (n == 0) return TS_OK;
-  CfScratch S;
+  Scratch S;   // what the call holds on the device besides the result
   int32_t* d_xy = nullptr; uint32_t* d_out = nullptr;
   if (S.get(&d_xy, (size_t)2 * n) != hipSuccess || S.get(&d_out, (size_t)n) != hipSuccess) {
     (void)hipGetLastError();
@@ -209,9 +195,7 @@ int ts_costfield_gather(ts_handle e, int32_t which, int32_t n, const int32_t* xy
   }
   HIPOK(hipMemcpyAsync(d_xy, xy, (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
   hipLaunchKernelGGL(k_cf_gather, dim3(nblk(n)), dim3(BLK), 0, e->stream, src, e->W, n, d_xy, d_out);
-  HIPOK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  return TS_OK;
+  return read_back(e, out, d_out, (size_t)n * sizeof(uint32_t));
 }
 
 int ts_costfield_bands(ts_handle e, int32_t n, const uint32_t* thresholds, uint64_t* counts) {
@@ -221,7 +205,7 @@ int ts_costfield_bands(ts_handle e, int32_t n, const uint32_t* thresholds, uint6
   for (int k = 1; k < n; k++)
     if (thresholds[k] < thresholds[k - 1]) return fail(e, TS_E_INVALID, "cost field: the thresholds must ascend");
   if (!e->cf.val) return fail(e, TS_E_STATE, "cost field: nothing has been computed");
-  CfScratch S;
+  Scratch S;   // what the call holds on the device besides the result
   uint32_t* d_thr = nullptr; unsigned long long* d_hist = nullptr;
   if (S.get(&d_thr, (size_t)n) != hipSuccess || S.get(&d_hist, (size_t)n) != hipSuccess) {
     (void)hipGetLastError();
@@ -232,8 +216,7 @@ int ts_costfield_bands(ts_handle e, int32_t n, const uint32_t* thresholds, uint6
   const int blocks = (int)std::min<long long>(nblk((long long)e->N), 1024);
   hipLaunchKernelGGL(k_cf_bands, dim3(blocks), dim3(BLK), 0, e->stream, e->cf.val, e->d.is_road, e->N, n, d_thr, d_hist);
   std::vector<unsigned long long> hist((size_t)n);
-  HIPOK(hipMemcpyAsync(hist.data(), d_hist, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
+  TRY(read_back(e, hist.data(), d_hist, (size_t)n * sizeof(unsigned long long)));
   unsigned long long sum = 0;
   for (int k = 0; k < n; k++) { sum += hist[k]; counts[k] = sum; }
   return TS_OK;

@@ -25,13 +25,11 @@ int dm_with_plane(E* e, int32_t bin, int32_t dir, F use) {
   const uint32_t* bin4 = nullptr;
   TRY(dm_bin(e, bin, dir, -1, &bin4));
   if (dir >= 0) return use(bin4 + (size_t)dir * (size_t)e->N);
+  Scratch tmp;
   uint32_t* sum = nullptr;
-  HIPOK(hipMalloc((void**)&sum, (size_t)e->N * sizeof(uint32_t)));
+  HIPOK(tmp.get(&sum, (size_t)e->N));
   hipLaunchKernelGGL(k_demand_sum4, dim3(nblk((long long)e->N)), dim3(BLK), 0, e->stream, bin4, e->N, sum);
-  const int rc = use(sum);
-  (void)hipStreamSynchronize(e->stream);
-  (void)hipFree(sum);
-  return rc;
+  return use(sum);
 }
 
 void dm_launch_walk(int team, int blocks, hipStream_t st, const DemandArgs& a) {
@@ -84,6 +82,7 @@ int ts_demand_compute(ts_handle e, const TsDemandQuery* q, TsDemandInfo* out) {
   const size_t words = dm_plane_words(e, q->n_bins);
   const bool in_place = D.planes && D.n_bins == q->n_bins;
   uint32_t* planes = in_place ? D.planes : nullptr;
+  Scratch tmp;
   uint8_t* dsel = nullptr;
   if (!D.tot && dalloc(e, &D.tot, (size_t)DM_NTOT) != hipSuccess) {
     (void)hipGetLastError();
@@ -95,7 +94,7 @@ int ts_demand_compute(ts_handle e, const TsDemandQuery* q, TsDemandInfo* out) {
     return fail(e, TS_E_DEVICE, "demand: no device memory for the planes (the previous result stays)");
   }
   const bool stage = q->select && !q->select_on_device && e->n_vehicles_total > 0;
-  if (stage && hipMalloc((void**)&dsel, (size_t)e->n_vehicles_total) != hipSuccess) {
+  if (stage && tmp.get(&dsel, (size_t)e->n_vehicles_total) != hipSuccess) {
     (void)hipGetLastError();
     if (!in_place) dfree(e, planes);
     return fail(e, TS_E_DEVICE, "demand: no device memory for the selection (the previous result stays)");
@@ -123,7 +122,6 @@ int ts_demand_compute(ts_handle e, const TsDemandQuery* q, TsDemandInfo* out) {
   }
   if (r == hipSuccess) r = hipMemcpyAsync(tot, D.tot, sizeof(tot), hipMemcpyDeviceToHost, st);
   if (r == hipSuccess) r = hipStreamSynchronize(st);
-  if (dsel) (void)hipFree(dsel);
   if (r != hipSuccess) {   // the device failed under an accepted call: planes computed in place hold nothing usable any more
     dfree(e, planes);
     if (in_place) { D.planes = nullptr; D.n_bins = D.bin_cells = D.open_tail = D.selected = 0; }
@@ -147,25 +145,13 @@ int ts_demand_info(ts_handle e, TsDemandInfo* out) {
 int ts_demand_download(ts_handle e, int32_t bin, int32_t dir, uint32_t* dst) {
   if (!e) return TS_E_INVALID;
   if (!dst) return fail(e, TS_E_INVALID, "demand: null pointer");
-  return dm_with_plane(e, bin, dir, [&](const uint32_t* src) {
-    HIPOK(hipMemcpyAsync(dst, src, (size_t)e->N * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPOK(hipStreamSynchronize(e->stream));
-    return (int)TS_OK;
-  });
+  return dm_with_plane(e, bin, dir, [&](const uint32_t* src) { return read_back(e, dst, src, (size_t)e->N * sizeof(uint32_t)); });
 }
 
 int ts_demand_pooled(ts_handle e, int32_t bin, int32_t dir, int32_t factor, uint64_t* dst) {
   if (!e) return TS_E_INVALID;
   if (!dst || factor < 1) return fail(e, TS_E_INVALID, "demand: null pointer or factor < 1");
-  const int f = std::min(factor, std::max(e->W, e->H));   // (a larger factor gives the same single block)
-  const int ow = (e->W + f - 1) / f, oh = (e->H + f - 1) / f;
-  if (oh > 65535) return fail(e, TS_E_INVALID, "demand: more than 65535 rows of pooled blocks (use a larger factor)");
-  const int threads = (long long)f * f <= 64 ? 64 : BLK;
-  return dm_with_plane(e, bin, dir, [&](const uint32_t* src) {
-    return obs_reduce(e, (size_t)ow * oh, dst, [&](unsigned long long* out) {
-      hipLaunchKernelGGL(k_obs_pool, dim3(ow, oh), dim3(threads), 0, e->stream, src, e->W, e->H, f, ow, out);
-    });
-  });
+  return pool_plane(e, "demand: ", factor, dst, [&](auto use) { return dm_with_plane(e, bin, dir, use); });
 }
 
 int ts_demand_groups(ts_handle e, int64_t* rows) {
@@ -175,9 +161,9 @@ int ts_demand_groups(ts_handle e, int64_t* rows) {
   const int items = e->d.G * e->dm.n_bins;
   if (items == 0) return TS_OK;
   const int per_block = BLK / 64;
-  return obs_reduce(e, (size_t)items * TS_DG_NFIELDS, rows, [&](unsigned long long* out) {
+  return launch_read<long long>(e, (size_t)items * TS_DG_NFIELDS, rows, [&](long long* out) {
     hipLaunchKernelGGL(k_demand_groups, dim3((items + per_block - 1) / per_block), dim3(BLK), 0, e->stream, e->d, e->dm.planes,
-                       e->dm.n_bins, (long long*)out);
+                       e->dm.n_bins, out);
   });
 }
 

@@ -66,12 +66,6 @@ int grow(E* e, T** p, C& cap, size_t need, size_t nc) {
   cap = (C)nc;
   return TS_OK;
 }
-// copy `bytes` from the device and wait for them (and for everything queued before)
-int read_back(E* e, void* dst, const void* src, size_t bytes) {
-  HIPOK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  return TS_OK;
-}
 
 // entries in the replanning work queue (RQueue, replan.h) as k_decide_main or the last pass left it
 inline int replan_pending(const ReplanCtl& r) { return r.class_n[0] + r.class_n[1] + r.class_n[2] + r.class_n[3]; }
@@ -1236,13 +1230,11 @@ int ts_create(const TsWorld* w, const TsParams* params, ts_handle* out) {
   if (hipStreamCreate(&e->stream) != hipSuccess) return bail(TS_E_DEVICE);
 #define A(ptr, n) if (dalloc(e, &ptr, (size_t)(n)) != hipSuccess) return bail(TS_E_DEVICE);
   A(d.occ, N) A(d.stop, N) A(d.rain, N) A(d.is_road, N) A(d.cell, N) A(d.gclaim_r, 1)
-  uint8_t* t_allowed = nullptr;   // static planes only needed to build the cell records
+  Scratch tmp;                    // static planes only needed to build the cell records: they go when this call returns
+  uint8_t* t_allowed = nullptr;
   int8_t *t_road_type = nullptr, *t_inter = nullptr;
-  if (hipMalloc((void**)&t_allowed, N) != hipSuccess || hipMalloc((void**)&t_road_type, N) != hipSuccess ||
-      hipMalloc((void**)&t_inter, N) != hipSuccess) {
-    (void)hipFree(t_allowed); (void)hipFree(t_road_type); (void)hipFree(t_inter);
+  if (tmp.get(&t_allowed, N) != hipSuccess || tmp.get(&t_road_type, N) != hipSuccess || tmp.get(&t_inter, N) != hipSuccess)
     return bail(TS_E_DEVICE);
-  }
   A(d.cnt, 1) A(e->d_total, 1) A(e->d_crc, 256) A(d.occ_snap, N) A(e->d_status, 4)
 #undef A
   hipStream_t st = e->stream;
@@ -1282,7 +1274,7 @@ int ts_create(const TsWorld* w, const TsParams* params, ts_handle* out) {
             if (x < W && y < H && is_node[(size_t)y * W + x]) node[(size_t)y * W + x] = n_nodes++;
           }
     d.n_nodes = n_nodes;
-    if (hipMalloc((void**)&t_node, N * 4) != hipSuccess) { (void)hipFree(t_allowed); (void)hipFree(t_road_type); (void)hipFree(t_inter); return bail(TS_E_DEVICE); }
+    if (tmp.get(&t_node, N) != hipSuccess) return bail(TS_E_DEVICE);
     ok &= hipMemcpy(t_node, node.data(), N * 4, hipMemcpyHostToDevice) == hipSuccess;
   }
   if (params->respect_awareness) {
@@ -1322,7 +1314,6 @@ int ts_create(const TsWorld* w, const TsParams* params, ts_handle* out) {
   ok &= hipHostMalloc((void**)&e->hcnt, sizeof(DevCnt)) == hipSuccess;
   ok &= hipHostMalloc((void**)&e->hm, sizeof(HostMirror)) == hipSuccess;
   ok &= hipStreamSynchronize(st) == hipSuccess;
-  (void)hipFree(t_allowed); (void)hipFree(t_road_type); (void)hipFree(t_inter); (void)hipFree(t_node);
   if (!ok) return bail(TS_E_DEVICE);
   ok = hipHostMalloc((void**)&e->h_words, MTPipe::TW_CAP * 4) == hipSuccess;
   ok &= dalloc(e, &d.words, (size_t)MTPipe::TW_CAP) == hipSuccess;
@@ -1695,10 +1686,9 @@ static int add_vehicles_core(ts_handle e, int n, std::vector<int32_t>& start, st
   int32_t *ds = nullptr, *dg = nullptr, *dp = nullptr, *dl = nullptr;
   uint32_t* dof = nullptr;
   uint8_t* dser = nullptr;
-  struct Temps { void* p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; ~Temps() { for (void* q : p) if (q) (void)hipFree(q); } } temps;
-  HIPOK(hipMalloc((void**)&ds, (size_t)n * 4)); temps.p[0] = ds; HIPOK(hipMalloc((void**)&dg, (size_t)n * 4)); temps.p[1] = dg;
-  HIPOK(hipMalloc((void**)&dp, (size_t)n * 4)); temps.p[2] = dp; HIPOK(hipMalloc((void**)&dl, (size_t)n * 4)); temps.p[3] = dl;
-  HIPOK(hipMalloc((void**)&dof, (size_t)n * 4)); temps.p[4] = dof; HIPOK(hipMalloc((void**)&dser, (size_t)n)); temps.p[5] = dser;
+  Scratch tmp;
+  HIPOK(tmp.get(&ds, (size_t)n)); HIPOK(tmp.get(&dg, (size_t)n)); HIPOK(tmp.get(&dp, (size_t)n));
+  HIPOK(tmp.get(&dl, (size_t)n)); HIPOK(tmp.get(&dof, (size_t)n)); HIPOK(tmp.get(&dser, (size_t)n));
   HIPOK(hipMemcpyAsync(ds, start.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
   HIPOK(hipMemcpyAsync(dg, goal.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
   HIPOK(hipMemcpyAsync(dp, pop.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
@@ -1931,14 +1921,11 @@ int ts_download_map(ts_handle e, int32_t which, int8_t* dst) {
   if (!e || !dst) return TS_E_INVALID;
   HIPOK(hipStreamSynchronize(e->stream));
   if (which == TS_MAP_STUCK) {   // lives only in the cell records
-    int8_t* tmp = nullptr;
-    HIPOK(hipMalloc((void**)&tmp, (size_t)e->N));
-    hipLaunchKernelGGL(k_cells_to_plane, dim3(nblk((long long)e->N)), dim3(BLK), 0, e->stream, e->d.cell, e->N, tmp);
-    hipError_t r = hipMemcpyAsync(dst, tmp, e->N, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(tmp);
-    HIPOK(r);
-    return TS_OK;
+    Scratch tmp;
+    int8_t* plane = nullptr;
+    HIPOK(tmp.get(&plane, (size_t)e->N));
+    hipLaunchKernelGGL(k_cells_to_plane, dim3(nblk((long long)e->N)), dim3(BLK), 0, e->stream, e->d.cell, e->N, plane);
+    return read_back(e, dst, plane, (size_t)e->N);
   }
   const int8_t* m = which == TS_MAP_OCCUPANCY ? e->d.occ : which == TS_MAP_STOP ? e->d.stop
                    : which == TS_MAP_RAIN ? e->d.rain : nullptr;
@@ -1951,14 +1938,12 @@ int ts_download_density(ts_handle e, float* dst) {
   if (!e || !dst) return TS_E_INVALID;
   float *t0 = nullptr, *t1 = nullptr, *dn = nullptr;
   size_t N = e->N;
-  HIPOK(hipMalloc((void**)&t0, N * 4)); HIPOK(hipMalloc((void**)&t1, N * 4)); HIPOK(hipMalloc((void**)&dn, N * 4));
+  Scratch tmp;
+  HIPOK(tmp.get(&t0, N)); HIPOK(tmp.get(&t1, N)); HIPOK(tmp.get(&dn, N));
   const int r = e->P.vehicle_awareness_range;
   hipLaunchKernelGGL(k_density_pass0, dim3(nblk(N)), dim3(BLK), 0, e->stream, e->d.occ, e->d.is_road, e->W, e->H, r, t0, t1);
   hipLaunchKernelGGL(k_density_pass1, dim3(nblk(N)), dim3(BLK), 0, e->stream, t0, t1, e->W, e->H, r, dn);
-  HIPOK(hipMemcpyAsync(dst, dn, N * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  (void)hipFree(t0); (void)hipFree(t1); (void)hipFree(dn);
-  return TS_OK;
+  return read_back(e, dst, dn, N * 4);
 }
 
 int ts_download_vehicles(ts_handle e, int32_t* rows, int32_t cap_rows) {
@@ -1966,12 +1951,11 @@ int ts_download_vehicles(ts_handle e, int32_t* rows, int32_t cap_rows) {
   int n = e->n_active;
   if (n > cap_rows) return TS_E_CAPACITY;
   if (n == 0) return 0;
+  Scratch tmp;
   int32_t* drows = nullptr;
-  HIPOK(hipMalloc((void**)&drows, (size_t)n * TS_V_NFIELDS * 4));
+  HIPOK(tmp.get(&drows, (size_t)n * TS_V_NFIELDS));
   hipLaunchKernelGGL(k_rows, dim3(nblk(n)), dim3(BLK), 0, e->stream, e->d, n, e->d_crc, drows);
-  HIPOK(hipMemcpyAsync(rows, drows, (size_t)n * TS_V_NFIELDS * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  (void)hipFree(drows);
+  TRY(read_back(e, rows, drows, (size_t)n * TS_V_NFIELDS * 4));
   return n;
 }
 
@@ -1981,12 +1965,11 @@ int ts_download_vehicle_meta(ts_handle e, int32_t* rows, int32_t cap_rows) {
   const int n = e->n_active;
   if (n > cap_rows) return TS_E_CAPACITY;
   if (n == 0) return 0;
+  Scratch tmp;
   int32_t* drows = nullptr;
-  HIPOK(hipMalloc((void**)&drows, (size_t)n * TS_M_NFIELDS * 4));
+  HIPOK(tmp.get(&drows, (size_t)n * TS_M_NFIELDS));
   hipLaunchKernelGGL(k_meta_rows, dim3(nblk(n)), dim3(BLK), 0, e->stream, e->d, n, drows);
-  HIPOK(hipMemcpyAsync(rows, drows, (size_t)n * TS_M_NFIELDS * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  (void)hipFree(drows);
+  TRY(read_back(e, rows, drows, (size_t)n * TS_M_NFIELDS * 4));
   if (!e->svc.empty()) {
     std::unordered_map<int, int> type_of;
     for (const auto& v : e->svc) type_of[v.vid] = v.type;
@@ -2020,12 +2003,11 @@ int ts_download_path(ts_handle e, int32_t active_pos, int32_t* xy, int32_t cap_c
   if (!xy) return n;
   if (n > cap_cells) return TS_E_CAPACITY;
   if (n == 0) return 0;
+  Scratch tmp;
   int32_t* dxy = nullptr;
-  HIPOK(hipMalloc((void**)&dxy, (size_t)n * 8));
+  HIPOK(tmp.get(&dxy, (size_t)n * 2));
   hipLaunchKernelGGL(k_path_cells, dim3(1), dim3(64), 0, e->stream, e->d, vid, dxy);
-  HIPOK(hipMemcpyAsync(xy, dxy, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  (void)hipFree(dxy);
+  TRY(read_back(e, xy, dxy, (size_t)n * 8));
   return n;
 }
 
@@ -2033,12 +2015,11 @@ int ts_download_groups(ts_handle e, int32_t* rows) {
   if (!e || !rows) return TS_E_INVALID;
   int G = e->d.G;
   if (G == 0) return 0;
+  Scratch tmp;
   int32_t* drows = nullptr;
-  HIPOK(hipMalloc((void**)&drows, (size_t)G * TS_G_NFIELDS * 4));
+  HIPOK(tmp.get(&drows, (size_t)G * TS_G_NFIELDS));
   hipLaunchKernelGGL(k_group_rows, dim3(nblk(G)), dim3(BLK), 0, e->stream, e->d, drows);
-  HIPOK(hipMemcpyAsync(rows, drows, (size_t)G * TS_G_NFIELDS * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  (void)hipFree(drows);
+  TRY(read_back(e, rows, drows, (size_t)G * TS_G_NFIELDS * 4));
   return G;
 }
 

@@ -29,20 +29,6 @@ int obs_plane(E* e, int32_t plane, const uint32_t** out) {
   return TS_OK;
 }
 
-// run `launch` with a device buffer of n_out 64-bit sums and copy them to dst
-template <typename F>
-int obs_reduce(E* e, size_t n_out, void* dst, F launch) {
-  unsigned long long* dout = nullptr;
-  HIPOK(hipMalloc((void**)&dout, std::max<size_t>(n_out, 1) * 8));
-  launch(dout);
-  hipError_t r = hipGetLastError();
-  if (r == hipSuccess) r = hipMemcpyAsync(dst, dout, n_out * 8, hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  (void)hipFree(dout);
-  HIPOK(r);
-  return TS_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -95,9 +81,7 @@ int ts_observe_download(ts_handle e, int32_t plane, uint32_t* dst) {
   if (!dst) return fail(e, TS_E_INVALID, "observe: null pointer");
   const uint32_t* src = nullptr;
   TRY(obs_plane(e, plane, &src));
-  HIPOK(hipMemcpyAsync(dst, src, (size_t)e->N * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  return TS_OK;
+  return read_back(e, dst, src, (size_t)e->N * sizeof(uint32_t));
 }
 
 int ts_observe_pooled(ts_handle e, int32_t plane, int32_t factor, uint64_t* dst) {
@@ -105,13 +89,7 @@ int ts_observe_pooled(ts_handle e, int32_t plane, int32_t factor, uint64_t* dst)
   if (!dst || factor < 1) return fail(e, TS_E_INVALID, "observe: null pointer or factor < 1");
   const uint32_t* src = nullptr;
   TRY(obs_plane(e, plane, &src));
-  const int f = std::min(factor, std::max(e->W, e->H));   // (a larger factor gives the same single block; keeps x0 + f in range)
-  const int ow = (e->W + f - 1) / f, oh = (e->H + f - 1) / f;
-  if (oh > 65535) return fail(e, TS_E_INVALID, "observe: more than 65535 rows of pooled blocks (use a larger factor)");
-  const int threads = (long long)f * f <= 64 ? 64 : BLK;
-  return obs_reduce(e, (size_t)ow * oh, dst, [&](unsigned long long* out) {
-    hipLaunchKernelGGL(k_obs_pool, dim3(ow, oh), dim3(threads), 0, e->stream, src, e->W, e->H, f, ow, out);
-  });
+  return pool_plane(e, "observe: ", factor, dst, [&](auto use) { return use(src); });
 }
 
 int ts_observe_regions(ts_handle e, int32_t plane, int32_t n, const int32_t* rects, uint64_t* sums) {
@@ -120,18 +98,13 @@ int ts_observe_regions(ts_handle e, int32_t plane, int32_t n, const int32_t* rec
   const uint32_t* src = nullptr;
   TRY(obs_plane(e, plane, &src));
   if (n == 0) return TS_OK;
-  int32_t* drects = nullptr;
-  HIPOK(hipMalloc((void**)&drects, (size_t)n * 16));
-  hipError_t r = hipMemcpyAsync(drects, rects, (size_t)n * 16, hipMemcpyHostToDevice, e->stream);
-  int rc = TS_OK;
-  if (r == hipSuccess)
-    rc = obs_reduce(e, (size_t)n, sums, [&](unsigned long long* out) {
-      hipLaunchKernelGGL(k_obs_regions, dim3(n), dim3(BLK), 0, e->stream, src, e->W, e->H, drects, out);
-    });
-  (void)hipStreamSynchronize(e->stream);
-  (void)hipFree(drects);
-  HIPOK(r);
-  return rc;
+  Scratch tmp;
+  int32_t* drects = nullptr;   // four per rectangle
+  HIPOK(tmp.get(&drects, (size_t)n * 4));
+  HIPOK(hipMemcpyAsync(drects, rects, (size_t)n * 16, hipMemcpyHostToDevice, e->stream));
+  return launch_read<unsigned long long>(e, (size_t)n, sums, [&](unsigned long long* out) {
+    hipLaunchKernelGGL(k_obs_regions, dim3(n), dim3(BLK), 0, e->stream, src, e->W, e->H, drects, out);
+  });
 }
 
 int ts_observe_groups(ts_handle e, int64_t* rows) {
@@ -143,8 +116,8 @@ int ts_observe_groups(ts_handle e, int64_t* rows) {
   const int G = e->d.G;
   if (G == 0) return TS_OK;
   const int per_block = BLK / 64;
-  return obs_reduce(e, (size_t)G * TS_OG_NFIELDS, rows, [&](unsigned long long* out) {
-    hipLaunchKernelGGL(k_obs_groups, dim3((G + per_block - 1) / per_block), dim3(BLK), 0, e->stream, e->d, (long long*)out);
+  return launch_read<long long>(e, (size_t)G * TS_OG_NFIELDS, rows, [&](long long* out) {
+    hipLaunchKernelGGL(k_obs_groups, dim3((G + per_block - 1) / per_block), dim3(BLK), 0, e->stream, e->d, out);
   });
 }
 

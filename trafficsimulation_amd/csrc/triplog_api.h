@@ -38,9 +38,7 @@ int tl_zero_counters(E* e) {
 // the log's device counters, after sealing what is staged
 int tl_counters(E* e, TripLog* out) {
   TRY(tl_seal(e));
-  HIPOK(hipMemcpyAsync(out, e->d.tlog, sizeof(TripLog), hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  return TS_OK;
+  return read_back(e, out, e->d.tlog, sizeof(TripLog));
 }
 
 }  // namespace
@@ -151,10 +149,7 @@ int64_t ts_triplog_read(ts_handle e, int64_t first, int64_t n, TsTripRecord* out
   TripLog c;
   TRY(tl_counters(e, &c));
   const int64_t k = std::max<int64_t>(0, std::min<int64_t>(n, c.count - first));
-  if (k > 0) {
-    HIPOK(hipMemcpyAsync(out, e->tl.rec + first, (size_t)k * sizeof(TsTripRecord), hipMemcpyDeviceToHost, e->stream));
-    HIPOK(hipStreamSynchronize(e->stream));
-  }
+  if (k > 0) TRY(read_back(e, out, e->tl.rec + first, (size_t)k * sizeof(TsTripRecord)));
   return k;
 }
 
@@ -199,23 +194,19 @@ int ts_triplog_od(ts_handle e, uint32_t reason_mask, uint64_t* count, double* du
   TripLog c;
   TRY(tl_counters(e, &c));
   const size_t nz2 = (size_t)e->tl.n_zones * e->tl.n_zones;
+  Scratch tmp;
   unsigned long long* buf = nullptr;   // count, duration, distance, then the unzoned counter
-  HIPOK(hipMalloc((void**)&buf, (3 * nz2 + 1) * 8));
-  hipError_t r = hipMemsetAsync(buf, 0, (3 * nz2 + 1) * 8, e->stream);   // (all-zero bits are 0.0 too)
-  if (r == hipSuccess && c.count > 0) {
+  HIPOK(tmp.get(&buf, 3 * nz2 + 1));
+  HIPOK(hipMemsetAsync(buf, 0, (3 * nz2 + 1) * 8, e->stream));   // (all-zero bits are 0.0 too)
+  if (c.count > 0) {
     hipLaunchKernelGGL(k_triplog_od, dim3(nblk(c.count)), dim3(BLK), 0, e->stream, e->d, c.count, reason_mask, count ? buf : nullptr,
                        duration ? (double*)(buf + nz2) : nullptr, distance ? buf + 2 * nz2 : nullptr, buf + 3 * nz2);
-    r = hipGetLastError();
+    HIPOK(hipGetLastError());
   }
-  if (r == hipSuccess && count) r = hipMemcpyAsync(count, buf, nz2 * 8, hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess && duration) r = hipMemcpyAsync(duration, buf + nz2, nz2 * 8, hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess && distance) r = hipMemcpyAsync(distance, buf + 2 * nz2, nz2 * 8, hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipMemcpyAsync(unzoned, buf + 3 * nz2, 8, hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  else (void)hipStreamSynchronize(e->stream);
-  (void)hipFree(buf);
-  HIPOK(r);
-  return TS_OK;
+  if (count) HIPOK(hipMemcpyAsync(count, buf, nz2 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (duration) HIPOK(hipMemcpyAsync(duration, buf + nz2, nz2 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (distance) HIPOK(hipMemcpyAsync(distance, buf + 2 * nz2, nz2 * 8, hipMemcpyDeviceToHost, e->stream));
+  return read_back(e, unzoned, buf + 3 * nz2, 8);
 }
 
 }  // extern "C"
