@@ -68,6 +68,8 @@ if __name__ == "__main__":
     ap.add_argument("--demand", metavar="OUT.npy", default=None, help="write the planned load at the end of the run (remaining routes per cell, (H, W) uint32) to this file")
     ap.add_argument("--isochrone", nargs=2, metavar=("X,Y", "OUT.npy"), default=None,
                     help="write the travel cost from every cell to cell (X, Y) at the end of the run ((H, W) uint32, 0xFFFFFFFF: unreachable) to OUT.npy")
+    ap.add_argument("--evacuate", metavar="OUT.npy", default=None,
+                    help="write the load of every live vehicle's route to its nearest highway exit at the end of the run ((H, W) uint32) to this file")
     ap.add_argument("--frames", metavar="DIR", default=None, help="write a frame of the whole city into DIR every --frame-every ticks (PNG with PIL, else PPM)")
     ap.add_argument("--frame-every", type=int, default=10)
     ap.add_argument("--zoom", type=int, default=1, help="pixels per cell of the frames (1..64)")
@@ -94,6 +96,23 @@ if __name__ == "__main__":
         np.save(a.isochrone[1], m.engine.costfield.plane("cost"))
         print(f"cost to ({x}, {y}): {iso['reached']} cells reached in {iso['rounds']} rounds, farthest at {iso['max_value']}; road cells within "
               + ", ".join(f"{t}: {int(n)}" for t, n in zip(thr, iso["road_cells"])))
+    if a.evacuate:
+        import numpy as np
+        # on the device (include/trafficsim_cfroute.h): the catchments of the exits, a route per vehicle, their summed load
+        vehicles = list(m.active_vehicle_agents)
+        zone = m.catchments("highway_exits")
+        if vehicles:
+            ev = m.assigned_load(m.highway_exits, vehicles)
+            routes = m.routes_along(m.highway_exits, vehicles)
+            np.save(a.evacuate, ev["load"])
+            y, x = divmod(int(ev["load"].argmax()), m.width)
+            by_exit = np.bincount(routes["owner"][routes["owner"] >= 0], minlength=zone["n"])
+            print(f"evacuation: {ev['routes']} of {len(vehicles)} vehicles reach one of {zone['n']} exits in {ev['steps']} steps "
+                  f"(longest route {routes['trace_longest']}); busiest cell ({x}, {y}) with {int(ev['load'][y, x])} entries; "
+                  f"busiest exit {int(by_exit.argmax())} takes {int(by_exit.max())}")
+        else:
+            np.save(a.evacuate, np.zeros((m.height, m.width), dtype=np.uint32))
+            print("evacuation: no live vehicles")
     if a.trips:
         import numpy as np
         rec, info = m.trips(), m.engine.triplog_info()

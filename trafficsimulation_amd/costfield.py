@@ -69,6 +69,12 @@ class CostField:
     def available(self) -> bool:
         return self.api.prefix == "ts_" and hasattr(self.api.lib, "ts_costfield_compute")
 
+    @property
+    def routes(self):
+        """The routes along this engine's cost field, as a cfroute.RouteField (a view like this one)."""
+        from .cfroute import RouteField
+        return RouteField(self.api)
+
     @staticmethod
     def _info(info: TsCostFieldInfo) -> dict:
         d = capi._info_dict(info)
@@ -83,7 +89,10 @@ class CostField:
         penalties (else they cannot be entered); `ignore_flow`: steps against the flow at the contraflow penalty;
         `free_flow`: occupancy and lights are not looked at; `max_cost`: values above it are unreachable (0: no limit).
         Returns info()."""
-        fn = self._ext("costfield_compute")
+        return self._compute(self._ext("costfield_compute"), seeds, seed_cost, mode, soft, ignore_flow, free_flow, max_cost)
+
+    def _compute(self, fn, seeds, seed_cost, mode, soft, ignore_flow, free_flow, max_cost) -> dict:
+        """compute() through the entry `fn` (cfroute.RouteField.compute: the same query, and a hop plane)."""
         if mode not in MODES:
             raise ValueError(f"unknown mode {mode!r} ('from' or 'to')")
         xy = capi._i32(seeds).reshape(-1, 2)

@@ -38,11 +38,16 @@ void cf_launch_finish(const CostFieldArgs& a, uint32_t* val, int32_t* own, unsig
     else { if (to) fn<1, true>(__VA_ARGS__); else fn<1, false>(__VA_ARGS__); }           \
   } while (0)
 
-}  // namespace
+// cfroute_api.h, for a compute that is to leave a hop plane (ts_cfroute_compute): room for the new plane beside the one held,
+// with the cell words that stay with it; the plane from the settled labels; the new plane in place of the old.  And for
+// whatever ends a field: the hop plane goes with it.
+hipError_t cfr_stage(E* e, const TsCostFieldQuery* q, uint32_t** cw);
+hipError_t cfr_hops(E* e, const CostFieldArgs& a, int NH, bool to, const int32_t* d_xy, const int32_t* d_cost);
+void cfr_publish(E* e, const TsCostFieldQuery* q, const CostFieldArgs& a, int NH);
+void cfr_drop(E* e);
 
-extern "C" {
-
-int ts_costfield_compute(ts_handle e, const TsCostFieldQuery* q, TsCostFieldInfo* out) {
+// ts_costfield_compute, and with `hops` ts_cfroute_compute: the same field, and the hop plane while the labels exist
+int cf_compute(E* e, const TsCostFieldQuery* q, TsCostFieldInfo* out, bool hops) {
   if (!e) return TS_E_INVALID;
   if (!q || !q->seed_xy) return fail(e, TS_E_INVALID, "cost field: null pointer");
   if ((q->mode != TS_CF_FROM && q->mode != TS_CF_TO) || (q->soft_obstacles | 1) != 1 || (q->ignore_flow | 1) != 1 || (q->free_flow | 1) != 1 ||
@@ -77,7 +82,7 @@ int ts_costfield_compute(ts_handle e, const TsCostFieldQuery* q, TsCostFieldInfo
   uint32_t* ctl = nullptr;           // [0, 2) list lengths by parity, [2, 2 + 2 n_tiles) flags by parity
   int32_t *lists = nullptr, *d_xy = nullptr, *d_cost = nullptr;
   unsigned long long* tot = nullptr;
-  hipError_t r = S.get(&cw, N);
+  hipError_t r = hops ? cfr_stage(e, q, &cw) : S.get(&cw, N);
   if (r == hipSuccess) r = S.get(&lab, (size_t)NH * N);
   if (r == hipSuccess && NH == 4) r = S.get(&seed, N);
   if (r == hipSuccess) r = S.get(&ctl, 2 + 2 * n_tiles);
@@ -143,6 +148,7 @@ int ts_costfield_compute(ts_handle e, const TsCostFieldQuery* q, TsCostFieldInfo
     if (r == hipSuccess) r = hipStreamSynchronize(st);
     if (r == hipSuccess && n_cur > n_tiles) r = hipErrorUnknown;   // (a list cannot outgrow the tiles: the flags keep entries unique)
   }
+  if (r == hipSuccess && hops) r = cfr_hops(e, a, NH, to, d_xy, d_cost);
   unsigned long long h_tot[2] = {0, 0};
   if (r == hipSuccess) {
     CF_DISPATCH(cf_launch_finish, NH, to, a, D.spare_val, D.spare_own, tot, st);
@@ -153,6 +159,7 @@ int ts_costfield_compute(ts_handle e, const TsCostFieldQuery* q, TsCostFieldInfo
   if (r != hipSuccess) return fail(e, TS_E_DEVICE, std::string("cost field: ") + hipGetErrorString(r));
   std::swap(D.val, D.spare_val);
   std::swap(D.own, D.spare_own);
+  if (hops) cfr_publish(e, q, a, NH); else cfr_drop(e);
   TsCostFieldInfo& I = D.info;
   memset(&I, 0, sizeof(I));
   I.mode = q->mode; I.soft_obstacles = q->soft_obstacles; I.ignore_flow = q->ignore_flow; I.free_flow = q->free_flow;
@@ -163,6 +170,12 @@ int ts_costfield_compute(ts_handle e, const TsCostFieldQuery* q, TsCostFieldInfo
   if (out) cf_fill_info(e, out);
   return TS_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int ts_costfield_compute(ts_handle e, const TsCostFieldQuery* q, TsCostFieldInfo* out) { return cf_compute(e, q, out, false); }
 
 int ts_costfield_info(ts_handle e, TsCostFieldInfo* out) {
   if (!e || !out) return TS_E_INVALID;
@@ -236,6 +249,7 @@ int ts_costfield_release(ts_handle e) {
   if (!e) return TS_E_INVALID;
   HIPOK(hipStreamSynchronize(e->stream));
   auto& D = e->cf;
+  cfr_drop(e);
   dfree(e, D.val); dfree(e, D.own); dfree(e, D.spare_val); dfree(e, D.spare_own);
   D.val = D.spare_val = nullptr; D.own = D.spare_own = nullptr;
   memset(&D.info, 0, sizeof(D.info));

@@ -49,6 +49,7 @@
 #include "lights_proto.h"
 #include "render.h"
 #include "costfield.h"
+#include "cfroute.h"
 #include "host_state.h"
 #include "host_shuffle.h"
 #include "host_agents.h"
@@ -2181,3 +2182,4 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
 #include "render_api.h"
 #include "demand_api.h"
 #include "costfield_api.h"
+#include "cfroute_api.h"

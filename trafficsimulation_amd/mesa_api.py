@@ -1141,6 +1141,50 @@ class CityModel:
         thr = np.asarray(thresholds, dtype=np.uint32).reshape(-1)
         return dict(info, thresholds=thr, road_cells=cf.bands(thr))
 
+    # ---- routes along a cost field (include/trafficsim_cfroute.h) ---------------------------------------
+    def _route_starts(self, starts):
+        """((n, 2) int32 cells, int8 headings) of `starts`: (x, y) pairs and cells have no heading, a vehicle agent stands
+        where it is now and is held with the heading it drives with."""
+        self._flush_host_writes()
+        xy = self._seed_cells(starts)
+        head = np.full(len(xy), -1, dtype=np.int8)
+        for i, s in enumerate(starts):
+            if hasattr(s, "_spawn_idx"):
+                d = s._field("direction")
+                head[i] = d if d is not None and 0 <= d <= 3 else -1
+        return xy, head
+
+    def routes_along(self, seeds, starts, mode: str = "to", seed_cost=None, **modes) -> dict:
+        """Shortest routes read off a cost field, all in one launch: from every start to its nearest seed (`mode="to"`; a
+        vehicle agent's route honours the heading it has now) or from the nearest seed to every start (`"from"`), under the
+        pathfinder's cost rule and the traffic as it is.  `seeds`, `starts`: (x, y) pairs, cells or vehicle agents; `modes` as
+        for cost_field().  Returns {"routes": a list of (k, 2) int32 arrays of (x, y) cells, each without its first cell as
+        A* paths are, "dirs": the same routes as direction bytes with their CSR offsets "off", "cost": uint32 per route
+        (0xFFFFFFFF: no route), "owner": int32 index into "seeds" (-1: none), "seeds", "starts", "headings"} and the fields of
+        `engine.costfield.routes.info()`.  The cost field of the seeds stays the engine's result."""
+        seed_xy = self._seed_cells(seeds)
+        xy, head = self._route_starts(starts)
+        r = self.engine.costfield.routes
+        r.compute(seed_xy, seed_cost, mode=mode, **modes)
+        r.trace(xy, head if mode == "to" else None)
+        off, dirs, cost, owner = r.routes()
+        _, cells = r.cells()
+        return dict(r.info(), routes=[cells[off[i]:off[i + 1]] for i in range(len(xy))], off=off, dirs=dirs, cost=cost, owner=owner,
+                    seeds=seed_xy, starts=xy, headings=head)
+
+    def assigned_load(self, seeds, starts, weights=None, mode: str = "to", seed_cost=None, **modes) -> dict:
+        """All-or-nothing assignment: every start sends `weights` units (default 1) down its route to the nearest seed, summed
+        per cell on the device without materialising the routes.  Returns {"load": (H, W) uint32, "by_direction": (4, H, W)
+        by the direction N E S W of the step into the cell - field for field what planned_load() and the ENTER planes of
+        observe() hold -, "routes", "unreached", "steps"} and the fields of `engine.costfield.routes.info()`."""
+        seed_xy = self._seed_cells(seeds)
+        xy, head = self._route_starts(starts)
+        r = self.engine.costfield.routes
+        r.compute(seed_xy, seed_cost, mode=mode, **modes)
+        load = r.load(xy, head if mode == "to" else None, weights)
+        return dict(r.info(), **{k: load[k] for k in ("routes", "unreached", "steps")}, load=r.load_plane(),
+                    by_direction=np.stack([r.load_plane(d) for d in range(4)]), seeds=seed_xy, starts=xy)
+
     # ---- getters used by the UI (city_model.py:1965-2149) ------------------------------------------
     # ---- device renderer (include/trafficsim_render.h) ---------------------------------------------------
     def _render_defaults(self):
