@@ -242,8 +242,7 @@ int ck_count_paths(E* e, int nv, uint64_t* words) {
   hipLaunchKernelGGL(k_ckpt_count_paths, dim3(nb), dim3(BLK), 0, e->stream, e->d, nv, e->ck_bsum);
   hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, e->stream, e->ck_bsum, nb, e->ck_bsum + nb);
   int total = 0;
-  HIPOK(hipMemcpyAsync(&total, e->ck_bsum + nb, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
+  TRY(read_back(e, &total, e->ck_bsum + nb, sizeof(int)));
   if (total < 0) return fail(e, TS_E_CAPACITY, "checkpoint: more than 2^31 live path words");
   *words = (uint64_t)total;
   return TS_OK;

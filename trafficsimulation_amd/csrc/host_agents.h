@@ -10,8 +10,7 @@ int host_agent_register(E* e, int slot) {
   const int hid = e->n_host_agents;
   if (hid + 1 > e->cap_hslot) {
     int nc = std::max(64, e->cap_hslot * 2);
-    int rc = regrow(e, &e->d.hslot, (size_t)e->n_host_agents, (size_t)nc);
-    if (rc) return rc;
+    TRY(regrow(e, &e->d.hslot, (size_t)e->n_host_agents, (size_t)nc));
     e->cap_hslot = nc;
   }
   HIPOK(hipMemcpy(e->d.hslot + hid, &slot, 4, hipMemcpyHostToDevice));
@@ -69,11 +68,9 @@ int rain_add_random(E* e) {
   c.radius = r.randint(e->P.rain_radius_min, e->P.rain_radius_max);
   // schedule.add(rain): a new entry at the end of the schedule (it does not step in the tick that created it)
   if ((long long)e->n_sched + 1 >= (long long)RANK_MASK) return fail(e, TS_E_CAPACITY, "schedule exceeds 2^24 agents");
-  int rc = ensure_vehicle_capacity(e, e->cap_v, e->n_sched + 1);
-  if (rc) return rc;
+  TRY(ensure_vehicle_capacity(e, e->cap_v, e->n_sched + 1));
   const int hid = e->n_host_agents;
-  rc = host_agent_register(e, e->n_sched);
-  if (rc) return rc;
+  TRY(host_agent_register(e, e->n_sched));
   const int8_t kind = K_RAIN;
   HIPOK(hipMemcpy(e->d.sched_kind + e->n_sched, &kind, 1, hipMemcpyHostToDevice));
   HIPOK(hipMemcpy(e->d.sched_ref + e->n_sched, &hid, 4, hipMemcpyHostToDevice));
@@ -91,8 +88,7 @@ int rain_manager_step(E* e, RainDiscs& discs) {
   if (e->rain_cooldown_left > 0) e->rain_cooldown_left--;
   if ((int)e->rains.size() < e->P.rain_occurrences_max && e->rain_cooldown_left == 0 &&
       e->rng_global.random() < e->P.rain_spawn_chance) {
-    int rc = rain_add_random(e);
-    if (rc) return rc;
+    TRY(rain_add_random(e));
   }
   discs.n = 0;
   for (int hid : e->rains) {
@@ -325,8 +321,7 @@ int spawn_service_at(E* e, int origin, int kind, int id) {
     e->d.arr_cap = 1 << 16;
     HIPOK(dalloc(e, &e->d.arr, (size_t)e->d.arr_cap * 3));
   }
-  int rc = add_vehicle_planned(e, origin, target, TS_POP_THROUGH);
-  if (rc) return rc;
+  TRY(add_vehicle_planned(e, origin, target, TS_POP_THROUGH));
   const int vid = e->n_vehicles_total - 1;
   hipLaunchKernelGGL(k_flags_or, dim3(1), dim3(64), 0, e->stream, e->d, vid, (int)(VF_SVC | VF_KEEP | (phase == 0 ? VF_TOBLOCK : 0)));
   ts_engine::SvcVeh v;
@@ -361,8 +356,7 @@ int update_cached_stats(E* e) {
     hipLaunchKernelGGL(k_live_stats, dim3(nblk(e->n_active)), dim3(BLK), 0, e->stream, d, e->n_active, e->C.elapsed, e->d_live_stats);
   double raw[8];
   HIPOK(hipMemcpyAsync(raw, e->d_live_stats, sizeof(raw), hipMemcpyDeviceToHost, e->stream));
-  int rc = sync_counters(e);
-  if (rc) return rc;
+  TRY(sync_counters(e));
   TsCachedStats& c = G.cs;
   memset(&c, 0, sizeof(c));
   c.valid = 1;
@@ -409,8 +403,7 @@ int generator_step(E* e) {
   const double total_secs = G.T.start_offset_seconds + e->C.elapsed;
   const int new_day = (int)std::floor(total_secs / 86400.0);
   if (new_day > G.current_day) {
-    int rc = sync_counters(e);      // (the completed counts live on the device)
-    if (rc) return rc;
+    TRY(sync_counters(e));      // (the completed counts live on the device)
     const long long done = e->C.count_completed_internal + e->C.count_completed_through;
     G.daily_difference_history.push_back((done - G.completed_at_day_start) - (e->C.created_internal + e->C.created_through));   // finished - spawned (165-167)
     G.completed_at_day_start = done;
@@ -424,19 +417,17 @@ int generator_step(E* e) {
   G.pending.swap(keep);
   for (const auto& t : spawn) {
     if (t.kind == TS_TRIP_SERVICE_FOOD || t.kind == TS_TRIP_SERVICE_WASTE) {
-      int rc = spawn_service(e, t);
-      if (rc) return rc;
+      TRY(spawn_service(e, t));
       continue;
     }
     if (t.kind == TS_POP_INTERNAL) e->C.created_internal++; else e->C.created_through++;
     (void)e->rng_global.randint(0, 9999);  // the id suffix of "V_{depart:06d}_{randint(0, 9999):04d}"
     if ((long long)e->n_sched + 1 >= (long long)RANK_MASK) return fail(e, TS_E_CAPACITY, "schedule exceeds 2^24 agents");
-    int rc = add_vehicle_planned(e, t.origin, t.dest, t.kind);
-    if (rc) return rc;
+    TRY(add_vehicle_planned(e, t.origin, t.dest, t.kind));
   }
   // _update_cached_stats every STATISTICS_UPDATE_INTERVAL ticks, inside this step (188-194)
   const int interval = G.T.statistics_update_interval > 0 ? G.T.statistics_update_interval : 20;
-  if (++G.ticks_since_stats >= interval) { int rc = update_cached_stats(e); if (rc) return rc; G.ticks_since_stats = 0; }
+  if (++G.ticks_since_stats >= interval) { TRY(update_cached_stats(e)); G.ticks_since_stats = 0; }
   return TS_OK;
 }
 

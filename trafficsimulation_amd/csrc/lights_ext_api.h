@@ -64,8 +64,7 @@ int le_bytes(E* e, const int8_t* v, int on_device, int lo, const char* what, con
   HIPOK(hipMemsetAsync(e->le.x.bad, 0, sizeof(int), e->stream));
   hipLaunchKernelGGL(k_le_check, dim3(le_grid(e, e->le.gblock)), dim3(e->le.gblock), 0, e->stream, v, G, lo, e->le.x.bad);
   HIPOK(hipGetLastError());
-  HIPOK(hipMemcpyAsync(&bad, e->le.x.bad, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
+  TRY(read_back(e, &bad, e->le.x.bad, sizeof(int)));
   if (bad) return fail(e, TS_E_INVALID, std::string("lights_ext: ") + what + " out of range");
   *dev = v;
   return TS_OK;

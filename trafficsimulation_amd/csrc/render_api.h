@@ -183,9 +183,7 @@ int ts_render(ts_handle e, const TsRenderView* v, uint8_t* dst) {
   if (!e) return TS_E_INVALID;
   if (!v || !dst) return fail(e, TS_E_INVALID, "render: null pointer");
   TRY(rn_frame(e, v));
-  HIPOK(hipMemcpyAsync(dst, e->rn.out, (size_t)e->rn.last_w * e->rn.last_h * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPOK(hipStreamSynchronize(e->stream));
-  return TS_OK;
+  return read_back(e, dst, e->rn.out, (size_t)e->rn.last_w * e->rn.last_h * 4);
 }
 
 int ts_render_info(ts_handle e, TsRenderInfo* out) {
