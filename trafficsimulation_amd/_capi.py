@@ -437,7 +437,8 @@ ENTRIES = {
     }),
     # the hooks are two groups because their refusals name two different things
     "debug_batch": ("batched pathfinder", {"debug_batch_info": [_H, _P, _I32]}),
-    "debug_quad": ("quad searcher", {"debug_quad_stats": [_H, _P, _I32]}),
+    "debug_quad": ("quad searcher", {"debug_quad_stats": [_H, _P, _I32], "debug_quad_walks": [_H, _P, _I32],
+                                     "debug_arena_info": [_H, _P, _I32]}),      # (the arena the quads' tables share with k_replan's)
 }
 # the entries that do not return an int status
 RESTYPES = {"default_params": None, "last_error": C.c_char_p, "profile_name": C.c_char_p, "triplog_read": C.c_int64}
@@ -909,6 +910,27 @@ class CApi:
         n = self._chk(fn(self.h, out.ctypes.data, len(out)))
         assert n == len(out), f"ts_debug_quad_stats reports {n} counters, this wrapper knows {len(out)}"
         return dict(zip(self.QUAD_STATS, (int(v) for v in out)))
+
+    ARENA_INFO = ("to_quads", "to_waves", "clears", "big_dist_flag", "big_dist_seen", "arena_shared", "arena_quad")
+    QUAD_WALKS = ("walks", "cells", "round_trips", "odd", "len1", "len2")
+
+    def _debug_words(self, entry, names) -> dict:
+        fn = self._ext(entry)
+        out = np.zeros(len(names), dtype=np.int64)
+        n = self._chk(fn(self.h, out.ctypes.data, len(out)))
+        assert n == len(out), f"ts_{entry} reports {n} words, this wrapper knows {len(out)}"
+        return dict(zip(names, (int(v) for v in out)))
+
+    def debug_arena_info(self) -> dict:
+        """Debugging hook (ts_debug_arena_info, not part of include/trafficsim.h): the table arena k_replan and the quads share -
+        hand-overs each way, clears run, the big-dist flag on the device and the hand-overs that found it set, whether the
+        quads' tables alias the arena and whether they hold it now."""
+        return self._debug_words("debug_arena_info", self.ARENA_INFO)
+
+    def debug_quad_walks(self) -> dict:
+        """Debugging hook (ts_debug_quad_walks, not part of include/trafficsim.h): the quads' walks back along found paths - walks,
+        cells written, HBM round trips, walks of odd length (ended on the first cell of a pair), of one cell, of two."""
+        return self._debug_words("debug_quad_walks", self.QUAD_WALKS)
 
     # ---- checkpoints (include/trafficsim_checkpoint.h) ----------------------------------------------
     def checkpoint_size(self) -> int:

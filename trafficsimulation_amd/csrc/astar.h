@@ -26,6 +26,7 @@
 #pragma once
 #include <type_traits>
 #include "dev.h"
+#include "arena_epochs.h"
 
 namespace {
 
@@ -48,11 +49,13 @@ constexpr int LDS_HEAP = TS_LDS_HEAP;
 #define TS_REPLAN_OCC __attribute__((amdgpu_waves_per_eu(TS_REPLAN_WAVES, 8)))
 struct __attribute__((aligned(8))) HQ { int32_t f, i; };             // heap entry: f_arr, i_arr (g_arr / s_arr: see above)
 struct __attribute__((aligned(8))) TEnt { int32_t dist; uint32_t meta; };   // meta = stamp << 14 | steps << 2 | came-from direction
-// (TS_DEBUG_STAMP_MAX: a test build that wraps the searcher tables' epochs every few hundred searches instead of every 262 143)
+// The stamps run over W_EPOCH_LO + 1 .. W_EPOCH_LO + T_STAMP_MAX (arena_epochs.h: a range the quads' records, which can lie in the
+// same memory, never look live in); T_STAMP_MAX = searches between two wraps.
+// (TS_DEBUG_STAMP_MAX: a test build that wraps the searcher tables' epochs every few hundred searches instead of every 65 535)
 #ifndef TS_DEBUG_STAMP_MAX
-#define TS_DEBUG_STAMP_MAX ((1u << 18) - 1)
+#define TS_DEBUG_STAMP_MAX 0xFFFFu
 #endif
-constexpr uint32_t T_STAMP_SHIFT = 14, T_STEPS_MASK = 0xFFF, T_STAMP_MAX = TS_DEBUG_STAMP_MAX;
+constexpr uint32_t T_STAMP_SHIFT = W_STAMP_SHIFT, T_STEPS_MASK = 0xFFF, T_STAMP_MAX = TS_DEBUG_STAMP_MAX;
 constexpr int A_STEPS_MAX = (int)T_STEPS_MASK - 1;   // largest binding step limit a search can carry (a limit >= N never binds)
 
 // (slot LDS_HEAP of both arrays is a spare no search reads: a lane-predicated store sends its idle lanes there instead of
@@ -76,6 +79,8 @@ struct AScratch {
   int heap_cap;
   TEnt* tab;     // one record per search node (Dev::n_nodes), nodes numbered in tiled order, and one spare behind them
   uint32_t epoch;
+  uint32_t big_thr;    // a dist from here on could pass for a quad's live record (ASlots::big_thr) ...
+  uint32_t* big_flag;  // ... and a search that stored one says so here (ASlots::big_flag)
   int32_t *A, *P, *T, *PO, *PD;  // cap cells each: A* result, current new path, splice target, staged pre-paths
   int32_t *BYP, *OV, *DV;        // MAXB cells each: bypass result, staged overtake / detour paths
   int cap;        // capacity of the cell buffers
@@ -98,6 +103,10 @@ struct ASlots {
   int8_t* gd;
   int32_t* cells;        // per slot: 5 * cap + 3 * MAXB
   uint32_t* slot_epoch;
+  // the one way a record of these tables could pass for a quad's live one once the arena changes hands without a clear: a dist
+  // word of big_thr (2^24; TS_DEBUG_ARENA_BIGDIST) or more.  A search that stores one sets *big_flag, and the next hand-over clears.
+  uint32_t big_thr;
+  uint32_t* big_flag;
 };
 
 __device__ __forceinline__ void scratch_bind(const ASlots& t, int slot, AScratch& S) {
@@ -111,6 +120,7 @@ __device__ __forceinline__ void scratch_bind(const ASlots& t, int slot, AScratch
   S.cap = t.cap;
   S.use_reach = t.use_reach;
   S.epoch = t.slot_epoch[slot];
+  S.big_thr = t.big_thr; S.big_flag = t.big_flag;
   S.calls = 0; S.expansions = 0; S.relaxations = 0;
   S.q_status = 0; S.q_replay = 0; S.q_done = 0; S.q_log = nullptr; S.q_start = 0; S.q_goal = 0; S.q_soft = 0; S.q_cap = 0; S.q_out = nullptr;
 }
@@ -209,15 +219,17 @@ template <bool SPILL> __device__ __forceinline__ void hd_put_if(gi8p gd, bool p,
   } else g_ld[p ? k : LDS_HEAP] = (int8_t)v;
 }
 
-// a fresh epoch for the searcher's table (cleared by the wave when the 18-bit stamp wraps)
+// a fresh epoch for the searcher's table (cleared by the wave when the stamp reaches the end of its range: wave_epoch_next)
 __device__ __forceinline__ uint32_t next_epoch(const Dev& d, AScratch& S) {
-  if (S.epoch >= T_STAMP_MAX) {
+  bool wrap;
+  const uint32_t e = wave_epoch_next(S.epoch, T_STAMP_MAX, wrap);
+  if (wrap) {
     const size_t n = (size_t)max(d.n_nodes, 1);     // (the spare record behind them is never read)
     for (size_t q = lane_id(); q < n; q += 64) S.tab[q] = TEnt{0, 0u};
-    S.epoch = 0;
     __syncthreads();
   }
-  return ++S.epoch;
+  S.epoch = e;
+  return e;
 }
 
 // what a search keeps in registers while its loop runs (d, P and S themselves live in scratch memory behind references)
@@ -263,6 +275,7 @@ struct ACtx {
   // AL_OVERFLOW before n_relax can wrap); n_exp_spill: expansions made while part of the heap sat in HBM
   int n_exp, n_relax, n_exp_spill;
   int max_heap;
+  uint32_t big;           // per lane: the largest dist word a table store of this search carried (ASlots::big_thr)
   long long prof[8], pt;
   __device__ __forceinline__ void xy_of(int cell, int& x, int& y) const { cell_xy(W, w_magic, cell, x, y); }
   __device__ __forceinline__ uint32_t tile_ix(int x, int y) const { return tix(W8, x, y); }
@@ -495,7 +508,9 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
       const int h_l = abs(nx_l - gx) + abs(ny_l - gy);
       const int ngi_l = HALF ? (ng2_l >> 1) : (int)ng_l;
       const u64 ent_l = hq_pack(HALF ? ngi_l + h_l : (int)(ng_l + (double)h_l), nidx_l);
-      // (every lane stores: the idle ones to the table's spare record and the spare dir byte)
+      // (every lane stores: the idle ones to the table's spare record and the spare dir byte - their dist words count for
+      // `big` like any other: the spare record lies in the arena too)
+      C.big = max(C.big, (uint32_t)ngi_l);
       st8(tab, ok_l ? r_l : tab_spare, (u64)(uint32_t)ngi_l | ((u64)(stamp | (C.limited ? (uint32_t)(steps + 1) << 2 : 0u) | (uint32_t)dd_l) << 32));
       hd_put_if<SPILL>(gd, ok_l, heap_size + __builtin_popcount(relax & below_l), dd_l);
       KP(5);
@@ -559,7 +574,7 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
     C.turn2 = (int)(C.turn_pen * 2.0); C.contra2 = (int)(C.contra_pen * 2.0); C.veh2 = (int)(C.veh_pen * 2.0); C.stop2 = (int)(C.stop_pen * 2.0);
     C.rt2_1 = (int)(C.rt1 * 2.0); C.rt2_2 = (int)(C.rt2 * 2.0); C.rt2_3 = (int)(C.rt3 * 2.0);
   }
-  C.n_exp = 0; C.n_relax = 0; C.n_exp_spill = 0; C.max_heap = 0;
+  C.n_exp = 0; C.n_relax = 0; C.n_exp_spill = 0; C.max_heap = 0; C.big = 0;
   C.tab_spare = (uint32_t)uni(max(d.n_nodes, 1));
   for (int k = 0; k < 8; k++) C.prof[k] = 0;
   C.pt = clock64();
@@ -595,6 +610,8 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
   if (!C.fov) r = C.half ? run(std::true_type{}, std::false_type{}) : run(std::false_type{}, std::false_type{});
   else r = C.half ? run(std::true_type{}, std::true_type{}) : run(std::false_type{}, std::true_type{});
   S.expansions += C.n_exp; S.relaxations += C.n_relax;
+  // (once per search: a dist word that a quad could take for a live record went into this slot's table)
+  if (ballot(C.big >= S.big_thr) != 0ull && C.lane == 0) __hip_atomic_store(S.big_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (C.lane == 0) {   // profiling aid: deepest heap / longest search any searcher has seen (ts_debug_read words 4, 5)
     atomicMax(&d.cnt->max_heap, C.max_heap);
     atomicMax(&d.cnt->max_search_exp, C.n_exp);

@@ -19,7 +19,8 @@
 //   * dir_arr (indexed by heap SLOT, never moved by the sifts: the stale-slot quirk) is only ever read at the heap's
 //     last slot and written at the slots behind it - a stack.  Two bits per slot, the 32 slots around the heap's end in
 //     a register pair, the rest in HBM; slot 0 in a register of its own;
-//   * dist / came_from: one 4-byte record per CELL (dist 22 bits | direction 2 | epoch stamp 8) in a table that is a
+//   * dist / came_from: one 4-byte record per CELL (dist 22 bits | direction 2 | epoch stamp 8: epochs 1 .. 191, kept apart from
+//     k_replan's stamps so that the two kernels can share table memory without clearing it between them, arena_epochs.h) in a table that is a
 //     1152 x 1152-cell window centred on the search's start (8 x 8-tiled, addressed by the cell's offset in it): the record's address
 //     does not depend on the map entry, so both loads of an expansion leave together (k_replan's node-numbered table costs
 //     a dependent second round trip), and a searcher costs 5.3 MB instead of 8 bytes per road cell of the whole map.  A
@@ -73,14 +74,20 @@ constexpr int Q_SPILL = TS_QUAD_SPILL;      // heap slots per search beyond LDS 
 #define TS_QUAD_MAX_EXP (1 << 17)
 #endif
 constexpr int Q_MAX_EXP = TS_QUAD_MAX_EXP;  // expansions after which a quad hands its search (and vehicle) to k_replan
-constexpr uint32_t Q_DIST_MASK = (1u << 22) - 1, Q_STAMP_SHIFT = 24, Q_DIR_SHIFT = 22;
-enum { QS_NEEDJOB = 0, QS_POLICY = 1, QS_SEARCH = 2, QS_FOUND = 3, QS_EMPTY = 4, QS_ABANDON = 5, QS_IDLE = 6 };
+constexpr uint32_t Q_DIST_MASK = (1u << 22) - 1, Q_STAMP_SHIFT = Q_EPOCH_SHIFT, Q_DIR_SHIFT = 22;
+enum { QS_NEEDJOB = 0, QS_POLICY = 1, QS_SEARCH = 2, QS_FOUND = 3, QS_EMPTY = 4, QS_ABANDON = 5, QS_IDLE = 6, QS_WRAP = 7, QS_START = 8 };
 // the quads' own diagnostics (QSlots::stats, added up per engine by run_quad_pass, read by ts_debug_quad_stats): hand-backs
 // to k_replan by reason, searches started, table-epoch wraps, and the sift-down's steps beyond LDS: those that consulted the
 // third level fetched ahead (QST_STEP3) and the blocking steps below it (QST_DEEP).  Not simulation state: never exchanged,
 // never checkpointed.
 enum { QST_WINDOW = 1, QST_HEAP = 2, QST_BUDGET = 3, QST_PATHBUF = 4, QST_BAIL = 5, QST_OVERFLOW = 6, QST_SEARCHES = 7, QST_WRAPS = 8,
-       QST_STEP3 = 9, QST_DEEP = 10, QST_N = 16 };
+       QST_STEP3 = 9, QST_DEEP = 10,
+       // the walks back along found paths: cells written, HBM round trips they took (two cells per trip), walks, walks of odd length
+       // (they end on the first cell of a pair), walks of one cell and of two
+       QST_WALK_CELLS = 11, QST_WALK_TRIPS = 12, QST_WALKS = 13, QST_WALK_ODD = 14, QST_WALK_LEN1 = 15, QST_WALK_LEN2 = 16,
+       // (TS_QUAD_PROF builds: wave cycles the quads spent outside the lockstep loop, by segment - policy passes, search set-up,
+       // path walk, the shift copy behind it; each quad stamps its own, the rest is what the wave's total leaves)
+       QST_PROF = 20, QST_N = 24 };
 
 struct QSlots {
   int n_slots;            // searches = quads: sixteen per wave
@@ -92,7 +99,8 @@ struct QSlots {
   uint32_t* gdw;          // per slot (QL + Q_SPILL) / 16 + 4 words of 2-bit directions
   int32_t* cells;         // per slot 5 * Q_CELLS + 3 * MAXB
   int32_t* log;           // per slot 3 * QLOG
-  uint32_t* slot_epoch;
+  uint32_t* slot_epoch;        // per slot, over 1 .. epoch_max (0: fresh or cleared); kept from launch to launch and across hand-overs of the arena
+  uint32_t epoch_max;          // Q_EPOCH_MAX (arena_epochs.h; TS_DEBUG_QUAD_EPOCH_MAX: earlier wraps for tests)
   unsigned long long* stats;   // QST_N counters (QST_*)
 };
 constexpr int Q_DWORDS = (QL + Q_SPILL) / 16 + 4;
@@ -122,8 +130,13 @@ struct QState {
 };
 #ifdef TS_QUAD_PROF
 #define QP(k) do { const long long _t = clock64(); s.pf[k] += _t - s.pt; s.pt = _t; } while (0)
+// (outside the lockstep loop: QSEG_BEGIN where a segment starts, QSEG(k) where it ends - QST_PROF + k)
+#define QSEG_BEGIN() do { pf_mark = clock64(); } while (0)
+#define QSEG(k) do { const long long _t = clock64(); pf_seg[k] += _t - pf_mark; pf_mark = _t; } while (0)
 #else
 #define QP(k) do { } while (0)
+#define QSEG_BEGIN() do { } while (0)
+#define QSEG(k) do { } while (0)
 #endif
 struct QConst {   // per quad, fixed for the kernel's lifetime
   TS_GLOBAL uint32_t* tab;
@@ -497,6 +510,7 @@ __device__ __forceinline__ void quad_scratch_bind(const QSlots& qs, int slot, AS
   S.BYP = c + 5 * Q_CELLS; S.OV = S.BYP + MAXB; S.DV = S.OV + MAXB;
   S.cap = Q_CELLS;
   S.use_reach = 0;
+  S.big_thr = ~0u; S.big_flag = nullptr;      // (the quads' records carry 22-bit dists: nothing to watch)
   S.calls = 0; S.expansions = 0; S.relaxations = 0;
   S.q_log = qs.log + (size_t)slot * (3 * QLOG);
   S.q_status = DV_BAIL; S.q_replay = 0; S.q_done = 0;
@@ -551,10 +565,12 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
   req.start = req.goal = req.soft = req.cap = 0; req.out = nullptr;
   int st = QS_NEEDJOB, job = -1, n_done = 0;
   unsigned n_started = 0, n_wraps = 0;      // (QST_SEARCHES / QST_WRAPS of this quad: counted out once, at the end)
+  unsigned n_walks = 0, n_cells = 0, n_odd = 0, n_trips = 0;     // (QST_WALKS, QST_WALK_CELLS / _ODD / _TRIPS likewise)
 #ifdef TS_QUAD_PROF
   long long pf_t0 = clock64(), pf_search = 0, pf_turns = 0, pf_quadturns = 0;
   for (int k = 0; k < 10; k++) s.pf[k] = 0;
   s.pt = clock64();
+  long long pf_seg[4] = {0, 0, 0, 0}, pf_mark = 0;
 #endif
   for (;;) {
     // ---------------- per quad: everything that is not a search turn ----------------
@@ -567,22 +583,57 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
           const TS_GLOBAL uint32_t* tab = K.tab;
           gi32p outg = (gi32p)(uintptr_t)req.out;
           int px, py; xy_unpack(s.goal_xy, px, py);
+          unsigned trips = 0;
+          QSEG_BEGIN();
+          // Two cells per HBM round trip (the fifteen other quads of the wave wait for this chain of dependent loads): with the
+          // record of the current cell c, lane j requests the record of c minus direction j - the four cells c can have come
+          // from (the load is clamped to c's own record where that cell lies outside the window or the map).  c's record names
+          // the direction d0 it was reached by, lane d0's record is that of the cell before it.  Only records on the path are
+          // ever interpreted: the three others may be stale or another epoch's and are dropped unread.  (The tables start on
+          // 256-byte boundaries, an 8 x 8 tile of records is two 128-byte lines: most of the extra loads ride on the line of c's own.
+          // Measured on the first replanning wave of the bench workload, wave cycles in this loop: 266.5e9 one cell per trip, 186.3e9
+          // so, 193.8e9 when lanes only ask for records in c's own line - profiles/r15_quad_prof.json.)
           while (px != s.sx || py != s.sy) {
+            const int qx = px - K.dx, qy = py - K.dy;
+            const bool qin = ((unsigned)qx < (unsigned)K.W) & ((unsigned)qy < (unsigned)K.H) &
+                             ((unsigned)(qx - s.ox) < (unsigned)K.tw) & ((unsigned)(qy - s.oy) < (unsigned)K.th);
+            const uint32_t ixc = q_tix(K, s.ox, s.oy, px, py);
+            const uint32_t rc = tab[ixc], rq = tab[qin ? q_tix(K, s.ox, s.oy, qx, qy) : ixc];
+            trips++;
             if (len >= req.cap) { len = -1; break; }
             outg[req.cap - 1 - len] = py * K.W + px;
             len++;
-            const int dd = (int)((tab[q_tix(K, s.ox, s.oy, px, py)] >> Q_DIR_SHIFT) & 3u);
-            px -= (dd == 1) - (dd == 3); py -= (dd == 0) - (dd == 2);
+            const int d0 = (int)((rc >> Q_DIR_SHIFT) & 3u);
+            px -= (d0 == 1) - (d0 == 3); py -= (d0 == 0) - (d0 == 2);
+            if (px == s.sx && py == s.sy) break;      // (the start was reached at the first cell of the pair)
+            const int r0 = qperm<QP_B0>((int)rq), r1 = qperm<QP_B1>((int)rq), r2 = qperm<QP_B2>((int)rq), r3 = qperm<QP_B3>((int)rq);
+            const int d1 = (int)(((uint32_t)(d0 == 0 ? r0 : d0 == 1 ? r1 : d0 == 2 ? r2 : r3) >> Q_DIR_SHIFT) & 3u);
+            if (len >= req.cap) { len = -1; break; }
+            outg[req.cap - 1 - len] = py * K.W + px;
+            len++;
+            px -= (d1 == 1) - (d1 == 3); py -= (d1 == 0) - (d1 == 2);
           }
           wave_mem_sync();
+          QSEG(2);
+          if (len > 0) {
+            n_walks++; n_cells += (unsigned)len; n_odd += (unsigned)(len & 1); n_trips += trips;
+            if ((len <= 2) & one) atomicAdd(&qs.stats[len == 1 ? QST_WALK_LEN1 : QST_WALK_LEN2], 1ull);
+          }
+          // the path slides to the front of its buffer, sixteen cells per step: every lane loads its four before it stores them
+          // (a store writes below everything still to be read: shift > 0)
           const int shift = req.cap - len;
           if (len > 0 && shift > 0)
-            for (int k0 = 0; k0 < len; k0 += 4) {
-              const int k = k0 + j;
-              const int v = k < len ? outg[shift + k] : 0;
-              if (k < len) outg[k] = v;
+            for (int k0 = 0; k0 < len; k0 += 16) {
+              const int ka = k0 + j, kb = ka + 4, kc = ka + 8, kd = ka + 12;
+              const int va = ka < len ? outg[shift + ka] : 0, vb = kb < len ? outg[shift + kb] : 0;
+              const int vc = kc < len ? outg[shift + kc] : 0, vd = kd < len ? outg[shift + kd] : 0;
+              if (ka < len) outg[ka] = va;
+              if (kb < len) outg[kb] = vb;
+              if (kc < len) outg[kc] = vc;
+              if (kd < len) outg[kd] = vd;
             }
           wave_mem_sync();
+          QSEG(3);
         }
         if (len < 0) { st = QS_ABANDON; s.why = QST_PATHBUF; }
         else {
@@ -608,18 +659,20 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
         st = QS_POLICY;
       }
       if (st == QS_POLICY) {
+        QSEG_BEGIN();
         const int r = quad_policy(d, P, qs, q, slot, job, n_done, req);
+        QSEG(0);
         if (r != DV_SUSPEND) { st = QS_NEEDJOB; continue; }
+        // (a table whose epochs are used up is cleared by the whole wave, below: the quad waits there for the others to come out)
+        if (epoch >= qs.epoch_max) { st = QS_WRAP; break; }
+        st = QS_START;
+      }
+      if (st == QS_START) {
         // ---- a fresh search (113-128): new epoch for the table, start record, one-entry heap
-        epoch++;
+        QSEG_BEGIN();
+        bool wrap;
+        epoch = quad_epoch_next(epoch, qs.epoch_max, wrap);
         n_started++;
-        if (epoch > 255u) {
-          n_wraps++;
-          const size_t n = qs.tab_entries;
-          for (size_t t = (size_t)j; t < n; t += 4) K.tab[t] = 0u;
-          epoch = 1;
-          wave_mem_sync();
-        }
         int gxx, gyy, sxx, syy;
         cell_xy(d, req.goal, gxx, gyy); cell_xy(d, req.start, sxx, syy);
         s.gx = gxx; s.gy = gyy; s.sx = sxx; s.sy = syy;
@@ -635,8 +688,24 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
         }
         s.hs = 1;
         wave_mem_sync();
+        QSEG(1);
         st = QS_SEARCH;
       }
+    }
+    // ---------------- tables whose epochs are used up: the whole wave clears them, one after the other ----------------
+    // (191 searches per slot between two of these, kept across launches: an ordinary event, not a rare one - 64 lanes with
+    // 8-byte stores take tens of microseconds for the 5.3 MB where the quad's own four lanes, a word each, took a millisecond)
+    if (unsigned long long wr = ballot(st == QS_WRAP)) {
+      const size_t n2 = qs.tab_entries >> 1;      // (a multiple of 64 words: whole 8 x 8 tiles)
+      do {
+        const int src = __builtin_ctzll(wr);
+        wr &= ~(0xFull << src);
+        gu64p t8 = (gu64p)(uintptr_t)rl((u64)(uintptr_t)K.tab, src);
+        for (size_t t = (size_t)lane; t < n2; t += 64) t8[t] = 0ull;
+      } while (wr);
+      wave_mem_sync();
+      if (st == QS_WRAP) { n_wraps++; st = QS_START; }     // (quad_epoch_next starts over at 1: epoch >= epoch_max)
+      continue;
     }
     const unsigned long long act = ballot(st == QS_SEARCH);
     if (act == 0ull) break;
@@ -663,11 +732,17 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
     for (int k = 0; k < 8; k++) atomicAdd((unsigned long long*)&d.cnt->qprof[k], (unsigned long long)s.pf[k]);
     for (int k = 8; k < 10; k++) atomicAdd((unsigned long long*)&d.cnt->prof[k - 4], (unsigned long long)s.pf[k]);   // (prof[4..5]: DevCnt keeps its layout)
   }
+  if (one) for (int k = 0; k < 4; k++) atomicAdd(&qs.stats[QST_PROF + k], (unsigned long long)pf_seg[k]);
 #endif
   if (one) {
     qs.slot_epoch[slot] = epoch;
     if (n_started) atomicAdd(&qs.stats[QST_SEARCHES], (unsigned long long)n_started);
     if (n_wraps) atomicAdd(&qs.stats[QST_WRAPS], (unsigned long long)n_wraps);
+    if (n_walks) {
+      atomicAdd(&qs.stats[QST_WALKS], (unsigned long long)n_walks); atomicAdd(&qs.stats[QST_WALK_CELLS], (unsigned long long)n_cells);
+      atomicAdd(&qs.stats[QST_WALK_TRIPS], (unsigned long long)n_trips);
+      if (n_odd) atomicAdd(&qs.stats[QST_WALK_ODD], (unsigned long long)n_odd);
+    }
     if (s.n_step3) atomicAdd(&qs.stats[QST_STEP3], (unsigned long long)s.n_step3);
     if (s.n_deep) atomicAdd(&qs.stats[QST_DEEP], (unsigned long long)s.n_deep);
   }

@@ -942,6 +942,32 @@ int ts_debug_quad_stats(ts_handle e, int64_t* out, int32_t n) {
   return TS_QUAD_STATS_N;
 }
 
+// debugging hook (not part of include/trafficsim.h): the table arena k_replan and the quads share, as int64 - [0] hand-overs to the
+// quads, [1] hand-overs to k_replan's waves, [2] clears run (none unless a big dist was seen or TS_ARENA_CLEAR=1), [3] the big-dist flag
+// as it stands on the device, [4] hand-overs that found it set, [5] the quads' tables alias the arena, [6] the quads hold it now.
+// Writes min(n, TS_ARENA_INFO_N) words and returns TS_ARENA_INFO_N.
+constexpr int TS_ARENA_INFO_N = 7;
+int ts_debug_arena_info(ts_handle e, int64_t* out, int32_t n) {
+  if (!e || (!out && n > 0) || n < 0) return TS_E_INVALID;
+  uint32_t big = 0;
+  if (e->slots_ready) TRY(read_back(e, &big, e->slots.big_flag, sizeof(big)));
+  const long long v[TS_ARENA_INFO_N] = {e->arena_to_q, e->arena_to_w, e->arena_clears, (long long)big, e->arena_big_seen,
+                                        e->arena_shared ? 1 : 0, e->arena_quad ? 1 : 0};
+  for (int k = 0; k < std::min<int>(n, TS_ARENA_INFO_N); k++) out[k] = v[k];
+  return TS_ARENA_INFO_N;
+}
+// debugging hook (not part of include/trafficsim.h): the quads' walks back along found paths over this engine's quad passes, as
+// int64 - [0] walks, [1] cells written, [2] HBM round trips (two cells each, the last one of an odd walk one), [3] walks of odd
+// length (they ended on the first cell of a pair), [4] walks of one cell, [5] walks of two.  Returns TS_QUAD_WALK_N.
+constexpr int TS_QUAD_WALK_N = 6;
+int ts_debug_quad_walks(ts_handle e, int64_t* out, int32_t n) {
+  if (!e || (!out && n > 0) || n < 0) return TS_E_INVALID;
+  const long long* qs = e->quad_stats;
+  const long long v[TS_QUAD_WALK_N] = {qs[QST_WALKS], qs[QST_WALK_CELLS], qs[QST_WALK_TRIPS], qs[QST_WALK_ODD], qs[QST_WALK_LEN1], qs[QST_WALK_LEN2]};
+  for (int k = 0; k < std::min<int>(n, TS_QUAD_WALK_N); k++) out[k] = v[k];
+  return TS_QUAD_WALK_N;
+}
+
 int ts_set_device(int32_t device) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return TS_E_DEVICE;

@@ -23,8 +23,9 @@ inline QuadRequest quad_request() {
 // 1152 x 1152 cells (5.3 MB), the heap's HBM spill, the direction words and the path staging buffers - sixteen slots per wave,
 // TS_QUAD_WAVES_PER_CU waves per CU (TS_QUAD_SLOTS overrides the count).  The two kernels never need all their tables at
 // once - a replanning wave runs on the quads with a few k_replan waves beside them, every other tick on k_replan alone - so
-// the quads' tables ALIAS the tables of k_replan's slots beyond the first `side_slots`: the arena is cleared (and the epochs
-// of its slots reset) whenever it changes hands, twice per six ticks, ~40 ms for ~170 GB (arena_to_quads / arena_to_waves).
+// the quads' tables ALIAS the tables of k_replan's slots beyond the first `side_slots`.  The arena changes hands twice per
+// six ticks and is not cleared for it (arena_to_quads / arena_to_waves below: the two record formats cannot collide; the
+// clears it replaces took 22 ms for 152 GB and about as long for 165 GB each time).
 int ensure_slots(E* e) {
   if (e->slots_ready) return TS_OK;
   // (the quad searcher, astar_quad.h: on unless TS_QUAD=0; it carries half-unit costs without a field-of-view mask)
@@ -65,8 +66,11 @@ int ensure_slots(E* e) {
   HIPOK(dalloc(e, &T.gd, S * spill));
   HIPOK(dalloc(e, &T.cells, S * ((size_t)5 * T.cap + 3 * MAXB)));
   HIPOK(dalloc(e, &T.slot_epoch, S));
+  HIPOK(dalloc(e, &T.big_flag, 1));
+  T.big_thr = getenv("TS_DEBUG_ARENA_BIGDIST") ? (uint32_t)std::max(1, atoi(getenv("TS_DEBUG_ARENA_BIGDIST"))) : ARENA_BIGDIST;
   HIPOK(hipMemsetAsync(T.tab, 0, S * T.tab_entries * sizeof(TEnt), e->stream));
-  HIPOK(hipMemsetAsync(T.slot_epoch, 0, S * 4, e->stream));
+  HIPOK(hipMemsetAsync(T.slot_epoch, 0, S * 4, e->stream));     // (0: a fresh slot - its first stamp is the first of k_replan's range)
+  HIPOK(hipMemsetAsync(T.big_flag, 0, sizeof(uint32_t), e->stream));
   HIPOK(hipStreamSynchronize(e->stream));
   e->slots_ready = true;
   return TS_OK;
@@ -78,10 +82,12 @@ int ensure_qslots(E* e) {
   ASlots& T = e->slots;
   QSlots& Q = e->qslots;
   const auto [q_want, q_side] = quad_request();
+  Q.epoch_max = quad_epoch_limit(getenv("TS_DEBUG_QUAD_EPOCH_MAX") ? atoll(getenv("TS_DEBUG_QUAD_EPOCH_MAX")) : 0);
   // the quads' tables: inside k_replan's table arena behind the slots of the side waves when they fit there, in memory of
   // their own otherwise (small maps: a node-indexed table is smaller than a window then)
   e->side_slots = std::max(1, std::min(T.n_slots / 4, 1024));
-  const size_t alias_bytes = (size_t)(T.n_slots - e->side_slots) * T.tab_entries * sizeof(TEnt);
+  // (less 256 bytes: the quads' tables start on a 256-byte boundary, so that 32 of their records are one 128-byte line)
+  const size_t alias_raw = (size_t)(T.n_slots - e->side_slots) * T.tab_entries * sizeof(TEnt), alias_bytes = alias_raw > 256 ? alias_raw - 256 : 0;
   const size_t need = (size_t)q_want * Q.tab_entries * 4;
   size_t f2 = 0, t2 = 0;
   HIPOK(hipMemGetInfo(&f2, &t2));
@@ -92,7 +98,7 @@ int ensure_qslots(E* e) {
   if (alias_bytes >= need / 2 && alias_bytes >= (size_t)256 * Q.tab_entries * 4) {
     Q.n_slots = (int)std::min<long long>(q_want, (long long)(alias_bytes / (Q.tab_entries * 4)) / 16 * 16);
     if ((double)Q.n_slots * (double)q_side > (double)f2 * qfrac) return off();
-    Q.tab = (uint32_t*)(T.tab + (size_t)e->side_slots * T.tab_entries);
+    Q.tab = (uint32_t*)(((uintptr_t)(T.tab + (size_t)e->side_slots * T.tab_entries) + 255) & ~(uintptr_t)255);
     e->arena_shared = true;
     e->arena_quad = false;
   } else {
@@ -119,21 +125,54 @@ int ensure_qslots(E* e) {
   e->qslots_ready = true;
   return TS_OK;
 }
-// the shared part of the table arena changes hands: cleared, the epochs of the slots that own it reset
+// The shared part of the table arena changes hands WITHOUT a clear: the two kernels' records cannot pass for each other's
+// (arena_epochs.h: stamps disjoint in the top byte of a word, zero no stamp of either), and the epochs of both kinds of slot
+// are kept across hand-overs, so what a slot left behind before it lost its table is as stale to it afterwards as anything
+// it wrote before.  The one exception is a k_replan dist word of 2^24 or more (ASlots::big_thr): a search that stored one raised
+// ASlots::big_flag, and the next hand-over to the quads clears their tables as every hand-over used to.  TS_ARENA_CLEAR=1 keeps
+// that behaviour for both directions (A/B runs, bisection).
+// A hand-over clear: the tables of the slots that take the shared part of the arena and their epochs (TS_DEBUG_REPLAN times it
+// with HIP events of its own)
+int arena_clear(E* e, void* tab, size_t tab_bytes, uint32_t* epochs, size_t n_epochs, const char* to) {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  const bool timed = getenv("TS_DEBUG_REPLAN") != nullptr;
+  if (timed) { HIPOK(hipEventCreate(&ev[0])); HIPOK(hipEventCreate(&ev[1])); HIPOK(hipEventRecord(ev[0], e->stream)); }
+  HIPOK(hipMemsetAsync(tab, 0, tab_bytes, e->stream));
+  HIPOK(hipMemsetAsync(epochs, 0, n_epochs * 4, e->stream));
+  e->arena_clears++;
+  if (timed) {
+    float ms = 0.0f;
+    HIPOK(hipEventRecord(ev[1], e->stream));
+    HIPOK(hipEventSynchronize(ev[1]));
+    HIPOK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    HIPOK(hipEventDestroy(ev[0])); HIPOK(hipEventDestroy(ev[1]));
+    fprintf(stderr, "[replan] tick %lld: the table arena goes to %s, %.1f GB cleared in %.2f ms\n", (long long)e->C.step_count, to, (double)tab_bytes * 1e-9, (double)ms);
+  }
+  return TS_OK;
+}
+inline bool arena_always_clear() { return env_int("TS_ARENA_CLEAR", 0) != 0; }
 int arena_to_quads(E* e) {
   if (!e->arena_shared || e->arena_quad) return TS_OK;
-  HIPOK(hipMemsetAsync(e->qslots.tab, 0, (size_t)e->qslots.n_slots * e->qslots.tab_entries * 4, e->stream));
-  HIPOK(hipMemsetAsync(e->qslots.slot_epoch, 0, (size_t)e->qslots.n_slots * 4, e->stream));
+  // (read here rather than with a pass' counters: query batches and spawn-time searches use these tables too)
+  uint32_t big = 0;
+  TRY(read_back(e, &big, e->slots.big_flag, sizeof(big)));
+  if (big) e->arena_big_seen++;
+  if (big || arena_always_clear()) {
+    TRY(arena_clear(e, e->qslots.tab, (size_t)e->qslots.n_slots * e->qslots.tab_entries * 4, e->qslots.slot_epoch, (size_t)e->qslots.n_slots, "the quads"));
+    if (big) HIPOK(hipMemsetAsync(e->slots.big_flag, 0, sizeof(uint32_t), e->stream));
+  }
   e->arena_quad = true;
+  e->arena_to_q++;
   return TS_OK;
 }
 int arena_to_waves(E* e) {
   if (!e->arena_shared || !e->arena_quad) return TS_OK;
   const ASlots& T = e->slots;
   const size_t n = (size_t)(T.n_slots - e->side_slots);
-  HIPOK(hipMemsetAsync(T.tab + (size_t)e->side_slots * T.tab_entries, 0, n * T.tab_entries * sizeof(TEnt), e->stream));
-  HIPOK(hipMemsetAsync(T.slot_epoch + e->side_slots, 0, n * 4, e->stream));
+  if (arena_always_clear())
+    TRY(arena_clear(e, T.tab + (size_t)e->side_slots * T.tab_entries, n * T.tab_entries * sizeof(TEnt), T.slot_epoch + e->side_slots, n, "k_replan's waves"));
   e->arena_quad = false;
+  e->arena_to_w++;
   return TS_OK;
 }
 
@@ -292,6 +331,10 @@ int run_quad_pass(E* e) {
     // the entries fetched ahead - "sift deep" is what follows it, the blocking levels)
     fprintf(stderr, "[quadprof] per wave turn: delivery of the last entry %.0f, deep sift's first step %.0f\n", (double)pf[4] / pf[2], (double)pf[5] / pf[2]);
     HIPOK(hipMemset(d.cnt->qprof, 0, sizeof(qf)));
+    // (outside the lockstep loop: every quad stamps its own segments, and quads that leave the loop together share their cycles)
+    const double out = (double)(pf[0] - pf[1]), seg[4] = {(double)qst[QST_PROF], (double)qst[QST_PROF + 1], (double)qst[QST_PROF + 2], (double)qst[QST_PROF + 3]};
+    fprintf(stderr, "[quadprof] outside the lockstep loop %.0f wave cycles: policy passes %.0f, search set-up %.0f, path walk %.0f, shift copy %.0f, rest %.0f\n",
+            out, seg[0], seg[1], seg[2], seg[3], out - seg[0] - seg[1] - seg[2] - seg[3]);
   }
 #endif
   if (getenv("TS_DEBUG_REPLAN")) {
