@@ -93,7 +93,20 @@ struct AScratch {
   int32_t* q_log;                          // per finished search: path length, expansions, relaxations
   int q_start, q_goal, q_soft, q_cap;      // the search the policy is waiting for
   int32_t* q_out;
+  // DM_WAVE with a tail control block (k_replan's plain passes, replan.h RTail): the same log, kept by astar_any<DM_WAVE> for the
+  // searches without a step limit and on the flow, so that a step_decide whose search was handed to the host (DV_HANDOFF) can be
+  // re-run from the top with that search's result in the log.  t_ctl == nullptr: no search of this wave is ever handed over.
+  struct TailCtl* t_ctl;
+  int t_thr, t_floor, t_first;             // hand over when t_ctl->idle >= t_thr and the search has made t_floor expansions; first look at t_first
 };
+// The tail control block of a k_replan pass (device memory; the host zeroes idle and n before the launch and reads n and the
+// entries after the pass' stream has drained): waves that found the queue empty, searches handed to the host, and for each the
+// queue entry, the searcher slot, its ordinal among the logged searches of this step_decide, its arguments and where its path goes.
+struct TailEnt { int32_t i, slot, ord, start, goal, soft, out_off, out_cap; };   // out_off: ints from ASlots::cells
+struct TailCtl { int idle, n, cap, pad_; };     // TailEnt list[cap] follows
+constexpr int TAIL_PERIOD = 4096;     // fresh expansions between two looks at TailCtl::idle
+constexpr int TAIL_GAVE_UP = -1;      // astar_loop's heap size once the search has given up
+
 
 struct ASlots {
   int n_slots, heap_cap, cap, use_reach;
@@ -123,6 +136,7 @@ __device__ __forceinline__ void scratch_bind(const ASlots& t, int slot, AScratch
   S.big_thr = t.big_thr; S.big_flag = t.big_flag;
   S.calls = 0; S.expansions = 0; S.relaxations = 0;
   S.q_status = 0; S.q_replay = 0; S.q_done = 0; S.q_log = nullptr; S.q_start = 0; S.q_goal = 0; S.q_soft = 0; S.q_cap = 0; S.q_out = nullptr;
+  S.t_ctl = nullptr; S.t_thr = 0; S.t_floor = 0; S.t_first = -1;
 }
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
@@ -276,6 +290,12 @@ struct ACtx {
   int n_exp, n_relax, n_exp_spill;
   int max_heap;
   uint32_t big;           // per lane: the largest dist word a table store of this search carried (ASlots::big_thr)
+  // the tail rule (AScratch::t_ctl; `tail`: this search follows it): n_exp then counts up to zero, the expansions made are
+  // n_exp + n_exp_base (exp_made), and at zero the search looks at the idle counter
+  int n_exp_base, tail_thr, tail_floor;
+  bool tail;
+  const TS_GLOBAL int* tail_idle;
+  __device__ __forceinline__ int exp_made() const { return n_exp + n_exp_base; }
   long long prof[8], pt;
   __device__ __forceinline__ void xy_of(int cell, int& x, int& y) const { cell_xy(W, w_magic, cell, x, y); }
   __device__ __forceinline__ uint32_t tile_ix(int x, int y) const { return tix(W8, x, y); }
@@ -285,7 +305,8 @@ struct ACtx {
 #else
 #define KP(k) do { } while (0)
 #endif
-enum { AL_EMPTY = -2, AL_OVERFLOW = -1, AL_SWITCH = -3 };   // astar_loop results besides a path length >= 0
+enum { AL_EMPTY = -2, AL_OVERFLOW = -1, AL_SWITCH = -3, AL_HANDOFF = -4 };   // astar_loop results besides a path length >= 0
+constexpr int AW_HANDOFF = -2;   // astar_wave: the search was abandoned for the host to run (besides a length >= 0 and -1 = capacity)
 
 // ---------------------------------------------------------------------------------------------
 // astar_core's main loop, one search spread over one wavefront.  The algorithm is the sequential one - same heap
@@ -303,7 +324,9 @@ enum { AL_EMPTY = -2, AL_OVERFLOW = -1, AL_SWITCH = -3 };   // astar_loop result
 // SPILL = false runs while the whole heap fits LDS (straight LDS accesses); SPILL = true is the general form.  Either
 // returns AL_SWITCH when the other one should take over.
 // ---------------------------------------------------------------------------------------------
-template <bool SPILL, bool HALF, bool FOV>
+// TAIL: the loop carries the tail rule's test (searches of a wave with a tail control block, half units, no field of view);
+// without it the loop is instruction for instruction what it was before the rule existed.
+template <bool SPILL, bool HALF, bool FOV, bool TAIL = false>
 __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
   // A lone wave issues one instruction every four cycles whatever its kind, so this loop is written for instruction
   // count: lane-parallel vector work and one ballot in place of scalar walks, no scalar <-> vector round trips that
@@ -439,9 +462,21 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
     const bool node_c = rl((int)node_l, 4) != 0;     // (only a start cell can be off the node set: dist 0, no steps)
     const uint32_t m_c = node_c ? (uint32_t)(e_c >> 32) : (epoch << T_STAMP_SHIFT);
     const int dist_c = !node_c ? 0 : (m_c >> T_STAMP_SHIFT) == epoch ? (int)(uint32_t)e_c : A_INF;
-    const bool fresh = g <= dist_c;      // (a stale pop relaxes nothing)
+    bool fresh = g <= dist_c;      // (a stale pop relaxes nothing)
     KP(3);
     C.n_exp += fresh ? 1 : 0;
+    // the tail rule: one scalar compare per turn; every TAIL_PERIOD fresh expansions a look at the idle counter.  The search is
+    // abandoned (nothing of it is kept) once all but t_max waves of the launch have found the queue empty.
+    // (A search under the rule counts its expansions from minus the number still to go until the next look - the count itself is
+    // n_exp + n_exp_base -, so the test is a compare with zero.  Giving up is no exit of its own - that would stage the loop's
+    // results on every turn: the heap size goes to TAIL_GAVE_UP and the pop counts as stale, so the turn relaxes nothing and the
+    // loop ends as if the heap were empty; astar_wave reads the heap size.)
+    if constexpr (TAIL) if (__builtin_expect(C.n_exp == 0, 0)) {
+      const int made = C.n_exp_base;
+      C.n_exp_base = made + TAIL_PERIOD; C.n_exp = -TAIL_PERIOD;
+      const int idle = uni(__hip_atomic_load(C.tail_idle, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      if ((idle >= C.tail_thr) & (made >= C.tail_floor)) { heap_size = TAIL_GAVE_UP; fresh = false; }
+    }
     const int steps = C.limited ? (int)((m_c >> 2) & T_STEPS_MASK) : 0;
     const uint32_t bits = (uint32_t)rl((int)a_l, 4) & 15u;
     // ---- lane dd < 4 evaluates neighbour dd from what was fetched before the sift-down -------------------------
@@ -542,8 +577,10 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
 // astar_core (astar_numba.py:87-239).  All 64 lanes call it with identical arguments and get the same return value.
 // Writes the path (start excluded, goal included) to out[0..len); returns len >= 0, or -1 when the heap or the output
 // buffer is too small.
+// may_hand_off (astar_any<DM_WAVE> for a logged search of a wave with a tail control block): the search follows the tail rule and
+// returns AW_HANDOFF, counted nowhere, when it gives up for the host.
 __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int start_idx, int goal_idx, bool soft,
-                          bool ignore_flow, int maximum_steps, int32_t* out, int out_cap) {
+                          bool ignore_flow, int maximum_steps, int32_t* out, int out_cap, bool may_hand_off = false) {
   ACtx C;
   C.lane = lane_id();
   // the arguments arrive in vector registers: tell the compiler they are wave-uniform (scalar loop control)
@@ -574,13 +611,20 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
     C.turn2 = (int)(C.turn_pen * 2.0); C.contra2 = (int)(C.contra_pen * 2.0); C.veh2 = (int)(C.veh_pen * 2.0); C.stop2 = (int)(C.stop_pen * 2.0);
     C.rt2_1 = (int)(C.rt1 * 2.0); C.rt2_2 = (int)(C.rt2 * 2.0); C.rt2_3 = (int)(C.rt3 * 2.0);
   }
-  C.n_exp = 0; C.n_relax = 0; C.n_exp_spill = 0; C.max_heap = 0; C.big = 0;
+  C.n_relax = 0; C.n_exp_spill = 0; C.max_heap = 0; C.big = 0;     // (n_exp: with the tail rule's switches below)
   C.tab_spare = (uint32_t)uni(max(d.n_nodes, 1));
   for (int k = 0; k < 8; k++) C.prof[k] = 0;
   C.pt = clock64();
   // the chain of relaxations behind a heap entry never revisits a cell (dist strictly falls), so it is shorter than
   // N: a limit of N or more never binds and the steps need not be carried
   C.limited = C.maximum_steps < C.N;
+  {
+    const bool tail = may_hand_off && S.t_ctl != nullptr && !C.limited && !C.ignore_flow && C.half && !C.fov;
+    C.tail = uni((int)tail) != 0;
+    C.n_exp_base = uni(tail ? S.t_first : 0); C.n_exp = -C.n_exp_base;
+    C.tail_thr = uni(S.t_thr); C.tail_floor = uni(max(S.t_floor, 1));
+    C.tail_idle = (const TS_GLOBAL int*)(uintptr_t)uni64((u64)(uintptr_t)(tail ? &S.t_ctl->idle : nullptr));
+  }
   C.xy_of(C.goal_idx, C.gx, C.gy);
   C.xy_of(C.start_idx, C.sx, C.sy);
   C.goal_xy = xy_pack(C.gx, C.gy);
@@ -596,31 +640,34 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
   int r;
   // (the default policy is the <HALF, no FOV> pair; the other instantiations serve fractional penalties and
   // VEHICLE_RESPECT_AWARENESS)
-  auto run = [&](auto half_c, auto fov_c) {
-    constexpr bool HF = decltype(half_c)::value, FV = decltype(fov_c)::value;
+  auto run = [&](auto half_c, auto fov_c, auto tail_c) {
+    constexpr bool HF = decltype(half_c)::value, FV = decltype(fov_c)::value, TL = decltype(tail_c)::value;
     for (;;) {
-      int q = astar_loop<false, HF, FV>(C, heap_size);
+      int q = astar_loop<false, HF, FV, TL>(C, heap_size);
       if (q != AL_SWITCH) return q;
-      const int exp0 = C.n_exp;
-      q = astar_loop<true, HF, FV>(C, heap_size);
-      C.n_exp_spill += C.n_exp - exp0;
+      const int exp0 = C.exp_made();
+      q = astar_loop<true, HF, FV, TL>(C, heap_size);
+      C.n_exp_spill += C.exp_made() - exp0;
       if (q != AL_SWITCH) return q;
     }
   };
-  if (!C.fov) r = C.half ? run(std::true_type{}, std::false_type{}) : run(std::false_type{}, std::false_type{});
-  else r = C.half ? run(std::true_type{}, std::true_type{}) : run(std::false_type{}, std::true_type{});
-  S.expansions += C.n_exp; S.relaxations += C.n_relax;
+  if (C.tail && C.half && !C.fov) r = run(std::true_type{}, std::false_type{}, std::true_type{});
+  else if (!C.fov) r = C.half ? run(std::true_type{}, std::false_type{}, std::false_type{}) : run(std::false_type{}, std::false_type{}, std::false_type{});
+  else r = C.half ? run(std::true_type{}, std::true_type{}, std::false_type{}) : run(std::false_type{}, std::true_type{}, std::false_type{});
+  if (heap_size == TAIL_GAVE_UP) r = AL_HANDOFF;
+  if (r == AL_HANDOFF) S.calls--;     // (the abandoned part is not counted: the host's search is)
+  else { S.expansions += C.exp_made(); S.relaxations += C.n_relax; }
   // (once per search: a dist word that a quad could take for a live record went into this slot's table)
   if (ballot(C.big >= S.big_thr) != 0ull && C.lane == 0) __hip_atomic_store(S.big_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (C.lane == 0) {   // profiling aid: deepest heap / longest search any searcher has seen (ts_debug_read words 4, 5)
     atomicMax(&d.cnt->max_heap, C.max_heap);
-    atomicMax(&d.cnt->max_search_exp, C.n_exp);
+    if (r != AL_HANDOFF) atomicMax(&d.cnt->max_search_exp, C.exp_made());
     if (C.n_exp_spill) atomicAdd((unsigned long long*)&d.cnt->spill_exp, (unsigned long long)C.n_exp_spill);
 #ifdef TS_KPROF
     for (int k = 0; k < 8; k++) d.cnt->prof[k] = C.prof[k];
 #endif
   }
-  return r == AL_EMPTY ? 0 : r;
+  return r == AL_EMPTY ? 0 : r == AL_HANDOFF ? AW_HANDOFF : r;
 }
 
 // Strict reachability of `goal` from `start`: a frontier BFS by the wave over the same edges the strict A* relaxes

@@ -205,6 +205,11 @@ int ts_destroy(ts_handle e) {
   if (e->quad_stream) { (void)hipStreamSynchronize(e->quad_stream); (void)hipStreamDestroy(e->quad_stream); }
   if (e->quad_ev0) (void)hipEventDestroy(e->quad_ev0);
   if (e->quad_ev1) (void)hipEventDestroy(e->quad_ev1);
+  delete e->tail.pool;            // joins the host tail's workers
+  if (e->tail.stream) { (void)hipStreamSynchronize(e->tail.stream); (void)hipStreamDestroy(e->tail.stream); }
+  if (e->tail.ev_go) (void)hipEventDestroy(e->tail.ev_go);
+  if (e->tail.ev_copied) (void)hipEventDestroy(e->tail.ev_copied);
+  if (e->tail.h_amap) (void)hipHostFree(e->tail.h_amap);
   if (e->hm) (void)hipHostFree(e->hm);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   uint32_t* hw = e->h_words;
@@ -991,6 +996,38 @@ int ts_profile_get(ts_handle e, int32_t id, double* total_ms, int64_t* launches,
   return TS_OK;
 }
 
+// debugging hook (not part of include/trafficsim.h; profiles/tail_probe.py): n searches (start cell, goal cell, soft; no step limit,
+// on the flow) on `threads` threads of the host tail's pool (0: all), on a fresh copy of the A* snapshot of the engine's current
+// maps.  Per search its path length, its expansions and the milliseconds it took; *wall_ms: the whole batch.  Nothing is counted
+// or committed.  TS_E_UNSUPPORTED where the host searcher does not apply (fractional penalties, field-of-view masking).
+int ts_debug_tail_probe(ts_handle e, int32_t n, const int32_t* start, const int32_t* goal, const int32_t* soft, int32_t threads,
+                        int32_t* out_len, int32_t* out_exp, double* out_ms, double* wall_ms) {
+  if (!e || n < 0 || (n > 0 && (!start || !goal || !soft || !out_len || !out_exp || !out_ms)) || !wall_ms) return TS_E_INVALID;
+  for (int k = 0; k < n; k++) if (start[k] < 0 || start[k] >= e->N || goal[k] < 0 || goal[k] >= e->N) return fail(e, TS_E_INVALID, "probe endpoints out of bounds");
+  if (!astar_half_units(e->P) || e->P.respect_awareness) return fail(e, TS_E_UNSUPPORTED, "the host searcher carries half-unit costs without a field-of-view mask");
+  TRY(ensure_density(e, e->d.occ));
+  e->density_valid = false;
+  TRY(ensure_slots(e));
+  e->amap_valid = false;
+  TRY(ensure_amap(e));
+  e->amap_valid = false;
+  TRY(tail_snapshot_begin(e));
+  TRY(tail_snapshot_wait(e));
+  const ahost::Map map = tail_map(e);
+  const ahost::Costs costs = tail_costs(e->P);
+  const int cap = e->slots.cap;
+  const double t0 = now_ms();
+  e->tail.pool->run(n, [&](ahost::Searcher& s, int k) {
+    thread_local std::vector<int32_t> cells;
+    cells.resize((size_t)cap);
+    const double t = now_ms();
+    const ahost::Result r = s.run(map, costs, ahost::Query{start[k], goal[k], soft[k] != 0, false, 0x7FFFFFFF}, cells.data(), cap);
+    out_ms[k] = now_ms() - t; out_len[k] = r.len; out_exp[k] = r.n_exp;
+  }, threads);
+  *wall_ms = now_ms() - t0;
+  return TS_OK;
+}
+
 int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_t soft, int32_t ignore_flow,
              int32_t maximum_steps, int32_t* out_xy, int32_t cap_cells) {
   if (!e) return TS_E_INVALID;
@@ -1005,6 +1042,22 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
   e->amap_valid = false;
   TRY(ensure_amap(e));
   e->amap_valid = false;
+  if (e->tail.astar_host) {   // TS_ASTAR_HOST (a test hook): the host searcher on a fresh copy of the snapshot
+    TRY(tail_snapshot_begin(e));
+    TRY(tail_snapshot_wait(e));
+    std::vector<int32_t> cells((size_t)e->slots.cap);
+    ahost::Result r{};
+    const ahost::Map map = tail_map(e);
+    const ahost::Costs costs = tail_costs(e->P);
+    const ahost::Query q{sy * e->W + sx, gy * e->W + gx, soft != 0, ignore_flow != 0, maximum_steps};
+    e->tail.pool->run(1, [&](ahost::Searcher& s, int) { r = s.run(map, costs, q, cells.data(), (int)cells.size()); });
+    if (r.len < 0) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");
+    hipLaunchKernelGGL(k_searcher_account, dim3(1), dim3(1), 0, e->stream, e->d, 1ll, (long long)r.n_exp, (long long)r.n_relax);
+    HIPOK(hipStreamSynchronize(e->stream));
+    if (r.len > cap_cells) return TS_E_CAPACITY;
+    for (int k = 0; k < r.len; k++) { out_xy[2 * k] = cells[(size_t)k] % e->W; out_xy[2 * k + 1] = cells[(size_t)k] / e->W; }
+    return r.len;
+  }
   hipLaunchKernelGGL(k_astar_single, dim3(1), dim3(64), 0, e->stream, e->d, e->P, e->slots, sy * e->W + sx, gy * e->W + gx, soft,
                      ignore_flow, maximum_steps, e->d_status);
   TRY(read_back(e, &e->hm->scratch, e->d_status, sizeof(int)));

@@ -10,7 +10,8 @@
 
 namespace {
 
-enum { DV_DONE = 0, DV_DEFER = 1, DV_OVERFLOW = 2, DV_POOL_FULL = 3, DV_SUSPEND = 4, DV_BAIL = 5 };
+// (DV_HANDOFF: DM_WAVE under the tail rule - a search was abandoned for the host to run, nothing is committed; replan.h)
+enum { DV_DONE = 0, DV_DEFER = 1, DV_OVERFLOW = 2, DV_POOL_FULL = 3, DV_SUSPEND = 4, DV_BAIL = 5, DV_HANDOFF = 6 };
 // Who runs a vehicle's step_decide: one lane without scratch (k_decide_main: bails out as soon as a search is needed), one
 // wavefront (k_replan: every lane the same code on the same values, searches spread over the wave), or one quad of four
 // lanes (k_replan_quad, astar_quad.h: sixteen vehicles per wave, their searches advancing in lockstep)
@@ -125,7 +126,28 @@ constexpr int QLOG = 8;   // searches one step_decide can make in quad mode (bey
 template <int MODE>
 __device__ __forceinline__ int astar_any(const Dev& d, const TsParams& P, AScratch& S, int start_idx, int goal_idx, bool soft,
                                          bool ignore_flow, int maximum_steps, int32_t* out, int out_cap) {
-  if constexpr (MODE == DM_WAVE) return astar_wave(d, P, S, start_idx, goal_idx, soft, ignore_flow, maximum_steps, out, out_cap);
+  if constexpr (MODE == DM_WAVE) {
+    // With a log (a k_replan pass that carries a tail control block, and its re-run): the quads' scheme for the searches the tail
+    // rule applies to - no step limit, on the flow; the bypass searches always run.  Such a search is replayed from the log when an
+    // earlier pass finished it (the host's among them; its path sits in `out`), may be abandoned for the host, and is logged.  Two
+    // of them share an `out` buffer only when the first came back empty, so a replayed path is always intact.
+    if (S.q_log == nullptr || maximum_steps < d.N || ignore_flow)
+      return astar_wave(d, P, S, start_idx, goal_idx, soft, ignore_flow, maximum_steps, out, out_cap);
+    const int k = S.q_replay++;
+    if (k < S.q_done) {
+      S.calls++; S.expansions += S.q_log[3 * k + 1]; S.relaxations += S.q_log[3 * k + 2];
+      return S.q_log[3 * k];
+    }
+    const long long e0 = S.expansions, r0 = S.relaxations;
+    const int r = astar_wave(d, P, S, start_idx, goal_idx, soft, ignore_flow, maximum_steps, out, out_cap, k < QLOG);
+    if (r == AW_HANDOFF) {
+      S.q_start = start_idx; S.q_goal = goal_idx; S.q_soft = soft ? 1 : 0; S.q_out = out; S.q_cap = out_cap;
+      S.q_status = DV_HANDOFF;
+      return -1;
+    }
+    if (k < QLOG && lane_id() == 0) { S.q_log[3 * k] = r; S.q_log[3 * k + 1] = (int)(S.expansions - e0); S.q_log[3 * k + 2] = (int)(S.relaxations - r0); }
+    return r;
+  }
   else if constexpr (MODE == DM_QUAD) {
     const int k = S.q_replay++;
     if (k < S.q_done) {   // finished in an earlier pass: its path already sits in `out`
@@ -140,6 +162,15 @@ __device__ __forceinline__ int astar_any(const Dev& d, const TsParams& P, AScrat
     return -1;
   }
   else return -1;   // (one vehicle per lane never searches: decide_vehicle<DM_LANE> defers before it gets here)
+}
+// reach_strict_wave with its answer in the same log (an entry of its own: a re-run does not flood the component again)
+__device__ __forceinline__ int reach_logged(const Dev& d, AScratch& S, int start, int goal) {
+  if (S.q_log == nullptr) return reach_strict_wave(d, S, start, goal);
+  const int k = S.q_replay++;
+  if (k < S.q_done) return S.q_log[3 * k];
+  const int r = reach_strict_wave(d, S, start, goal);
+  if (k < QLOG && lane_id() == 0) { S.q_log[3 * k] = r; S.q_log[3 * k + 1] = 0; S.q_log[3 * k + 2] = 0; }
+  return r;
 }
 // Phases 3 and 4, once a bypass of `bl` cells (S.BYP) ends on cell `merge_idx` of the path found (S.A[0..la)): the new path is
 // the bypass and what follows that cell (built in S.T, then swapped in as S.P), the path as it was and the bypass are staged
@@ -194,7 +225,7 @@ __device__ bool compute_path_internal_dev(const Dev& d, const TsParams& P, AScra
   const int sx_goal = v.target;
   int la;
   bool unreachable = false;
-  if constexpr (MODE == DM_WAVE) unreachable = v.reach_known && reach_strict_wave(d, S, v.pos, sx_goal) == 2;
+  if constexpr (MODE == DM_WAVE) unreachable = v.reach_known && reach_logged(d, S, v.pos, sx_goal) == 2;
   if (unreachable) {
     // the frontier BFS proved the target unreachable under the strict rules: the search would flood its whole
     // component and return [] (astar_numba.py:239).  Same result, without the flood.
@@ -396,7 +427,7 @@ __device__ int decide_vehicle(const Dev& d, const TsParams& P, int i, AScratch* 
       if (!S) return DV_DEFER;
       v.cooldown = P.pathfinding_cooldown;
       int len;
-      if (!compute_path_internal_dev<MODE>(d, P, *S, v, len)) return MODE == DM_QUAD ? S->q_status : DV_OVERFLOW;
+      if (!compute_path_internal_dev<MODE>(d, P, *S, v, len)) return MODE == DM_QUAD || (MODE == DM_WAVE && S->q_status == DV_HANDOFF) ? S->q_status : DV_OVERFLOW;
       v.newpath = true; v.plen = len; path_changed = true;
     }
     // _recompute_path_on_obstacle (454-504)
@@ -433,7 +464,7 @@ __device__ int decide_vehicle(const Dev& d, const TsParams& P, int i, AScratch* 
       v.cooldown = P.pathfinding_cooldown;
       const bool keep_new = v.newpath;
       int len;
-      if (!compute_path_internal_dev<MODE>(d, P, *S, v, len)) return MODE == DM_QUAD ? S->q_status : DV_OVERFLOW;
+      if (!compute_path_internal_dev<MODE>(d, P, *S, v, len)) return MODE == DM_QUAD || (MODE == DM_WAVE && S->q_status == DV_HANDOFF) ? S->q_status : DV_OVERFLOW;
       if (len > 0) {
         v.newpath = true; v.plen = len; path_changed = true;
         scan_ahead_dev(d, P, S, v, idx_stop, idx_veh, first_cell);

@@ -21,6 +21,7 @@
 #include <string>
 #include <thread>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <condition_variable>
 #include <unordered_map>
@@ -38,6 +39,7 @@
 // One translation unit; this file holds no function of its own.  The order is part of the code: device headers, the host state and
 // its helpers, the host subsystems (each uses what stands above it), the entries of include/trafficsim.h, checkpoints, extensions.
 #include "dev.h"
+#include "astar_host.h"
 #include "astar.h"
 #include "decide.h"
 #include "replan.h"

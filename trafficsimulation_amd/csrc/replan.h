@@ -118,13 +118,58 @@ __device__ __forceinline__ void replan_settle(const Dev& d, const RQueue& q, int
     if (q.owned_list) q.owned_list[atomicAdd(&d.cnt->replan.owned_n, 1)] = i;
   } else if (r == DV_POOL_FULL) q.retry_list[atomicAdd(&d.cnt->replan.retry_n, 1)] = i;
 }
+// The host tail.  A plain pass of run_replans can carry a tail control block (RTail: AScratch::t_ctl
+// and the slot's log): a wave that finds the queue empty counts itself in TailCtl::idle, and a search that sees all but t_max waves
+// of the launch idle (astar_loop's tail rule) is abandoned - decide_vehicle returns DV_HANDOFF without a commit, the wave files
+// the entry, its slot and the search's arguments in the list behind TailCtl and ends, leaving the slot as it is: the paths of the
+// searches this step_decide finished before are in its buffers, their results in its log.  Once the pass has drained, the host
+// runs the listed searches on its own threads (astar_host.h), puts each path where the search would have put it and its result
+// in the log, and k_replan_tail runs those step_decides again from the top on the same slots, replaying the log.  No kernel
+// waits for the host or reads what the host writes while it runs.
+struct RTail { TailCtl* ctl; int32_t* log; int t_max, floor, force, pad_; };   // ctl == nullptr: off; log: 3 * QLOG ints per searcher slot
+__device__ __forceinline__ void tail_bind(const RTail& t, int slot, int grid, AScratch& S) {
+  if (!t.ctl) return;
+  S.q_log = t.log + (size_t)slot * 3 * QLOG;
+  S.t_ctl = t.ctl;
+  // (TS_TAIL_FORCE: every search the rule applies to gives up when it has made `force` expansions, whatever the other waves do)
+  S.t_thr = t.force > 0 ? (int)0x80000000 : grid - t.t_max;
+  S.t_floor = t.force > 0 ? t.force : t.floor;
+  S.t_first = t.force > 0 ? t.force : TAIL_PERIOD;
+}
+// step_decide of queue entry i on this wave's slot, and what follows from its result; false: the wave ends here (a hand-off)
+__device__ __forceinline__ bool replan_entry(const Dev& d, const TsParams& P, AScratch* S, const RQueue& q, int i, int done) {
+  const long long c0 = S->calls, e0 = S->expansions, r0 = S->relaxations;
+  S->q_status = 0; S->q_replay = 0; S->q_done = done;
+  if (S->q_log) {
+    // the policy swaps S->A / S->P / S->T as it goes, and a wave keeps them from entry to entry: with a log every step_decide starts
+    // from the slot's own assignment, so that the re-run finds each replayed path in the buffer its search wrote
+    int32_t* const c = S->BYP - (size_t)5 * S->cap;
+    S->A = c; S->P = c + S->cap; S->T = c + 2 * (size_t)S->cap;
+  }
+  const int r = uni(decide_vehicle<DM_WAVE>(d, P, i, S));
+  if (threadIdx.x == 0) {
+    if (r == DV_HANDOFF) {
+      TailCtl* const t = S->t_ctl;
+      const int k = atomicAdd(&t->n, 1);     // (at most one per wave: the list has a place for every wave of the launch)
+      if (k < t->cap)
+        ((TailEnt*)(t + 1))[k] = TailEnt{i, (int)blockIdx.x, S->q_replay - 1, S->q_start, S->q_goal, S->q_soft,
+                                         (int)(S->q_out - (S->BYP - (size_t)5 * S->cap)), S->q_cap};   // (BYP: the one cell buffer the policy never swaps)
+    }
+    replan_settle(d, q, i, r, S->calls - c0, S->expansions - e0, S->relaxations - r0);
+    if (r == DV_OVERFLOW) atomicExch(&d.cnt->error, TS_E_CAPACITY);
+  }
+  return r != DV_HANDOFF;
+}
 __device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParams& P, AScratch* S, const RQueueFb& q) {
   const int n3 = uni(q.n[3]), n2 = uni(q.n[2]), n1 = uni(q.n[1]), n0 = uni(q.n[0]);
   const int j = wave_pop(&d.cnt->replan.cursor);
   int i, pos = j;
   bool mine = true;
   if (j >= n3 + n2 + n1 + n0) {
-    if (q.fb_waves == 0) return 0;
+    if (q.fb_waves == 0) {
+      if (S->t_ctl && threadIdx.x == 0) atomicAdd(&S->t_ctl->idle, 1);
+      return 0;
+    }
     // this launch's own lists are done: serve the hand-back list (the protocol and its give-up rule: see RQueue)
     if (threadIdx.x == 0) {
       int job = -1;
@@ -169,32 +214,54 @@ __device__ __attribute__((noinline)) int replan_turn(const Dev& d, const TsParam
   else if (j < n3 + n2) __builtin_amdgcn_s_setprio(2);
   else __builtin_amdgcn_s_setprio(0);
 #endif
-  const long long c0 = S->calls, e0 = S->expansions, r0 = S->relaxations;
 #ifdef TS_TRACE_REPLAN
-  const long long tr0 = wall_clock64();
+  const long long tr0 = wall_clock64(), tr_e0 = S->expansions;
   const int tr_bits = replan_cost_bits(d, max(d.active[i], 0));
 #endif
-  const int r = uni(decide_vehicle<DM_WAVE>(d, P, i, S));
+  const bool go_on = replan_entry(d, P, S, q, i, 0);
 #ifdef TS_TRACE_REPLAN
   if (threadIdx.x == 0 && g_rtrace && j < g_rtrace_cap && j < n3 + n2 + n1 + n0)
-    g_rtrace[j] = make_int4((int)(unsigned)tr0, (int)(unsigned)wall_clock64(), (int)(S->expansions - e0), tr_bits | ((int)blockIdx.x << 8));
+    g_rtrace[j] = make_int4((int)(unsigned)tr0, (int)(unsigned)wall_clock64(), (int)(S->expansions - tr_e0), tr_bits | ((int)blockIdx.x << 8));
 #endif
-  if (threadIdx.x == 0) {
-    replan_settle(d, q, i, r, S->calls - c0, S->expansions - e0, S->relaxations - r0);
-    if (r == DV_OVERFLOW) atomicExch(&d.cnt->error, TS_E_CAPACITY);
-  }
-  return 1;
+  return go_on ? 1 : 0;
 }
 
 // Replanning vehicles, one wave per searcher slot: every wave takes the next entry of the queue (RQueue) until it is empty;
 // all 64 lanes run the vehicle's step_decide together and share the work inside the searches.
-TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_replan(Dev d, TsParams P, ASlots sl, RQueueArgs qa) {
+TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_replan(Dev d, TsParams P, ASlots sl, RQueueArgs qa, RTail tl) {
   AScratch S;
   scratch_bind(sl, blockIdx.x, S);
+  tail_bind(tl, blockIdx.x, gridDim.x, S);
   const RQueueFb q = {rqueue_open(d, qa), qa.fb_waves};
   while (uni(replan_turn(d, P, &S, q))) {}
   if (threadIdx.x == 0) sl.slot_epoch[blockIdx.x] = S.epoch;
 }
+// The step_decides whose search the host finished (tl.ctl's list, n entries; see RTail), one per wave, each on the slot it was
+// abandoned on: re-run from the top with the log replayed as far as the host's search, the tail rule off.
+__device__ __attribute__((noinline)) void replan_rerun(const Dev& d, const TsParams& P, AScratch* S, const RQueue& q, int i, int done) {
+  replan_entry(d, P, S, q, i, done);
+}
+TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_replan_tail(Dev d, TsParams P, ASlots sl, RQueueArgs qa, RTail tl, int n) {
+  if ((int)blockIdx.x >= n) return;
+  const TailEnt t = ((const TailEnt*)(tl.ctl + 1))[blockIdx.x];
+  AScratch S;
+  scratch_bind(sl, t.slot, S);
+  S.q_log = tl.log + (size_t)t.slot * 3 * QLOG;
+  const RQueue q = rqueue_open(d, qa);
+  replan_rerun(d, P, &S, q, t.i, t.ord + 1);
+  if (threadIdx.x == 0) sl.slot_epoch[t.slot] = S.epoch;
+}
+// What a pass left unserved because its waves ended on hand-offs (TS_TAIL_FORCE, or fewer waves than t_max): the entries at cursor
+// values [from, total) that are this rank's, appended to `out` (the order of the queue does not touch any result)
+__global__ void k_tail_unserved(Dev d, RQueueArgs qa, int from, int total, int32_t* out, int* out_n) {
+  const int j = from + blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= total) return;
+  const RQueue q = rqueue_open(d, qa);
+  int i, pos;
+  if (rqueue_entry(q, j, i, pos)) out[atomicAdd(out_n, 1)] = i;
+}
+// searches the host ran for a caller of its own (ts_astar under TS_ASTAR_HOST), into the model's counters
+__global__ void k_searcher_account(Dev d, long long calls, long long exp, long long relax) { searcher_account(d, calls, exp, relax); }
 
 // ---- replicated-state multi-GPU mode (ts_set_replan_sharding) ------------------------------------------------------
 // What step_decide changed about a vehicle this rank planned, for the ranks that did not: one fixed record plus the

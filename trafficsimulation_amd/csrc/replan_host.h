@@ -28,6 +28,19 @@ inline QuadRequest quad_request() {
 // clears it replaces took 22 ms for 152 GB and about as long for 165 GB each time).
 int ensure_slots(E* e) {
   if (e->slots_ready) return TS_OK;
+  {
+    // the host tail's switches (TS_TAIL=0: off, the A/B and bisection switch).  Like the quads it carries half-unit costs without a
+    // field-of-view mask.  A pass has a tail worth a snapshot copy when its queue is many times longer than the tail itself.
+    E::TailHost& th = e->tail;
+    const bool can = astar_half_units(e->P) && !e->P.respect_awareness;
+    th.on = env_int("TS_TAIL", 1) != 0 && can;
+    th.t_max = std::max(1, env_int("TS_TAIL_MAX", 32));
+    th.floor = std::max(0, env_int("TS_TAIL_FLOOR", 65536));
+    th.threads = env_int("TS_TAIL_THREADS", 0);
+    th.force = std::max(0, env_int("TS_TAIL_FORCE", 0));
+    th.min_queue = env_int("TS_TAIL_MIN_QUEUE", 16 * th.t_max);
+    th.astar_host = env_int("TS_ASTAR_HOST", 0) != 0 && can;
+  }
   // (the quad searcher, astar_quad.h: on unless TS_QUAD=0; it carries half-unit costs without a field-of-view mask)
   e->quad_on = !(getenv("TS_QUAD") && atoi(getenv("TS_QUAD")) == 0) && astar_half_units(e->P) && !e->P.respect_awareness;
   ASlots& T = e->slots;
@@ -267,6 +280,126 @@ int replan_pass_done(E* e) {
   return e->hm->error == TS_E_CAPACITY ? fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers") : TS_OK;
 }
 
+// ---- the host tail (replan.h RTail) -------------------------------------------------------------
+static_assert(ahost::PEN_SHIFT == AMAP_PEN_SHIFT && ahost::INF == A_INF, "astar_host.h reads k_amap_build's words");
+inline ahost::Costs tail_costs(const TsParams& P) {
+  return ahost::Costs{(int)((double)P.turn_penalty * 2.0), (int)((double)P.contraflow_penalty * 2.0), (int)((double)P.obstacle_penalty_stop * 2.0),
+                      {0, (int)(P.road_type_penalty_r1 * 2.0), (int)(P.road_type_penalty_r2 * 2.0), (int)(P.road_type_penalty_r3 * 2.0)},
+                      P.turn_penalty_enabled != 0, P.road_type_penalties_enabled != 0};
+}
+inline ahost::Map tail_map(const E* e) {
+  return ahost::Map{e->tail.h_amap, e->W, e->H, e->d.W8, e->N, (uint32_t)std::max(e->d.n_nodes, 1), e->slots.heap_cap};
+}
+inline size_t amap_words(const E* e) { return (size_t)e->d.W8 * e->d.H8 * 64; }
+// the pool (created on first use: sixteen threads at the most, never more than this process may run on) and the side stream
+int tail_setup(E* e) {
+  E::TailHost& th = e->tail;
+  if (!th.pool) th.pool = new ahost::Pool(th.threads > 0 ? std::min(th.threads, 64) : ahost::pool_default_threads());
+  if (!th.stream) {
+    HIPOK(hipStreamCreateWithFlags(&th.stream, hipStreamNonBlocking));
+    HIPOK(hipEventCreateWithFlags(&th.ev_go, hipEventDisableTiming));
+    HIPOK(hipEventCreateWithFlags(&th.ev_copied, hipEventDisableTiming));
+  }
+  if (th.cap_amap < amap_words(e)) {
+    HIPOK(hipStreamSynchronize(th.stream));
+    HIPOK(regrow_pinned(&th.h_amap, amap_words(e)));
+    th.cap_amap = amap_words(e);
+  }
+  return TS_OK;
+}
+// Dev::amap as the engine's stream leaves it at this point -> the pinned copy, on the side stream (it travels under whatever the
+// engine's stream runs next); tail_snapshot_wait: the copy has landed
+int tail_snapshot_begin(E* e) {
+  E::TailHost& th = e->tail;
+  TRY(tail_setup(e));
+  HIPOK(hipEventRecord(th.ev_go, e->stream));
+  HIPOK(hipStreamWaitEvent(th.stream, th.ev_go, 0));
+  HIPOK(hipMemcpyAsync(th.h_amap, e->d.amap, amap_words(e) * 8, hipMemcpyDeviceToHost, th.stream));
+  HIPOK(hipEventRecord(th.ev_copied, th.stream));
+  return TS_OK;
+}
+int tail_snapshot_wait(E* e) {
+  HIPOK(hipEventSynchronize(e->tail.ev_copied));
+  return TS_OK;
+}
+// a pass with a tail is about to be launched: its control block (zeroed), the slots' logs, the snapshot copy
+int tail_begin(E* e, RTail& tl) {
+  E::TailHost& th = e->tail;
+  if (!th.ctl) {
+    const size_t S = (size_t)e->slots.n_slots;
+    uint8_t* raw = nullptr;
+    HIPOK(dalloc(e, &raw, sizeof(TailCtl) + S * sizeof(TailEnt)));
+    th.ctl = (TailCtl*)raw;
+    HIPOK(dalloc(e, &th.log, S * 3 * QLOG));
+    const TailCtl first = {0, 0, e->slots.n_slots, 0};
+    HIPOK(hipMemcpy(th.ctl, &first, sizeof(first), hipMemcpyHostToDevice));
+  }
+  HIPOK(hipMemsetAsync(th.ctl, 0, 2 * sizeof(int), e->stream));     // idle, n
+  TRY(tail_snapshot_begin(e));
+  tl = RTail{th.ctl, th.log, th.t_max, th.floor, th.force, 0};
+  return TS_OK;
+}
+// ... and has drained (replan_pass_done): the searches its waves abandoned run on the pool, their paths and results go where the
+// device would have put them, and k_replan_tail runs those step_decides again.  *handed: how many there were.
+int tail_finish(E* e, const RQueueArgs& qa, const RTail& tl, double t_launch, int* handed) {
+  E::TailHost& th = e->tail;
+  const TsParams& P = e->P;
+  const double t_pass = now_ms();
+  *handed = 0;
+  HIPOK(hipStreamWaitEvent(e->stream, th.ev_copied, 0));     // (whatever rebuilds the snapshot next waits for the copy)
+  TailCtl h{};
+  TRY(read_back(e, &h, th.ctl, sizeof(h)));
+  const int n = std::min(h.n, h.cap);
+  if (n <= 0) return TS_OK;
+  std::vector<TailEnt> list((size_t)n);
+  TRY(read_back(e, list.data(), th.ctl + 1, (size_t)n * sizeof(TailEnt)));
+  TRY(tail_snapshot_wait(e));
+  const ahost::Map map = tail_map(e);
+  const ahost::Costs costs = tail_costs(P);
+  std::vector<std::unique_ptr<int32_t[]>> out((size_t)n);
+  std::vector<int32_t> res((size_t)n * 3);
+  for (int k = 0; k < n; k++) out[(size_t)k].reset(new int32_t[(size_t)std::max(list[(size_t)k].out_cap, 1)]);
+  const double t_host = now_ms();
+  th.pool->run(n, [&](ahost::Searcher& s, int k) {
+    const TailEnt& t = list[(size_t)k];
+    const ahost::Result r = s.run(map, costs, ahost::Query{t.start, t.goal, t.soft != 0, false, 0x7FFFFFFF}, out[(size_t)k].get(), t.out_cap);
+    res[3 * (size_t)k] = r.len; res[3 * (size_t)k + 1] = r.n_exp; res[3 * (size_t)k + 2] = r.n_relax;
+  });
+  const double t_up = now_ms();
+  for (int k = 0; k < n; k++) {
+    const TailEnt& t = list[(size_t)k];
+    const int len = res[3 * (size_t)k];
+    if (len > 0) HIPOK(hipMemcpyAsync(e->slots.cells + (size_t)t.slot * ((size_t)5 * e->slots.cap + 3 * MAXB) + t.out_off, out[(size_t)k].get(), (size_t)len * 4, hipMemcpyHostToDevice, e->stream));
+    HIPOK(hipMemcpyAsync(th.log + ((size_t)t.slot * QLOG + t.ord) * 3, &res[3 * (size_t)k], 12, hipMemcpyHostToDevice, e->stream));
+  }
+  LAUNCH(e, PK_REPLAN, n, k_replan_tail, dim3(n), dim3(64), e->d, P, e->slots, qa, tl, n);
+  const int rc = replan_pass_done(e);       // (the stream drains here: the staged paths and results are no longer read)
+  const double t_end = now_ms();
+  th.passes++; th.searches += n;
+  host_prof(e, PH_REPLAN_TAIL, t_end - t_pass, n);
+  if (getenv("TS_DEBUG_REPLAN")) {
+    long long ex = 0, ex_max = 0;
+    for (int k = 0; k < n; k++) { ex += res[3 * (size_t)k + 1]; ex_max = std::max<long long>(ex_max, res[3 * (size_t)k + 1]); }
+    fprintf(stderr, "[replan] tick %lld: host tail: %.2f ms to the hand-off, %d searches handed over (%lld expansions, the longest %lld), "
+            "host %.2f ms on %d threads, re-run %.2f ms\n", (long long)e->C.step_count, t_pass - t_launch, n, ex, ex_max, t_up - t_host,
+            th.pool->threads(), t_end - t_up);
+  }
+  *handed = n;
+  return rc;
+}
+// what the pass left in the queue because its waves ended on hand-offs, into tail.unserved; *left: how many entries
+int tail_unserved(E* e, const RQueueArgs& qa, int from, int total, int* left) {
+  E::TailHost& th = e->tail;
+  *left = 0;
+  if (from >= total) return TS_OK;
+  TRY(grow(e, &th.unserved, th.cap_unserved, (size_t)(total - from), (size_t)(total - from) * 2));
+  HIPOK(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
+  hipLaunchKernelGGL(k_tail_unserved, dim3(nblk(total - from)), dim3(BLK), 0, e->stream, e->d, qa, from, total, th.unserved, e->d_status);
+  TRY(read_back(e, &e->hm->scratch, e->d_status, sizeof(int)));
+  *left = e->hm->scratch;
+  return TS_OK;
+}
+
 // The quad pass of a big queue (see run_replans): the classes in TS_QUAD_CLASSES go to k_replan_quad while k_replan serves the
 // others and the quads' hand-backs beside it (RQueue, replan.h).  What neither got to is queued again in list 0.
 int run_quad_pass(E* e) {
@@ -300,7 +433,7 @@ int run_quad_pass(E* e) {
   const int side_waves = env_int("TS_QUAD_SIDE_WAVES", e->quad_last_fb < 0 || e->quad_last_fb > 4096 ? 512 : 384);
   const int wgrid = std::min(e->side_slots, std::max(std::min(nw, e->side_slots), nq > 0 ? side_waves : 1));
   qa.class_mask = 15 & ~quad_mask; qa.fb_waves = qgrid;
-  if (nw > 0 || nq > 0) hipLaunchKernelGGL(k_replan, dim3(wgrid), dim3(64), 0, st, d, P, e->slots, qa);
+  if (nw > 0 || nq > 0) hipLaunchKernelGGL(k_replan, dim3(wgrid), dim3(64), 0, st, d, P, e->slots, qa, RTail{});   // (no host tail beside the quads)
   if (nq > 0) HIPOK(hipStreamWaitEvent(st, e->quad_ev1, 0));
   prof_end(e, tok);
   struct { int handback_n, quad_cursor, handback_claimed, quad_waves_done; } hb{};   // (the four words, as in DevCnt)
@@ -414,9 +547,21 @@ int run_replans(E* e) {   // e->hm->replan = the queue as k_decide_main left it
     }
     HIPOK(hipMemsetAsync(tr_buf, 0, (size_t)std::min(n, tr_cap) * sizeof(int4), e->stream));
 #endif
-    LAUNCH(e, PK_REPLAN, n, k_replan, dim3(grid), dim3(64), d, P, e->slots, qa);
+    // the host tail: a pass whose queue is long against the tail carries a control block, and the snapshot copy travels under it
+    // (TS_TAIL_FORCE: every pass does)
+    const E::TailHost& th = e->tail;
+    const bool tail_pass = th.on && (th.force > 0 || n >= th.min_queue);
+    RTail tail{};
+    if (tail_pass) TRY(tail_begin(e, tail));
+    LAUNCH(e, PK_REPLAN, n, k_replan, dim3(grid), dim3(64), d, P, e->slots, qa, tail);
     const double tl = now_ms();
-    const int rc = replan_pass_done(e);
+    int rc = replan_pass_done(e);
+    int handed = 0, left = 0;
+    if (tail_pass && rc == TS_OK) {
+      rc = tail_finish(e, qa, tail, tl, &handed);
+      // (waves that end on a hand-off can leave entries in the queue: with TS_TAIL_FORCE, or where the launch has no more waves than t_max)
+      if (rc == TS_OK) rc = tail_unserved(e, qa, std::min(hm.replan.cursor, n), n, &left);
+    }
 #ifdef TS_TRACE_REPLAN
     if (n >= 1000) {
       std::vector<int4> h((size_t)std::min(n, tr_cap));
@@ -436,11 +581,20 @@ int run_replans(E* e) {   // e->hm->replan = the queue as k_decide_main left it
     TRY(rc);
     const int retry = hm.replan.retry_n;
     if (getenv("TS_DEBUG_REPLAN"))
-      fprintf(stderr, "[replan] tick %lld: %d entries (classes %d/%d/%d/%d) on %d searchers, retry=%d, %.2f ms\n", (long long)e->C.step_count,
-              n, hm.replan.class_n[0], hm.replan.class_n[1], hm.replan.class_n[2], hm.replan.class_n[3], grid, retry, now_ms() - tl);
-    if (retry == 0) break;
-    // the path pool filled up: make room (GC, then growth) and run the entries that could not commit again
-    TRY(requeue_in_list0(e, nullptr, 0, retry));
+      fprintf(stderr, "[replan] tick %lld: %d entries (classes %d/%d/%d/%d) on %d searchers, retry=%d, handed to the host %d, left in the queue %d, %.2f ms\n",
+              (long long)e->C.step_count, n, hm.replan.class_n[0], hm.replan.class_n[1], hm.replan.class_n[2], hm.replan.class_n[3], grid, retry,
+              handed, left, now_ms() - tl);
+    if (handed > 0 && left == 0) {
+      // a wave that ends on a hand-off does not draw past the end of the queue as every other wave does once: the cursor is put
+      // where a pass without hand-offs leaves it, so that the counters a checkpoint stores do not depend on how many there were
+      hm.replan.cursor = n + grid;
+      HIPOK(hipMemcpyAsync(&d.cnt->replan.cursor, &hm.replan.cursor, sizeof(int), hipMemcpyHostToDevice, e->stream));
+      HIPOK(hipStreamSynchronize(e->stream));
+    }
+    if (retry == 0 && left == 0) break;
+    // the path pool filled up: make room (GC, then growth) and run the entries that could not commit again - with what a pass
+    // that ended on hand-offs left in the queue
+    TRY(requeue_in_list0(e, e->tail.unserved, left, retry));
   }
   d.pool_cap_words = e->pool_cap;
   return TS_OK;
