@@ -39,7 +39,7 @@ bool load(const char* path, Case& c) {
     ok = read_all(f, c.amap.data(), c.amap.size() * 8) && read_all(f, c.queries.data(), c.queries.size() * 4) &&
          read_all(f, c.off.data(), c.off.size() * 4) && read_all(f, c.xy.data(), c.xy.size() * 4);
     c.map = ahost::Map{c.amap.data(), c.W, c.H, W8, c.W * c.H, (uint32_t)h[3], h[4]};
-    c.costs = ahost::Costs{h[7], h[8], h[9], {0, h[10], h[11], h[12]}, h[5] != 0, h[6] != 0};
+    c.costs = ahost::Costs{HalfCosts{h[7], h[8], 0, h[9], h[10], h[11], h[12]}, h[5] != 0, h[6] != 0};   // (veh2: in the snapshot words)
     ok = ok && c.off[0] == 0 && c.off[c.nq] == h[14];
   }
   fclose(f);

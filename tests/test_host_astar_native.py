@@ -1,7 +1,8 @@
 """The host searcher (csrc/astar_host.h: the wave searcher's algorithm as a sequential host function, and its thread pool) on the CPU:
 tests/native/astar_host_check.cpp runs the 520 queries of tests/golden/astar_kats.npz - once single-threaded, eight times each on a
 pool of four threads - and every path must equal the reference's cell for cell.  The A* snapshot words it searches on are built
-here in numpy from their documented layout (csrc/dev.h Dev::amap, csrc/kernels.h k_amap_build).  The program is built and run
+here in numpy from their documented layout (the comment in csrc/astar_words.h; this restatement is the independent check and
+does not read that header).  The program is built and run
 three times: plain, under AddressSanitizer + UndefinedBehaviorSanitizer, and under ThreadSanitizer, as a plain executable."""
 import os
 import subprocess
@@ -12,7 +13,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "astar_host_check.cpp")
 INC = os.path.join(HERE, "..", "trafficsimulation_amd", "csrc")
-HDR = os.path.join(INC, "astar_host.h")
+HDRS = [os.path.join(INC, h) for h in ("astar_host.h", "astar_words.h", "arena_epochs.h")]
 BUILD = os.path.join(HERE, "native", "_build")
 GOLDEN = os.path.join(HERE, "golden")
 
@@ -85,7 +86,7 @@ def cases(tmp_path_factory):
 def test_host_searcher_reproduces_the_reference_paths(cases, name, flags):
     os.makedirs(BUILD, exist_ok=True)
     exe = os.path.join(BUILD, f"astar_host_check_{name}")
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(f) for f in [SRC, *HDRS]):
         subprocess.run(["g++", "-std=c++17", "-pthread", *flags, "-I", INC, "-o", exe, SRC], check=True)
     p = subprocess.run([exe, *cases], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stdout.startswith("astar host ok: 520 queries"), (p.stdout + p.stderr)[-2000:]

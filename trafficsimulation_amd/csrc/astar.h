@@ -18,19 +18,18 @@
 //     8 x 8-tiled order (no hashing, no probing, never outgrown), stamped with the searcher's epoch instead of the
 //     reference's O(W*H) initialisation per call (119-122).  A searcher's table is N x 8 bytes; the 288 GB of HBM
 //     hold several hundred of them even at 4096^2;
-//   * the maps a search reads are a per-tick snapshot in the same tiled order (Dev::amap: static byte + occupied +
-//     red, 2 bytes per cell = one 128-byte line per tile), so the neighbours of a cell usually share its line;
+//   * the maps a search reads are a per-tick snapshot in the same tiled order (Dev::amap; the word, the record and the
+//     half-unit costs: astar_words.h), so the neighbours of a cell usually share its line;
 //   * everything an expansion needs from HBM (5 map entries, 5 table records, 4 densities) is requested as soon as
 //     the popped cell is known and travels while the sift-down works in LDS: one memory round trip per expansion.
 //
 #pragma once
 #include <type_traits>
 #include "dev.h"
-#include "arena_epochs.h"
+#include "astar_words.h"
 
 namespace {
 
-constexpr int A_INF = 0x3F3F3F3F;
 constexpr int MAXB = 64;  // longest contraflow bypass (VEHICLE_MAX_CONTRAFLOW_*_STEPS <= 64)
 
 // heap slots (and dir bytes) a searcher keeps in LDS: 6.2 KB, twenty-four searchers per CU (736 entries already cost occupancy) (the deepest heap seen on
@@ -48,14 +47,14 @@ constexpr int LDS_HEAP = TS_LDS_HEAP;
 #endif
 #define TS_REPLAN_OCC __attribute__((amdgpu_waves_per_eu(TS_REPLAN_WAVES, 8)))
 struct __attribute__((aligned(8))) HQ { int32_t f, i; };             // heap entry: f_arr, i_arr (g_arr / s_arr: see above)
-struct __attribute__((aligned(8))) TEnt { int32_t dist; uint32_t meta; };   // meta = stamp << 14 | steps << 2 | came-from direction
+struct __attribute__((aligned(8))) TEnt { int32_t dist; uint32_t meta; };   // k_replan's table record (astar_words.h)
 // The stamps run over W_EPOCH_LO + 1 .. W_EPOCH_LO + T_STAMP_MAX (arena_epochs.h: a range the quads' records, which can lie in the
 // same memory, never look live in); T_STAMP_MAX = searches between two wraps.
 // (TS_DEBUG_STAMP_MAX: a test build that wraps the searcher tables' epochs every few hundred searches instead of every 65 535)
 #ifndef TS_DEBUG_STAMP_MAX
 #define TS_DEBUG_STAMP_MAX 0xFFFFu
 #endif
-constexpr uint32_t T_STAMP_SHIFT = W_STAMP_SHIFT, T_STEPS_MASK = 0xFFF, T_STAMP_MAX = TS_DEBUG_STAMP_MAX;
+constexpr uint32_t T_STAMP_SHIFT = W_STAMP_SHIFT, T_STAMP_MAX = TS_DEBUG_STAMP_MAX;
 constexpr int A_STEPS_MAX = (int)T_STEPS_MASK - 1;   // largest binding step limit a search can carry (a limit >= N never binds)
 
 // (slot LDS_HEAP of both arrays is a spare no search reads: a lane-predicated store sends its idle lanes there instead of
@@ -107,6 +106,8 @@ struct TailCtl { int idle, n, cap, pad_; };     // TailEnt list[cap] follows
 constexpr int TAIL_PERIOD = 4096;     // fresh expansions between two looks at TailCtl::idle
 constexpr int TAIL_GAVE_UP = -1;      // astar_loop's heap size once the search has given up
 
+// ints in a searcher slot's cell buffers (scratch_bind, quad_scratch_bind): A, P, T, PO, PD of `cap` cells each, then BYP, OV, DV of MAXB
+__host__ __device__ constexpr size_t slot_cell_ints(size_t cap) { return 5 * cap + 3 * MAXB; }
 
 struct ASlots {
   int n_slots, heap_cap, cap, use_reach;
@@ -114,7 +115,7 @@ struct ASlots {
   TEnt* tab;
   HQ* gq;
   int8_t* gd;
-  int32_t* cells;        // per slot: 5 * cap + 3 * MAXB
+  int32_t* cells;        // per slot: slot_cell_ints(cap)
   uint32_t* slot_epoch;
   // the one way a record of these tables could pass for a quad's live one once the arena changes hands without a clear: a dist
   // word of big_thr (2^24; TS_DEBUG_ARENA_BIGDIST) or more.  A search that stores one sets *big_flag, and the next hand-over clears.
@@ -127,7 +128,7 @@ __device__ __forceinline__ void scratch_bind(const ASlots& t, int slot, AScratch
   S.gq = t.gq + (size_t)slot * (size_t)(t.heap_cap - LDS_HEAP);
   S.gd = t.gd + (size_t)slot * (size_t)(t.heap_cap - LDS_HEAP);
   S.heap_cap = t.heap_cap;
-  int32_t* c = t.cells + (size_t)slot * ((size_t)5 * t.cap + 3 * MAXB);
+  int32_t* c = t.cells + (size_t)slot * slot_cell_ints((size_t)t.cap);
   S.A = c; S.P = c + t.cap; S.T = c + 2 * (size_t)t.cap; S.PO = c + 3 * (size_t)t.cap; S.PD = c + 4 * (size_t)t.cap;
   S.BYP = c + 5 * (size_t)t.cap; S.OV = S.BYP + MAXB; S.DV = S.OV + MAXB;
   S.cap = t.cap;
@@ -246,27 +247,13 @@ __device__ __forceinline__ uint32_t next_epoch(const Dev& d, AScratch& S) {
   return e;
 }
 
-// what a search keeps in registers while its loop runs (d, P and S themselves live in scratch memory behind references)
-// Half units carry the search costs exactly iff every penalty is a non-negative multiple of 0.5 of moderate size (the
-// reference's defaults are).  Host (k_amap_build's penalty bits) and device (astar_wave) decide with the same function.
-__host__ __device__ inline bool astar_half_units(const TsParams& P) {
-  const double pp[7] = {(double)P.turn_penalty, (double)P.contraflow_penalty, (double)P.obstacle_penalty_vehicle,
-                        (double)P.obstacle_penalty_stop, (double)P.road_type_penalty_r1, (double)P.road_type_penalty_r2,
-                        (double)P.road_type_penalty_r3};
-  bool half = true;
-  for (int k = 0; k < 7; k++) half = half && pp[k] >= 0.0 && pp[k] < 1048576.0 && (double)(int)(pp[k] * 2.0) == pp[k] * 2.0;
-  half = half && P.dynamic_penalty_scale >= 0.0 && P.dynamic_penalty_scale <= 64.0;   // (2 (g + 1) + penalties stays below 2^31 for every g < INF)
-  // the per-cell vehicle penalty travels in 22 bits of the map snapshot (density <= 1)
-  half = half && (double)P.obstacle_penalty_vehicle * (1.0 + (double)P.dynamic_penalty_scale) * 2.0 < 2097152.0;
-  return half;
-}
 // obstacle penalty of an occupied cell under VEHICLE_DYNAMIC_PENALTIES (astar_numba.py:203-206): int(veh_pen * (1 + scale * density))
 __device__ __forceinline__ double occ_penalty_dyn(double veh_pen, double dyn_scale, float dens) {
 #pragma clang fp contract(off)
   return __builtin_trunc(veh_pen * (1.0 + dyn_scale * (double)dens));
 }
-constexpr int AMAP_PEN_SHIFT = 10;   // Dev::amap low word: bits 0-9 flags, bits 10-31 the vehicle penalty in half units (HALF searches)
 
+// what a search keeps in registers while its loop runs (d, P and S themselves live in scratch memory behind references)
 struct ACtx {
   int W, H, W8, N, lane;
   u64 w_magic;
@@ -283,7 +270,7 @@ struct ACtx {
   uint32_t epoch;
   bool soft, ignore_flow, limited, turn_on, rt_on, dens_on;
   double turn_pen, contra_pen, veh_pen, stop_pen, dyn_scale, rt1, rt2, rt3;
-  int turn2, contra2, veh2, stop2, rt2_1, rt2_2, rt2_3;     // the same in half units (valid when `half`)
+  HalfCosts hc;           // the same in half units (valid when `half`)
   bool half;
   // per search, 32 bits (n_exp <= n_relax + 1: every pop but the first was pushed by a relaxation; the loop gives up with
   // AL_OVERFLOW before n_relax can wrap); n_exp_spill: expansions made while part of the heap sat in HBM
@@ -420,7 +407,7 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
         hq_put_if<SPILL>(gq, onp | put_x, put_x ? abs_end : (abs_l - 1) >> 1, put_x ? x : mine);
         if (!e_loaded) {                   // the first window is done: the map entries have had time to arrive
           const uint32_t r_l = (uint32_t)(am_l >> 32);
-          e_l = ld8(tab, r_l != 0xFFFFFFFFu ? r_l : 0u);
+          e_l = ld8(tab, r_l != AM_NO_NODE ? r_l : 0u);
           e_loaded = true;
         }
         if (done) break;
@@ -430,7 +417,7 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
     wave_mem_sync();
     KP(2);
     const uint32_t a_l = (uint32_t)am_l, r_l = (uint32_t)(am_l >> 32);
-    const bool node_l = r_l != 0xFFFFFFFFu;
+    const bool node_l = r_l != AM_NO_NODE;
     if (!e_loaded) e_l = ld8(tab, node_l ? r_l : 0u);     // (the heap held a single entry: no sift-down happened)
     if (cur == goal_xy) {
       // walk came_from back to the start, filling the output from its far end, then slide it to the front
@@ -442,7 +429,7 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
         if (lane == 0) outg[out_cap - 1 - len] = c;
         len++;
         const uint32_t pr = (uint32_t)(C.amap[C.tile_ix(px, py)] >> 32);
-        const int dd = (int)((tab[pr] >> 32) & 3u);
+        const int dd = (int)((tab[pr] >> 32) & T_DIR_MASK);
         px -= (dd == 1) - (dd == 3); py -= (dd == 0) - (dd == 2);
         c = py * W + px;
       }
@@ -477,8 +464,8 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
       const int idle = uni(__hip_atomic_load(C.tail_idle, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
       if ((idle >= C.tail_thr) & (made >= C.tail_floor)) { heap_size = TAIL_GAVE_UP; fresh = false; }
     }
-    const int steps = C.limited ? (int)((m_c >> 2) & T_STEPS_MASK) : 0;
-    const uint32_t bits = (uint32_t)rl((int)a_l, 4) & 15u;
+    const int steps = C.limited ? (int)((m_c >> T_STEPS_SHIFT) & T_STEPS_MASK) : 0;
+    const uint32_t bits = (uint32_t)rl((int)a_l, 4) & AM_DIRS_MASK;
     // ---- lane dd < 4 evaluates neighbour dd from what was fetched before the sift-down -------------------------
     // HALF: every penalty is a non-negative multiple of 0.5 (the reference's defaults are), so the reference's float `ng`
     // is carried exactly as an integer count of half units: ng < dist  <=>  ng2 < 2 dist, int(ng) = ng2 >> 1,
@@ -489,8 +476,8 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
     {
       const uint32_t m_l = (uint32_t)(e_l >> 32);
       const int dist_l = (m_l >> T_STAMP_SHIFT) == epoch ? (int)(uint32_t)e_l : A_INF;
-      bool n_occ = ((a_l >> 8) & 1u) != 0u, n_stop = ((a_l >> 9) & 1u) != 0u;
-      const bool n_road = ((a_l >> 4) & 1u) != 0u;
+      bool n_occ = ((a_l >> AM_OCC_BIT) & 1u) != 0u, n_stop = ((a_l >> AM_RED_BIT) & 1u) != 0u;
+      const bool n_road = ((a_l >> AM_ROAD_BIT) & 1u) != 0u;
       if constexpr (FOV) {
         // compute_fov_inplace (astar_numba.py:29-50): the neighbour is seen iff a straight run of road cells joins it to
         // the line of 2 * awareness - 1 cells through the START cell perpendicular to that run's direction
@@ -501,19 +488,19 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
                           (band_y & (dxs >= 0) & (run_lf > dxs)) | (band_y & (dxs <= 0) & (run_rt > -dxs));
         n_occ &= seen; n_stop &= seen;
       }
-      const uint32_t rt = (a_l >> 6) & 3u;
+      const uint32_t rt = (a_l >> AM_RT_SHIFT) & AM_RT_MASK;
       const bool flow = ((bits >> dd_l) & 1u) != 0u;
       const bool turn = C.turn_on & (prev_dir != -1) & (dd_l != prev_dir);
       bool cheaper;
       // (selects, not branches: a killed neighbour's cost is simply not used)
       if constexpr (HALF) {
         int n2 = 2 * (g + 1);
-        n2 += turn ? C.turn2 : 0;
-        n2 += flow ? 0 : C.contra2;
-        const int occ2 = (int)(a_l >> AMAP_PEN_SHIFT);     // k_amap_build: veh2, or the density-dependent penalty of this cell
+        n2 += turn ? C.hc.turn2 : 0;
+        n2 += flow ? 0 : C.hc.contra2;
+        const int occ2 = (int)(a_l >> AM_PEN_SHIFT);     // k_amap_build: veh2, or the density-dependent penalty of this cell
         n2 += n_occ ? occ2 : 0;
-        n2 += n_stop ? C.stop2 : 0;
-        const int rtp = (rt == 1u ? C.rt2_1 : 0) | (rt == 2u ? C.rt2_2 : 0) | (rt == 3u ? C.rt2_3 : 0);   // (a chain of ?: becomes nested branches)
+        n2 += n_stop ? C.hc.stop2 : 0;
+        const int rtp = (rt == 1u ? C.hc.rt2_1 : 0) | (rt == 2u ? C.hc.rt2_2 : 0) | (rt == 3u ? C.hc.rt2_3 : 0);   // (a chain of ?: becomes nested branches)
         n2 += (C.rt_on & n_road) ? rtp : 0;
         ng2_l = n2;
         cheaper = n2 < 2 * dist_l;
@@ -546,7 +533,7 @@ __device__ __forceinline__ int astar_loop(ACtx& C, int& heap_size) {
       // (every lane stores: the idle ones to the table's spare record and the spare dir byte - their dist words count for
       // `big` like any other: the spare record lies in the arena too)
       C.big = max(C.big, (uint32_t)ngi_l);
-      st8(tab, ok_l ? r_l : tab_spare, (u64)(uint32_t)ngi_l | ((u64)(stamp | (C.limited ? (uint32_t)(steps + 1) << 2 : 0u) | (uint32_t)dd_l) << 32));
+      st8(tab, ok_l ? r_l : tab_spare, (u64)(uint32_t)ngi_l | ((u64)(stamp | (C.limited ? (uint32_t)(steps + 1) << T_STEPS_SHIFT : 0u) | (uint32_t)dd_l) << 32));
       hd_put_if<SPILL>(gd, ok_l, heap_size + __builtin_popcount(relax & below_l), dd_l);
       KP(5);
       do {
@@ -608,8 +595,7 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
   {
     // half units carry the costs exactly iff every penalty is a non-negative multiple of 0.5 of moderate size
     C.half = astar_half_units(P);
-    C.turn2 = (int)(C.turn_pen * 2.0); C.contra2 = (int)(C.contra_pen * 2.0); C.veh2 = (int)(C.veh_pen * 2.0); C.stop2 = (int)(C.stop_pen * 2.0);
-    C.rt2_1 = (int)(C.rt1 * 2.0); C.rt2_2 = (int)(C.rt2 * 2.0); C.rt2_3 = (int)(C.rt3 * 2.0);
+    C.hc = half_costs(P);
   }
   C.n_relax = 0; C.n_exp_spill = 0; C.max_heap = 0; C.big = 0;     // (n_exp: with the tail rule's switches below)
   C.tab_spare = (uint32_t)uni(max(d.n_nodes, 1));
@@ -631,7 +617,7 @@ __device__ int astar_wave(const Dev& d, const TsParams& P, AScratch& S, int star
   const int sx = C.sx, sy = C.sy;
   if (C.lane == 0) {
     const uint32_t sr = (uint32_t)(C.amap[C.tile_ix(sx, sy)] >> 32);
-    if (sr != 0xFFFFFFFFu) C.tab[sr] = (u64)0u | ((u64)(C.epoch << T_STAMP_SHIFT) << 32);    // dist 0, steps 0
+    if (sr != AM_NO_NODE) C.tab[sr] = (u64)0u | ((u64)(C.epoch << T_STAMP_SHIFT) << 32);    // dist 0, steps 0
     g_lq[0] = hq_pack(abs(sx - C.gx) + abs(sy - C.gy), xy_pack(sx, sy));
     g_ld[0] = -1;
   }
@@ -691,7 +677,7 @@ __device__ int reach_strict_wave(const Dev& d, AScratch& S, int start, int goal)
     cell_xy(W, w_magic, start, sx, sy);
     ring[0] = start;
     const uint32_t sr = (uint32_t)(amap[tix(W8, sx, sy)] >> 32);
-    if (sr != 0xFFFFFFFFu) tabw[2 * (size_t)sr + 1] = stamp;
+    if (sr != AM_NO_NODE) tabw[2 * (size_t)sr + 1] = stamp;
   }
   __syncthreads();
   unsigned head = 0, tail = 1;
@@ -702,7 +688,7 @@ __device__ int reach_strict_wave(const Dev& d, AScratch& S, int start, int goal)
     head = min(tail, head + 64u);
     int cx = 0, cy = 0;
     if (c >= 0) cell_xy(W, w_magic, c, cx, cy);
-    const uint32_t bits = c >= 0 ? (uint32_t)amap[tix(W8, cx, cy)] & 15u : 0u;
+    const uint32_t bits = c >= 0 ? (uint32_t)amap[tix(W8, cx, cy)] & AM_DIRS_MASK : 0u;
     for (int dd = 0; dd < 4; dd++) {
       int n = -1;
       if (bits & (1u << dd)) {
@@ -710,7 +696,7 @@ __device__ int reach_strict_wave(const Dev& d, AScratch& S, int start, int goal)
         if (nx >= 0 && nx < W && ny >= 0 && ny < H) {
           const u64 an = amap[tix(W8, nx, ny)];
           const uint32_t rn = (uint32_t)(an >> 32);
-          if (((uint32_t)an & 0x300u) == 0u && rn != 0xFFFFFFFFu &&
+          if (((uint32_t)an & AM_BLOCKED) == 0u && rn != AM_NO_NODE &&
               __hip_atomic_exchange(&tabw[2 * (size_t)rn + 1], stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != stamp)
             n = ny * W + nx;
         }

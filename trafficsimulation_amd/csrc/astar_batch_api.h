@@ -71,12 +71,7 @@ int ts_astar_batch(ts_handle e, int32_t n, const int32_t* queries, int64_t* tota
     return TS_OK;
   }
   // "evaluated on the engine's current maps": density planes and snapshot once for the whole batch, dropped afterwards (ts_astar)
-  TRY(ensure_density(e, e->d.occ));
-  e->density_valid = false;
-  TRY(ensure_slots(e));
-  e->amap_valid = false;
-  TRY(ensure_amap(e));
-  e->amap_valid = false;
+  TRY(search_maps_now(e));
   // While the quads hold the shared part of the table arena only the side waves' slots are usable: a query batch never
   // clears or moves the arena (and so never touches the quads' tables or epochs)
   const int usable = (e->arena_shared && e->arena_quad) ? std::max(1, std::min(e->side_slots, e->slots.n_slots)) : e->slots.n_slots;

@@ -3,9 +3,8 @@
 // compile it (tests/native/astar_host_check.cpp); the engine includes it from engine.hip and finishes the last long searches of a
 // replanning pass with it (replan_host.h).
 //
-// A search reads a host copy of the A* snapshot (Dev::amap, k_amap_build's words in 8 x 8-tiled order): low word = allowed
-// directions (bits 0-3) | is_road << 4 | intersection << 5 | road_type << 6 | occupied << 8 | red << 9 | the cell's vehicle penalty in
-// half units << PEN_SHIFT, high word = the cell's search-node number (0xFFFFFFFF: not a node).  It covers searches in half units
+// A search reads a host copy of the A* snapshot (Dev::amap, k_amap_build's words in 8 x 8-tiled order) and keeps k_replan's table
+// record: both layouts, and the costs in half units, are astar_words.h.  It covers searches in half units
 // without a field-of-view mask - what astar_half_units(P) && !respect_awareness selects on the device - and restates them quirk for
 // quirk (astar_numba.py:87-239 as astar.h lists it): an f-only binary heap with strict '<' in both sifts, dir_arr in heap-slot order and
 // not moved by the sifts, relaxations in the order N, E, S, W, `ng` truncated when stored.  n_exp / n_relax count what the device
@@ -23,18 +22,14 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+#include "astar_words.h"
 
 namespace ahost {
 
-constexpr int PEN_SHIFT = 10;             // = AMAP_PEN_SHIFT (astar.h; engine.hip asserts it)
-constexpr int INF = 0x3F3F3F3F;           // = A_INF
-constexpr uint32_t NO_NODE = 0xFFFFFFFFu;
-constexpr uint32_t STEPS_MASK = 0xFFF, STAMP_SHIFT = 14, STAMP_MAX = (1u << (32 - STAMP_SHIFT)) - 1u;
+constexpr uint32_t STAMP_MAX = (1u << (32 - W_STAMP_SHIFT)) - 1u;   // a searcher's own epochs: every stamp the meta word holds
 
-struct Costs {       // TsParams' penalties in half units (astar_wave: C.turn2 ...), and the two switches
-  int turn2, contra2, stop2, rt2[4];    // rt2[0] = 0
-  bool turn_on, rt_on;
-};
+struct Costs { HalfCosts hc; bool turn_on, rt_on; };     // TsParams' penalties in half units, and the two switches
+inline Costs costs_of(const TsParams& P) { return Costs{half_costs(P), P.turn_penalty_enabled != 0, P.road_type_penalties_enabled != 0}; }
 struct Map {
   const uint64_t* amap;
   int W, H, W8, N;
@@ -51,23 +46,24 @@ class Searcher {
   Result run(const Map& m, const Costs& c, const Query& q, int32_t* out, int out_cap) {
     if (tab_.size() != (size_t)m.n_nodes + 1) { tab_.assign((size_t)m.n_nodes + 1, 0ull); epoch_ = 0; }
     if (++epoch_ > STAMP_MAX) { std::fill(tab_.begin(), tab_.end(), 0ull); epoch_ = 1; }
-    const uint32_t epoch = epoch_, stamp = epoch << STAMP_SHIFT;
+    const uint32_t epoch = epoch_;
     const uint64_t* amap = m.amap;
     uint64_t* tab = tab_.data();
     const int W = m.W, H = m.H, W8 = m.W8;
-    auto tix = [W8](int x, int y) { return (uint32_t)((((y >> 3) * W8 + (x >> 3)) << 6) | ((y & 7) << 3) | (x & 7)); };
+    // (tables for the loops below, filled from the header's definitions: compares per neighbour cost tests/native/astar_host_check 3 %)
+    const int rt2[4] = {0, c.hc.rt2_1, c.hc.rt2_2, c.hc.rt2_3};
+    const int DX[4] = {dir_dx(0), dir_dx(1), dir_dx(2), dir_dx(3)}, DY[4] = {dir_dy(0), dir_dy(1), dir_dy(2), dir_dy(3)};
     const int sx = q.start % W, sy = q.start / W, gx = q.goal % W, gy = q.goal / W;
     const int goal_xy = (gy << 16) | gx;
     const bool limited = q.maximum_steps < m.N;
     Result r{0, 0, 0};
     {
-      const uint32_t sr = (uint32_t)(amap[tix(sx, sy)] >> 32);
-      if (sr != NO_NODE) tab[sr] = (uint64_t)stamp << 32;      // dist 0, steps 0
+      const uint32_t sr = am_node(amap[tix(W8, sx, sy)]);
+      if (sr != AM_NO_NODE) tab[sr] = tent_word(0, epoch, 0u, 0u);      // dist 0, steps 0
     }
     hq_.clear(); hd_.clear();
     hq_.push_back(HQ{std::abs(sx - gx) + std::abs(sy - gy), (sy << 16) | sx});
     hd_.push_back(-1);
-    static const int DX[4] = {0, 1, 0, -1}, DY[4] = {1, 0, -1, 0};
     while (!hq_.empty()) {
       const HQ top = hq_[0];
       const int prev_dir = hd_[0];
@@ -93,7 +89,7 @@ class Searcher {
         }
       }
       const int cur = top.i, cx = cur & 0xFFFF, cy = (int)((uint32_t)cur >> 16);
-      const uint64_t am_c = amap[tix(cx, cy)];
+      const uint64_t am_c = amap[tix(W8, cx, cy)];
       if (cur == goal_xy) {
         // walk came_from back to the start, filling the output from its far end, then slide it to the front
         int len = 0, px = cx, py = cy;
@@ -101,8 +97,7 @@ class Searcher {
           if (len >= out_cap) { r.len = -1; return r; }
           out[out_cap - 1 - len] = cc;
           len++;
-          const uint32_t pr = (uint32_t)(amap[tix(px, py)] >> 32);
-          const int dd = (int)((tab[pr] >> 32) & 3u);
+          const int dd = tent_dir(tab[am_node(amap[tix(W8, px, py)])]);
           px -= DX[dd]; py -= DY[dd];
           cc = py * W + px;
         }
@@ -112,43 +107,40 @@ class Searcher {
         return r;
       }
       const int g = top.f - (std::abs(cx - gx) + std::abs(cy - gy));
-      const uint32_t r_c = (uint32_t)(am_c >> 32);
+      const uint32_t r_c = am_node(am_c);
       int dist_c = 0, steps = 0;
-      if (r_c != NO_NODE) {       // (only a start cell can be off the node set: dist 0, no steps)
+      if (r_c != AM_NO_NODE) {       // (only a start cell can be off the node set: dist 0, no steps)
         const uint64_t e_c = tab[r_c];
-        const uint32_t m_c = (uint32_t)(e_c >> 32);
-        dist_c = (m_c >> STAMP_SHIFT) == epoch ? (int)(uint32_t)e_c : INF;
-        steps = limited ? (int)((m_c >> 2) & STEPS_MASK) : 0;
+        dist_c = tent_dist(e_c, epoch);
+        steps = limited ? tent_steps(e_c) : 0;
       }
       if (!(g <= dist_c)) continue;      // a stale pop relaxes nothing
       r.n_exp++;
       if (steps + 1 > q.maximum_steps) continue;
-      const uint32_t bits = (uint32_t)am_c & 15u;
+      const uint32_t bits = am_dirs((uint32_t)am_c);
       for (int dd = 0; dd < 4; dd++) {
         const int nx = cx + DX[dd], ny = cy + DY[dd];
         if ((unsigned)nx >= (unsigned)W || (unsigned)ny >= (unsigned)H) continue;
-        const uint64_t am = amap[tix(nx, ny)];
-        const uint32_t a = (uint32_t)am, rn = (uint32_t)(am >> 32);
-        if (rn == NO_NODE) continue;
-        const bool n_occ = ((a >> 8) & 1u) != 0u, n_stop = ((a >> 9) & 1u) != 0u, n_road = ((a >> 4) & 1u) != 0u;
+        const uint64_t am = amap[tix(W8, nx, ny)];
+        const uint32_t a = (uint32_t)am, rn = am_node(am);
+        if (rn == AM_NO_NODE) continue;
+        const bool n_occ = am_occ(a), n_stop = am_red(a), n_road = am_road(a);
         const bool flow = ((bits >> dd) & 1u) != 0u;
         if (!(flow | (q.ignore_flow & n_road))) continue;
         if (!(q.soft | !(n_occ | n_stop))) continue;
         int n2 = 2 * (g + 1);
-        n2 += (c.turn_on & (prev_dir != -1) & (dd != prev_dir)) ? c.turn2 : 0;
-        n2 += flow ? 0 : c.contra2;
-        n2 += n_occ ? (int)(a >> PEN_SHIFT) : 0;
-        n2 += n_stop ? c.stop2 : 0;
-        n2 += (c.rt_on & n_road) ? c.rt2[(a >> 6) & 3u] : 0;
-        const uint64_t e_n = tab[rn];
-        const uint32_t m_n = (uint32_t)(e_n >> 32);
-        const int dist_n = (m_n >> STAMP_SHIFT) == epoch ? (int)(uint32_t)e_n : INF;
+        n2 += (c.turn_on & (prev_dir != -1) & (dd != prev_dir)) ? c.hc.turn2 : 0;
+        n2 += flow ? 0 : c.hc.contra2;
+        n2 += n_occ ? am_pen2(a) : 0;
+        n2 += n_stop ? c.hc.stop2 : 0;
+        n2 += (c.rt_on & n_road) ? rt2[am_road_type(a)] : 0;
+        const int dist_n = tent_dist(tab[rn], epoch);
         if (!(n2 < 2 * dist_n)) continue;
         // (the four neighbours are distinct cells: committing one changes no other one's test)
         if ((int)hq_.size() + 1 > m.heap_cap) { r.len = -1; return r; }
         r.n_relax++;
         const int ngi = n2 >> 1;
-        tab[rn] = (uint64_t)(uint32_t)ngi | ((uint64_t)(stamp | (limited ? (uint32_t)(steps + 1) << 2 : 0u) | (uint32_t)dd) << 32);
+        tab[rn] = tent_word(ngi, epoch, limited ? (uint32_t)(steps + 1) : 0u, (uint32_t)dd);
         const HQ ne{ngi + std::abs(nx - gx) + std::abs(ny - gy), (ny << 16) | nx};
         // heap_push: the dir byte stays in the slot the entry was appended to, the entry rises past every ancestor with a larger key
         int i = (int)hq_.size();
@@ -169,7 +161,7 @@ class Searcher {
 
  private:
   struct HQ { int32_t f, i; };      // heap entry: key, cell as y << 16 | x
-  std::vector<uint64_t> tab_;       // per node: dist | (epoch << 14 | steps << 2 | came-from direction) << 32
+  std::vector<uint64_t> tab_;       // per node: k_replan's table record (tent_word)
   uint32_t epoch_ = 0;
   std::vector<HQ> hq_;
   std::vector<int8_t> hd_;

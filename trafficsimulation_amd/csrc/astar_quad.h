@@ -97,8 +97,8 @@ struct QSlots {
   uint32_t* tab;
   unsigned long long* gq; // per slot Q_SPILL entries
   uint32_t* gdw;          // per slot (QL + Q_SPILL) / 16 + 4 words of 2-bit directions
-  int32_t* cells;         // per slot 5 * Q_CELLS + 3 * MAXB
-  int32_t* log;           // per slot 3 * QLOG
+  int32_t* cells;         // per slot slot_cell_ints(Q_CELLS)
+  int32_t* log;           // per slot SLOG_INTS
   uint32_t* slot_epoch;        // per slot, over 1 .. epoch_max (0: fresh or cleared); kept from launch to launch and across hand-overs of the arena
   uint32_t epoch_max;          // Q_EPOCH_MAX (arena_epochs.h; TS_DEBUG_QUAD_EPOCH_MAX: earlier wraps for tests)
   unsigned long long* stats;   // QST_N counters (QST_*)
@@ -148,7 +148,7 @@ struct QConst {   // per quad, fixed for the kernel's lifetime
   // wave-uniform
   const TS_GLOBAL u64* amap;
   int W, H, W8, tw, th, tw8, chk_x, chk_y;
-  int turn2, stop2, rt2_1, rt2_2, rt2_3;
+  HalfCosts hc;             // (contra2 and veh2 go unused: no contraflow here, the vehicle penalty rides in the snapshot word)
   bool turn_on, rt_on;
 };
 
@@ -363,17 +363,17 @@ __device__ __forceinline__ int quad_turn(const QConst& K, QState& s) {
   const int dist_c = ((t_c ^ s.stamp) >> Q_STAMP_SHIFT) == 0u ? (int)(t_c & Q_DIST_MASK) : A_INF;
   const bool stale = g > dist_c;                                // (165)
   const uint32_t a_l = (uint32_t)am_l;
-  const bool node_l = (uint32_t)(am_l >> 32) != 0xFFFFFFFFu;
+  const bool node_l = (uint32_t)(am_l >> 32) != AM_NO_NODE;
   const int dist_l = ((t_l ^ s.stamp) >> Q_STAMP_SHIFT) == 0u ? (int)(t_l & Q_DIST_MASK) : A_INF;
-  const bool n_occ = ((a_l >> 8) & 1u) != 0u, n_stop = ((a_l >> 9) & 1u) != 0u, n_road = ((a_l >> 4) & 1u) != 0u;
-  const uint32_t rt = (a_l >> 6) & 3u;
+  const bool n_occ = ((a_l >> AM_OCC_BIT) & 1u) != 0u, n_stop = ((a_l >> AM_RED_BIT) & 1u) != 0u, n_road = ((a_l >> AM_ROAD_BIT) & 1u) != 0u;
+  const uint32_t rt = (a_l >> AM_RT_SHIFT) & AM_RT_MASK;
   const bool flow = ((am_c >> j) & 1u) != 0u;
   const bool turn = K.turn_on & (prev_dir != -1) & (j != prev_dir);
   int n2 = 2 * (g + 1);
-  n2 += turn ? K.turn2 : 0;
-  n2 += n_occ ? (int)(a_l >> AMAP_PEN_SHIFT) : 0;
-  n2 += n_stop ? K.stop2 : 0;
-  const int rtp = rt == 1u ? K.rt2_1 : rt == 2u ? K.rt2_2 : rt == 3u ? K.rt2_3 : 0;
+  n2 += turn ? K.hc.turn2 : 0;
+  n2 += n_occ ? (int)(a_l >> AM_PEN_SHIFT) : 0;
+  n2 += n_stop ? K.hc.stop2 : 0;
+  const int rtp = rt == 1u ? K.hc.rt2_1 : rt == 2u ? K.hc.rt2_2 : rt == 3u ? K.hc.rt2_3 : 0;
   n2 += (K.rt_on & n_road) ? rtp : 0;
   const bool cand = !is_goal & !stale & inb & node_l & flow & ((s.soft != 0) | !(n_occ | n_stop));
   const bool ok = cand & inw & (n2 < 2 * dist_l);
@@ -505,14 +505,14 @@ struct QReq { int start, goal, soft, cap; int32_t* out; };
 
 __device__ __forceinline__ void quad_scratch_bind(const QSlots& qs, int slot, AScratch& S) {
   S.tab = nullptr; S.gq = nullptr; S.gd = nullptr; S.heap_cap = 0; S.epoch = 0;
-  int32_t* c = qs.cells + (size_t)slot * ((size_t)5 * Q_CELLS + 3 * MAXB);
+  int32_t* c = qs.cells + (size_t)slot * slot_cell_ints(Q_CELLS);
   S.A = c; S.P = c + Q_CELLS; S.T = c + 2 * Q_CELLS; S.PO = c + 3 * Q_CELLS; S.PD = c + 4 * Q_CELLS;
   S.BYP = c + 5 * Q_CELLS; S.OV = S.BYP + MAXB; S.DV = S.OV + MAXB;
   S.cap = Q_CELLS;
   S.use_reach = 0;
   S.big_thr = ~0u; S.big_flag = nullptr;      // (the quads' records carry 22-bit dists: nothing to watch)
   S.calls = 0; S.expansions = 0; S.relaxations = 0;
-  S.q_log = qs.log + (size_t)slot * (3 * QLOG);
+  S.q_log = qs.log + (size_t)slot * SLOG_INTS;
   S.q_status = DV_BAIL; S.q_replay = 0; S.q_done = 0;
   S.q_start = 0; S.q_goal = 0; S.q_soft = 0; S.q_cap = 0; S.q_out = nullptr;
 }
@@ -555,9 +555,7 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
   K.tw = qs.tw; K.th = qs.th; K.tw8 = qs.tw >> 3;
   K.chk_x = qs.chk_x; K.chk_y = qs.chk_y;
   K.turn_on = P.turn_penalty_enabled != 0; K.rt_on = P.road_type_penalties_enabled != 0;
-  K.turn2 = (int)((double)P.turn_penalty * 2.0); K.stop2 = (int)((double)P.obstacle_penalty_stop * 2.0);
-  K.rt2_1 = (int)((double)P.road_type_penalty_r1 * 2.0); K.rt2_2 = (int)((double)P.road_type_penalty_r2 * 2.0);
-  K.rt2_3 = (int)((double)P.road_type_penalty_r3 * 2.0);
+  K.hc = half_costs(P);
   uint32_t epoch = qs.slot_epoch[slot];
   QState s;
   s.hs = 0; s.dir0 = -1; s.wb = 0; s.dwin = 0; s.xpre = 0; s.why = 0; s.n_step3 = 0; s.n_deep = 0; s.gx = s.gy = s.sx = s.sy = 0; s.ox = s.oy = 0; s.goal_xy = 0; s.stamp = 0; s.soft = 0; s.n_exp = 0; s.n_relax = 0;
@@ -637,7 +635,7 @@ __global__ void __launch_bounds__(64) k_replan_quad(Dev d, TsParams P, QSlots qs
         }
         if (len < 0) { st = QS_ABANDON; s.why = QST_PATHBUF; }
         else {
-          int32_t* lg = qs.log + (size_t)slot * (3 * QLOG) + 3 * n_done;
+          int32_t* lg = qs.log + (size_t)slot * SLOG_INTS + 3 * n_done;
           lg[0] = len; lg[1] = s.n_exp; lg[2] = s.n_relax;
           n_done++;
           st = QS_POLICY;

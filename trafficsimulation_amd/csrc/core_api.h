@@ -1005,16 +1005,11 @@ int ts_debug_tail_probe(ts_handle e, int32_t n, const int32_t* start, const int3
   if (!e || n < 0 || (n > 0 && (!start || !goal || !soft || !out_len || !out_exp || !out_ms)) || !wall_ms) return TS_E_INVALID;
   for (int k = 0; k < n; k++) if (start[k] < 0 || start[k] >= e->N || goal[k] < 0 || goal[k] >= e->N) return fail(e, TS_E_INVALID, "probe endpoints out of bounds");
   if (!astar_half_units(e->P) || e->P.respect_awareness) return fail(e, TS_E_UNSUPPORTED, "the host searcher carries half-unit costs without a field-of-view mask");
-  TRY(ensure_density(e, e->d.occ));
-  e->density_valid = false;
-  TRY(ensure_slots(e));
-  e->amap_valid = false;
-  TRY(ensure_amap(e));
-  e->amap_valid = false;
+  TRY(search_maps_now(e));
   TRY(tail_snapshot_begin(e));
   TRY(tail_snapshot_wait(e));
   const ahost::Map map = tail_map(e);
-  const ahost::Costs costs = tail_costs(e->P);
+  const ahost::Costs costs = ahost::costs_of(e->P);
   const int cap = e->slots.cap;
   const double t0 = now_ms();
   e->tail.pool->run(n, [&](ahost::Searcher& s, int k) {
@@ -1036,19 +1031,14 @@ int ts_astar(ts_handle e, int32_t sx, int32_t sy, int32_t gx, int32_t gy, int32_
     return fail(e, TS_E_INVALID, "astar endpoints out of bounds");
   if (maximum_steps < e->N && maximum_steps > A_STEPS_MAX)
     return fail(e, TS_E_UNSUPPORTED, "a binding maximum_steps above 4094 is not carried (use >= width * height for 'unlimited')");
-  TRY(ensure_density(e, e->d.occ));  // "evaluated on the engine's current maps"
-  e->density_valid = false;
-  TRY(ensure_slots(e));
-  e->amap_valid = false;
-  TRY(ensure_amap(e));
-  e->amap_valid = false;
+  TRY(search_maps_now(e));  // "evaluated on the engine's current maps"
   if (e->tail.astar_host) {   // TS_ASTAR_HOST (a test hook): the host searcher on a fresh copy of the snapshot
     TRY(tail_snapshot_begin(e));
     TRY(tail_snapshot_wait(e));
     std::vector<int32_t> cells((size_t)e->slots.cap);
     ahost::Result r{};
     const ahost::Map map = tail_map(e);
-    const ahost::Costs costs = tail_costs(e->P);
+    const ahost::Costs costs = ahost::costs_of(e->P);
     const ahost::Query q{sy * e->W + sx, gy * e->W + gx, soft != 0, ignore_flow != 0, maximum_steps};
     e->tail.pool->run(1, [&](ahost::Searcher& s, int) { r = s.run(map, costs, q, cells.data(), (int)cells.size()); });
     if (r.len < 0) return fail(e, TS_E_CAPACITY, "an A* search exceeded its heap or path buffers");

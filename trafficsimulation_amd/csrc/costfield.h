@@ -50,20 +50,17 @@ __device__ __forceinline__ void cf_activate(uint32_t* flag, int32_t* list, uint3
 
 // ---- pre-pass: the maps as one word per cell --------------------------------------------------------------------------
 // soft / free_flow are the query's; dens_on = soft && dynamic_penalties_enabled (astar_wave's C.dens_on)
-__global__ void k_cf_cells(Dev d, int soft, int free_flow, int dens_on, int rt_on, double veh_pen, double dyn_scale, int stop2,
-                           int rt2_1, int rt2_2, int rt2_3, uint32_t* cw) {
+__global__ void k_cf_cells(Dev d, int soft, int free_flow, int dens_on, int rt_on, double veh_pen, double dyn_scale, HalfCosts hc,
+                           uint32_t* cw) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= d.N) return;
   const Cell& x = d.cell[c];
   const uint32_t stat = x.stat;
   const bool occ = !free_flow && x.occ == 1, stop = !free_flow && x.stop == 1;
   int cost2 = 2;
-  if (occ) cost2 += dens_on ? 2 * (int)occ_penalty_dyn(veh_pen, dyn_scale, d.density[c]) : (int)(veh_pen * 2.0);
-  if (stop) cost2 += stop2;
-  if (rt_on && st_is_road((uint8_t)stat)) {
-    const int rt = st_road_type((uint8_t)stat);
-    cost2 += rt == 1 ? rt2_1 : rt == 2 ? rt2_2 : rt == 3 ? rt2_3 : 0;
-  }
+  if (occ) cost2 += dens_on ? 2 * (int)occ_penalty_dyn(veh_pen, dyn_scale, d.density[c]) : hc.veh2;
+  if (stop) cost2 += hc.stop2;
+  if (rt_on && st_is_road((uint8_t)stat)) cost2 += rt2_of(hc, (uint32_t)st_road_type((uint8_t)stat));
   const bool enter = soft || !(occ || stop);
   cw[c] = (stat & 15u) | ((uint32_t)st_is_road((uint8_t)stat) << CW_ROAD) | ((enter ? 1u : 0u) << CW_ENTER) | ((uint32_t)cost2 << CW_COST);
 }

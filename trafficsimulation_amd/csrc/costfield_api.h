@@ -69,6 +69,7 @@ int cf_compute(E* e, const TsCostFieldQuery* q, TsCostFieldInfo* out, bool hops)
   int T = 32;
   if (const char* s = getenv("TS_DEBUG_COSTFIELD_TILE")) { const int v = atoi(s); if (v == 8 || v == 16) T = v; }
   const bool to = q->mode == TS_CF_TO;
+  const HalfCosts hc = half_costs(P);
   const int NH = (P.turn_penalty_enabled && P.turn_penalty > 0) ? 4 : 1;
   const int n = q->n_seeds;
   const size_t N = (size_t)e->N;
@@ -103,12 +104,10 @@ int cf_compute(E* e, const TsCostFieldQuery* q, TsCostFieldInfo* out, bool hops)
   e->density_valid = false;
   e->amap_valid = false;
   hipLaunchKernelGGL(k_cf_cells, dim3(nblk((long long)N)), dim3(BLK), 0, st, e->d, soft ? 1 : 0, free_flow ? 1 : 0, dens_on ? 1 : 0,
-                     P.road_type_penalties_enabled ? 1 : 0, (double)P.obstacle_penalty_vehicle, (double)P.dynamic_penalty_scale,
-                     (int)((double)P.obstacle_penalty_stop * 2.0), (int)(P.road_type_penalty_r1 * 2.0), (int)(P.road_type_penalty_r2 * 2.0),
-                     (int)(P.road_type_penalty_r3 * 2.0), cw);
+                     P.road_type_penalties_enabled ? 1 : 0, (double)P.obstacle_penalty_vehicle, (double)P.dynamic_penalty_scale, hc, cw);
   CostFieldArgs a{};
   a.W = e->W; a.H = e->H; a.N = e->N; a.T = T; a.tiles_x = tiles_x; a.tiles_y = tiles_y;
-  a.ignore_flow = q->ignore_flow; a.turn2 = NH == 4 ? 2 * P.turn_penalty : 0; a.contra2 = 2 * P.contraflow_penalty;
+  a.ignore_flow = q->ignore_flow; a.turn2 = NH == 4 ? hc.turn2 : 0; a.contra2 = hc.contra2;
   a.limit = (q->max_cost != 0 && q->max_cost < CF_INF - 1) ? q->max_cost + 1 : CF_INF;
   a.cw = cw; a.lab = lab; a.seed = seed;
   uint32_t* n_list = ctl;

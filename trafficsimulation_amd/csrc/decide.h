@@ -123,6 +123,7 @@ __device__ __forceinline__ void swap_ptr(int32_t*& a, int32_t*& b) { int32_t* t 
 // wave); plain stores are then harmless duplicates, atomics are issued by lane 0 only, and the searches use
 // astar_wave.  DM_QUAD: the same with the four lanes of a quad.  DM_LANE: one vehicle per lane (k_decide_main), nothing is shared.
 constexpr int QLOG = 8;   // searches one step_decide can make in quad mode (beyond that the vehicle goes to k_replan)
+constexpr int SLOG_INTS = 3 * QLOG;   // ints in a searcher slot's log (AScratch::q_log): length, expansions, relaxations per search
 template <int MODE>
 __device__ __forceinline__ int astar_any(const Dev& d, const TsParams& P, AScratch& S, int start_idx, int goal_idx, bool soft,
                                          bool ignore_flow, int maximum_steps, int32_t* out, int out_cap) {

@@ -5,6 +5,7 @@
 #include "../../include/trafficsim.h"
 #include "../../include/trafficsim_observe.h"
 #include "../../include/trafficsim_triplog.h"
+#include "astar_words.h"
 
 #define BLK 256
 
@@ -77,13 +78,13 @@ struct __attribute__((aligned(32))) Cell {
   uint32_t claim[4];
   int32_t veh;                 // first vehicle in the cell's list, -1 = none
   int8_t occ, stop, stuck;     // occupancy_map / stop_map / stuck_map
-  uint8_t stat;                // allowed_dirs (bits 0-3) | is_road << 4 | intersection << 5 | road_type << 6
+  uint8_t stat;                // allowed_dirs (bits 0-3) | is_road << 4 | intersection << 5 | road_type << 6: bits 0-7 of the A* snapshot word (astar_words.h)
   uint32_t pad_[2];
 };
-__host__ __device__ __forceinline__ int st_allowed(uint8_t s) { return s & 15; }
-__host__ __device__ __forceinline__ int st_is_road(uint8_t s) { return (s >> 4) & 1; }
-__host__ __device__ __forceinline__ int st_inter(uint8_t s) { return (s >> 5) & 1; }
-__host__ __device__ __forceinline__ int st_road_type(uint8_t s) { return (s >> 6) & 3; }
+__host__ __device__ __forceinline__ int st_allowed(uint8_t s) { return s & (int)AM_DIRS_MASK; }
+__host__ __device__ __forceinline__ int st_is_road(uint8_t s) { return (s >> AM_ROAD_BIT) & 1; }
+__host__ __device__ __forceinline__ int st_inter(uint8_t s) { return (s >> AM_INTER_BIT) & 1; }
+__host__ __device__ __forceinline__ int st_road_type(uint8_t s) { return (s >> AM_RT_SHIFT) & (int)AM_RT_MASK; }
 
 struct TripLog;   // triplog.h
 
@@ -119,10 +120,7 @@ struct Dev {
   uint8_t* tier_hint;  // per vehicle: bit length of the expansions its last replan took (cost_bits, below), orders the replanning work queue
   uint8_t* chg;        // per vehicle: what its replan of this tick rewrote (bit 0 path, bits 1-4 aux paths) - read and cleared by
                        // k_replan_export in the multi-GPU mode
-  // what a search reads about a cell, as of the last tick start (or the last ensure_amap), in tiled order: low word =
-  // static byte | occupied << 8 | red << 9, high word = the cell's search-node number (0xFFFFFFFF: not a node).  Nodes
-  // are the cells a search can ever stand on (roads, cells with flow bits, cells a flow bit points at), numbered in
-  // tiled order: a searcher's dist / came_from table has one record per NODE, a quarter of one record per cell.
+  // the A* snapshot: what a search reads about a cell, one word per cell in tiled order (the layout: astar_words.h)
   unsigned long long* amap;
   int n_nodes;
   // VEHICLE_RESPECT_AWARENESS only: per cell (tiled order) the lengths of the straight runs of road cells that end in it,
@@ -188,11 +186,8 @@ __device__ __forceinline__ void cell_xy(int W, unsigned long long w_magic, int c
   else { y = cell / W; x = cell - y * W; }
 }
 __device__ __forceinline__ void cell_xy(const Dev& d, int cell, int& x, int& y) { cell_xy(d.W, d.w_magic, cell, x, y); }
-// position of cell (x, y) in the 8 x 8-tiled order of a map (or a table window) `tiles` tiles wide
-__device__ __forceinline__ uint32_t tix(int tiles, int x, int y) {
-  // (tile rows and tiles per row are far below 2^24: the full-rate 24-bit multiply)
-  return (((__umul24((uint32_t)(y >> 3), (uint32_t)tiles) + (uint32_t)(x >> 3)) << 6) | (uint32_t)((y & 7) << 3) | (uint32_t)(x & 7));
-}
+// position of cell (x, y) in the tiled order of the map (astar_words.h tix)
+using ::tix;
 __device__ __forceinline__ uint32_t tix(const Dev& d, int x, int y) { return tix(d.W8, x, y); }
 // Work-queue order of the replans (largest first).  Per vehicle the bit length of the expansions its last replan took is
 // kept (Dev::tier_hint); the four classes are ranges of it (< 2 048, < 32 768, < 262 144 expansions, more), and inside a

@@ -673,7 +673,7 @@ __global__ void k_spawn(Dev d, TsParams P, SpawnArgs a, int n, int vid0, int act
     int x, y;
     cell_xy(d, pos, x, y);
     const uint32_t t = tix(d, x, y);
-    atomicOr(&d.amap[t], 0x100ull);
+    atomicOr(&d.amap[t], 1ull << AM_OCC_BIT);
   }
   for (int k = 0; k < 4; k++) { d.ax_len[k][vid] = 0; d.ax_off[k][vid] = 0; d.ax_start[k][vid] = pos; }
   d.active[active0 + i] = vid; d.active_idx[vid] = active0 + i;
@@ -813,20 +813,18 @@ __global__ void k_cells_init(Cell* cell, int n, const uint8_t* allowed, const in
   x.pad_[1] = 0;
   cell[c] = x;
 }
-// the A* snapshot of the maps (Dev::amap) from the cell records
-// pen_mode: what the penalty bits carry for searches in half units - 0 nothing (penalties are not multiples of 0.5: those
-// searches read the density map themselves), 1 the constant vehicle penalty, 2 the density-dependent one of this cell
-// (VEHICLE_DYNAMIC_PENALTIES; density = the tick-start snapshot, so a rebuild inside the tick gives the same bits)
+// the A* snapshot of the maps (Dev::amap) from the cell records (the word: astar_words.h)
+// pen_mode: what the penalty bits carry - 0 nothing, 1 the constant vehicle penalty, 2 the density-dependent one of this cell
 __global__ void k_amap_build(Dev d, int pen_mode, double veh_pen, double dyn_scale) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= d.N) return;
   int x, y;
   cell_xy(d, c, x, y);
   const uint2 w = *reinterpret_cast<const uint2*>(&d.cell[c].occ);   // .x = occ | stop << 8 | stuck << 16 | stat << 24, .y = node number
-  uint32_t flags = (w.x >> 24) | (((int8_t)(w.x & 0xFF) == 1) ? 0x100u : 0u) | (((int8_t)((w.x >> 8) & 0xFF) == 1) ? 0x200u : 0u);
+  uint32_t flags = (w.x >> 24) | (((int8_t)(w.x & 0xFF) == 1) ? 1u << AM_OCC_BIT : 0u) | (((int8_t)((w.x >> 8) & 0xFF) == 1) ? 1u << AM_RED_BIT : 0u);
   const int pen2 = pen_mode == 0 ? 0 : pen_mode == 1 ? (int)(veh_pen * 2.0) : 2 * (int)occ_penalty_dyn(veh_pen, dyn_scale, d.density[c]);
-  flags |= (uint32_t)pen2 << AMAP_PEN_SHIFT;
-  d.amap[tix(d, x, y)] = (unsigned long long)flags | ((unsigned long long)w.y << 32);
+  flags |= (uint32_t)pen2 << AM_PEN_SHIFT;
+  d.amap[tix(d, x, y)] = am_word(flags, w.y);
 }
 __global__ void k_claims_reset(Cell* cell, int n) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;

@@ -126,10 +126,10 @@ __device__ __forceinline__ void replan_settle(const Dev& d, const RQueue& q, int
 // runs the listed searches on its own threads (astar_host.h), puts each path where the search would have put it and its result
 // in the log, and k_replan_tail runs those step_decides again from the top on the same slots, replaying the log.  No kernel
 // waits for the host or reads what the host writes while it runs.
-struct RTail { TailCtl* ctl; int32_t* log; int t_max, floor, force, pad_; };   // ctl == nullptr: off; log: 3 * QLOG ints per searcher slot
+struct RTail { TailCtl* ctl; int32_t* log; int t_max, floor, force, pad_; };   // ctl == nullptr: off; log: SLOG_INTS ints per searcher slot
 __device__ __forceinline__ void tail_bind(const RTail& t, int slot, int grid, AScratch& S) {
   if (!t.ctl) return;
-  S.q_log = t.log + (size_t)slot * 3 * QLOG;
+  S.q_log = t.log + (size_t)slot * SLOG_INTS;
   S.t_ctl = t.ctl;
   // (TS_TAIL_FORCE: every search the rule applies to gives up when it has made `force` expansions, whatever the other waves do)
   S.t_thr = t.force > 0 ? (int)0x80000000 : grid - t.t_max;
@@ -246,7 +246,7 @@ TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_replan_tail(Dev d, TsParam
   const TailEnt t = ((const TailEnt*)(tl.ctl + 1))[blockIdx.x];
   AScratch S;
   scratch_bind(sl, t.slot, S);
-  S.q_log = tl.log + (size_t)t.slot * 3 * QLOG;
+  S.q_log = tl.log + (size_t)t.slot * SLOG_INTS;
   const RQueue q = rqueue_open(d, qa);
   replan_rerun(d, P, &S, q, t.i, t.ord + 1);
   if (threadIdx.x == 0) sl.slot_epoch[t.slot] = S.epoch;

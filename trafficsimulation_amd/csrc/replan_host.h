@@ -13,7 +13,7 @@ struct QuadRequest { long long want; size_t side; };
 inline QuadRequest quad_request() {
   const long long want = getenv("TS_QUAD_SLOTS") ? atoll(getenv("TS_QUAD_SLOTS")) : (long long)TS_QUAD_WAVES_PER_CU * 256 * 16;
   return {std::max<long long>(16, (want / 16) * 16),
-          (size_t)Q_SPILL * 8 + (size_t)Q_DWORDS * 4 + ((size_t)5 * Q_CELLS + 3 * MAXB) * 4 + 3 * QLOG * 4 + 4};
+          (size_t)Q_SPILL * 8 + (size_t)Q_DWORDS * 4 + slot_cell_ints(Q_CELLS) * 4 + SLOG_INTS * 4 + 4};
 }
 
 // Searcher slots for k_replan (one search per wave): per slot a direct-indexed table of one 8-byte record per search node
@@ -51,7 +51,7 @@ int ensure_slots(E* e) {
   T.use_reach = (getenv("TS_NO_REACH") || e->P.respect_awareness) ? 0 : 1;
   T.heap_cap = LDS_HEAP + (int)std::min<long long>(4 * N, 1ll << 18);   // (the deepest heap seen on 4096^2 runs is ~1500 entries)
   const size_t spill = (size_t)(T.heap_cap - LDS_HEAP);
-  const size_t per_slot = T.tab_entries * sizeof(TEnt) + spill * (sizeof(HQ) + 1) + ((size_t)5 * T.cap + 3 * MAXB) * 4 + 4;
+  const size_t per_slot = T.tab_entries * sizeof(TEnt) + spill * (sizeof(HQ) + 1) + slot_cell_ints((size_t)T.cap) * 4 + 4;
   size_t free_b = 0, total_b = 0;
   HIPOK(hipMemGetInfo(&free_b, &total_b));
   // (headroom for what grows later - the path pool doubles under load, the vehicle arrays regrow, a second engine in the
@@ -77,7 +77,7 @@ int ensure_slots(E* e) {
   HIPOK(dalloc(e, &T.tab, S * T.tab_entries));
   HIPOK(dalloc(e, &T.gq, S * spill));
   HIPOK(dalloc(e, &T.gd, S * spill));
-  HIPOK(dalloc(e, &T.cells, S * ((size_t)5 * T.cap + 3 * MAXB)));
+  HIPOK(dalloc(e, &T.cells, S * slot_cell_ints((size_t)T.cap)));
   HIPOK(dalloc(e, &T.slot_epoch, S));
   HIPOK(dalloc(e, &T.big_flag, 1));
   T.big_thr = getenv("TS_DEBUG_ARENA_BIGDIST") ? (uint32_t)std::max(1, atoi(getenv("TS_DEBUG_ARENA_BIGDIST"))) : ARENA_BIGDIST;
@@ -125,7 +125,7 @@ int ensure_qslots(E* e) {
   }
   const size_t QS = (size_t)Q.n_slots;
   if (dalloc(e, &Q.gq, QS * Q_SPILL) != hipSuccess || dalloc(e, &Q.gdw, QS * Q_DWORDS) != hipSuccess ||
-      dalloc(e, &Q.cells, QS * ((size_t)5 * Q_CELLS + 3 * MAXB)) != hipSuccess || dalloc(e, &Q.log, QS * 3 * QLOG) != hipSuccess ||
+      dalloc(e, &Q.cells, QS * slot_cell_ints(Q_CELLS)) != hipSuccess || dalloc(e, &Q.log, QS * SLOG_INTS) != hipSuccess ||
       dalloc(e, &Q.slot_epoch, QS) != hipSuccess || dalloc(e, &Q.stats, QST_N) != hipSuccess) { e->arena_shared = false; return off(); }
   HIPOK(hipMemsetAsync(Q.slot_epoch, 0, QS * 4, e->stream));
   HIPOK(hipMemsetAsync(Q.stats, 0, QST_N * sizeof(unsigned long long), e->stream));
@@ -222,6 +222,19 @@ int ensure_density(E* e, const int8_t* occ_src) {
   return TS_OK;
 }
 
+// The maps a query "on the engine's current maps" reads (ts_astar, ts_astar_batch_run, the probes): the density planes and the
+// snapshot from the cell records as they are now, built once for the call and dropped afterwards - the next tick, whose
+// searches read the tick-start state, builds its own.
+int search_maps_now(E* e) {
+  TRY(ensure_density(e, e->d.occ));
+  e->density_valid = false;
+  TRY(ensure_slots(e));
+  e->amap_valid = false;
+  TRY(ensure_amap(e));
+  e->amap_valid = false;
+  return TS_OK;
+}
+
 // Order class list h (n entries) by its sort key.  Sharded, the order must be total and the same on every rank: 64-bit keys
 // that end in the entry itself; otherwise key/value pairs.
 int sort_replan_list(E* e, int h, int n, bool sharded) {
@@ -281,12 +294,6 @@ int replan_pass_done(E* e) {
 }
 
 // ---- the host tail (replan.h RTail) -------------------------------------------------------------
-static_assert(ahost::PEN_SHIFT == AMAP_PEN_SHIFT && ahost::INF == A_INF, "astar_host.h reads k_amap_build's words");
-inline ahost::Costs tail_costs(const TsParams& P) {
-  return ahost::Costs{(int)((double)P.turn_penalty * 2.0), (int)((double)P.contraflow_penalty * 2.0), (int)((double)P.obstacle_penalty_stop * 2.0),
-                      {0, (int)(P.road_type_penalty_r1 * 2.0), (int)(P.road_type_penalty_r2 * 2.0), (int)(P.road_type_penalty_r3 * 2.0)},
-                      P.turn_penalty_enabled != 0, P.road_type_penalties_enabled != 0};
-}
 inline ahost::Map tail_map(const E* e) {
   return ahost::Map{e->tail.h_amap, e->W, e->H, e->d.W8, e->N, (uint32_t)std::max(e->d.n_nodes, 1), e->slots.heap_cap};
 }
@@ -330,7 +337,7 @@ int tail_begin(E* e, RTail& tl) {
     uint8_t* raw = nullptr;
     HIPOK(dalloc(e, &raw, sizeof(TailCtl) + S * sizeof(TailEnt)));
     th.ctl = (TailCtl*)raw;
-    HIPOK(dalloc(e, &th.log, S * 3 * QLOG));
+    HIPOK(dalloc(e, &th.log, S * SLOG_INTS));
     const TailCtl first = {0, 0, e->slots.n_slots, 0};
     HIPOK(hipMemcpy(th.ctl, &first, sizeof(first), hipMemcpyHostToDevice));
   }
@@ -355,7 +362,7 @@ int tail_finish(E* e, const RQueueArgs& qa, const RTail& tl, double t_launch, in
   TRY(read_back(e, list.data(), th.ctl + 1, (size_t)n * sizeof(TailEnt)));
   TRY(tail_snapshot_wait(e));
   const ahost::Map map = tail_map(e);
-  const ahost::Costs costs = tail_costs(P);
+  const ahost::Costs costs = ahost::costs_of(P);
   std::vector<std::unique_ptr<int32_t[]>> out((size_t)n);
   std::vector<int32_t> res((size_t)n * 3);
   for (int k = 0; k < n; k++) out[(size_t)k].reset(new int32_t[(size_t)std::max(list[(size_t)k].out_cap, 1)]);
@@ -369,8 +376,8 @@ int tail_finish(E* e, const RQueueArgs& qa, const RTail& tl, double t_launch, in
   for (int k = 0; k < n; k++) {
     const TailEnt& t = list[(size_t)k];
     const int len = res[3 * (size_t)k];
-    if (len > 0) HIPOK(hipMemcpyAsync(e->slots.cells + (size_t)t.slot * ((size_t)5 * e->slots.cap + 3 * MAXB) + t.out_off, out[(size_t)k].get(), (size_t)len * 4, hipMemcpyHostToDevice, e->stream));
-    HIPOK(hipMemcpyAsync(th.log + ((size_t)t.slot * QLOG + t.ord) * 3, &res[3 * (size_t)k], 12, hipMemcpyHostToDevice, e->stream));
+    if (len > 0) HIPOK(hipMemcpyAsync(e->slots.cells + (size_t)t.slot * slot_cell_ints((size_t)e->slots.cap) + t.out_off, out[(size_t)k].get(), (size_t)len * 4, hipMemcpyHostToDevice, e->stream));
+    HIPOK(hipMemcpyAsync(th.log + (size_t)t.slot * SLOG_INTS + 3 * t.ord, &res[3 * (size_t)k], 12, hipMemcpyHostToDevice, e->stream));
   }
   LAUNCH(e, PK_REPLAN, n, k_replan_tail, dim3(n), dim3(64), e->d, P, e->slots, qa, tl, n);
   const int rc = replan_pass_done(e);       // (the stream drains here: the staged paths and results are no longer read)
