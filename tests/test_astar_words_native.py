@@ -8,7 +8,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "astar_words_check.cpp")
 INC = os.path.join(HERE, "..", "trafficsimulation_amd", "csrc")
-HDRS = [os.path.join(INC, h) for h in ("astar_words.h", "arena_epochs.h")]
+HDRS = [os.path.join(INC, h) for h in ("astar_words.h", "arena_epochs.h", "path_words.h")]
 BUILD = os.path.join(HERE, "native", "_build")
 
 

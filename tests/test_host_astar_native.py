@@ -13,7 +13,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "astar_host_check.cpp")
 INC = os.path.join(HERE, "..", "trafficsimulation_amd", "csrc")
-HDRS = [os.path.join(INC, h) for h in ("astar_host.h", "astar_words.h", "arena_epochs.h")]
+HDRS = [os.path.join(INC, h) for h in ("astar_host.h", "astar_words.h", "arena_epochs.h", "path_words.h")]
 BUILD = os.path.join(HERE, "native", "_build")
 GOLDEN = os.path.join(HERE, "golden")
 

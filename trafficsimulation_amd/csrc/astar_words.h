@@ -1,5 +1,5 @@
 // astar_words.h - the words the A* searchers share, in one place: the snapshot word of a cell (Dev::amap), the tiled index it
-// is stored under, k_replan's table record, the search penalties in half units and the direction deltas.  The three search
+// is stored under, k_replan's table record and the search penalties in half units (the direction deltas: path_words.h).  The three search
 // loops (astar.h: the wave, astar_quad.h: the quads, astar_host.h: the host) stay three loops; this is the vocabulary they are
 // written in.  Plain C++17 as well as HIP: tests/native/astar_words_check.cpp runs these functions on the host.
 //
@@ -9,13 +9,8 @@
 #pragma once
 #include <cstdint>
 #include "arena_epochs.h"
+#include "path_words.h"   // TS_WORDS_FN; the directions and their deltas (dir_dx, dir_dy)
 #include "../../include/trafficsim.h"
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define TS_WORDS_FN __host__ __device__ __forceinline__
-#else
-#define TS_WORDS_FN inline
-#endif
 
 // ---- the A* snapshot word: what a search reads about a cell, as of the last tick start (or the last ensure_amap) ------------------
 // One 8-byte word per cell, in 8 x 8-tiled order (tix below: two rows of a tile are one 128-byte line, so the neighbours of a
@@ -105,7 +100,3 @@ TS_WORDS_FN HalfCosts half_costs(const TsParams& P) {
 }
 // the penalty of a road of type rt (0: none), for cold code
 TS_WORDS_FN int rt2_of(const HalfCosts& c, uint32_t rt) { return rt == 1u ? c.rt2_1 : rt == 2u ? c.rt2_2 : rt == 3u ? c.rt2_3 : 0; }
-
-// ---- direction deltas: N, E, S, W = +y, +x, -y, -x ---------------------------------------------------------------------------------
-TS_WORDS_FN int dir_dx(int dd) { return (dd == 1) - (dd == 3); }
-TS_WORDS_FN int dir_dy(int dd) { return (dd == 0) - (dd == 2); }

@@ -40,16 +40,15 @@ __global__ void k_ckpt_unpack_cells(Cell* __restrict__ cell, int n, const int32_
   stop_plane[c] = s;
 }
 
-// words a vehicle's paths take in a blob: the unread part of its main path (whole pool words from the one holding
-// path_cur on, as k_pool_gc keeps them) and its four aux paths; 0 for a vehicle that is gone
+// words a vehicle's paths take in a blob: the live words of its main path and of its four aux paths (path_words.h: path_live,
+// aux_words - what k_pool_gc keeps); 0 for a vehicle that is gone
 __device__ __forceinline__ void ck_path_words(const Dev& d, int v, int& w0, int& main_w, int (&ax_w)[4]) {
   w0 = 0; main_w = 0;
   for (int k = 0; k < 4; k++) ax_w[k] = 0;
   if (!(d.flags[v] & VF_ALIVE)) return;
-  const int cur = d.path_cur[v], len = d.path_len[v];
-  w0 = cur >> 4;
-  main_w = max(0, ((len + 15) >> 4) - w0);
-  for (int k = 0; k < 4; k++) { const int l = d.ax_len[k][v]; ax_w[k] = l > 0 ? (l + 15) >> 4 : 0; }
+  const PathLive l = path_live(d.path_cur[v], d.path_len[v]);
+  w0 = l.w0; main_w = l.words;
+  for (int k = 0; k < 4; k++) ax_w[k] = aux_words(d.ax_len[k][v]);
 }
 __device__ __forceinline__ int ck_total(int main_w, const int (&ax_w)[4]) { return main_w + ax_w[0] + ax_w[1] + ax_w[2] + ax_w[3]; }
 
@@ -77,7 +76,7 @@ __device__ __forceinline__ int ck_block_excl(int c) {
   return base + incl - c;
 }
 // every vehicle's words at its place in vehicle-id order (offsets from the block scan, never from arrival order), and its
-// main path's cursor and length as they read against the packed words (path_cur & 15, path_len - 16 * dropped words)
+// main path's cursor and length as they read against the packed words (path_live's)
 __global__ void k_ckpt_pack_paths(Dev d, int nv, const int* __restrict__ block_off, uint32_t* __restrict__ out,
                                   int32_t* __restrict__ out_cur, int32_t* __restrict__ out_len) {
   const int v = blockIdx.x * BLK + threadIdx.x;
@@ -85,9 +84,9 @@ __global__ void k_ckpt_pack_paths(Dev d, int nv, const int* __restrict__ block_o
   if (v < nv) ck_path_words(d, v, w0, mw, aw);
   const int off = block_off[blockIdx.x] + ck_block_excl(ck_total(mw, aw));
   if (v >= nv) return;
-  const int cur = d.path_cur[v], len = d.path_len[v];
-  out_cur[v] = cur & 15;                // (gone vehicles too: their cursors are canonical after a load as well)
-  out_len[v] = len - ((cur >> 4) << 4);
+  const PathLive l = path_live(d.path_cur[v], d.path_len[v]);
+  out_cur[v] = l.cur;                   // (gone vehicles too: their cursors are canonical after a load as well)
+  out_len[v] = l.len;
   uint32_t o = (uint32_t)off;
   const uint32_t src = d.path_off[v] + (uint32_t)w0;
   for (int q = 0; q < mw; q++) out[o + q] = d.pool[src + q];
@@ -560,9 +559,9 @@ int ts_checkpoint_load(ts_handle e, const void* src, uint64_t n) {
       memcpy(&f, fl + v, 2);
       if (!(f & VF_ALIVE)) continue;
       memcpy(&c0, cur + v, 4); memcpy(&l0, len + v, 4);
-      if (c0 < 0 || c0 > 15) return bad("path cursor");
-      want += (uint64_t)std::max(0, (l0 + 15) >> 4);
-      for (int a = 0; a < 4; a++) { memcpy(&la, axl[a] + v, 4); if (la > 0) want += (uint64_t)((la + 15) >> 4); }
+      if (c0 < 0 || c0 > PATH_STEP_MASK) return bad("path cursor");
+      want += (uint64_t)path_live(c0, l0).words;
+      for (int a = 0; a < 4; a++) { memcpy(&la, axl[a] + v, 4); want += (uint64_t)aux_words(la); }
     }
     if (want != S.path_words) return bad("path words");
   }

@@ -605,7 +605,7 @@ static int plan_vehicle(ts_handle e, int vid, int start, int goal) {
   if (e->P.pathfinding_cache && len > 0 && !(fl & (VF_OVER | VF_DETOUR))) {
     ts_engine::CachedPath cp;
     cp.len = len;
-    cp.words.resize((size_t)(len + 15) / 16);
+    cp.words.resize((size_t)path_words(len));
     uint32_t off = 0;
     HIPOK(hipMemcpy(&off, d.path_off + vid, 4, hipMemcpyDeviceToHost));
     HIPOK(hipMemcpy(cp.words.data(), d.pool + off, cp.words.size() * 4, hipMemcpyDeviceToHost));
@@ -641,7 +641,7 @@ static int add_vehicles_any(ts_handle e, int32_t n, const int32_t* start_xy, con
   for (int i = 0; i < n; i++) {
     long long len = O(i + 1) - O(i);
     if (len < 0 || len > 0x7FFFFFFF) return fail(e, TS_E_INVALID, "path_off must be non-decreasing");
-    words += ((size_t)len + 15) / 16;
+    words += path_words((size_t)len);
   }
   if (e->pool_used + words >= (1ull << 32)) return fail(e, TS_E_CAPACITY, "path pool exceeds 2^32 words");
   std::vector<uint32_t> enc(words, 0);
@@ -662,20 +662,18 @@ static int add_vehicles_any(ts_handle e, int32_t n, const int32_t* start_xy, con
       int dir;
       if (path_xy && off32) {
         int x = path_xy[2 * (o + k)], y = path_xy[2 * (o + k) + 1];
-        int dx = x - px, dy = y - py;
-        if (dx == 0 && dy == 1) dir = 0; else if (dx == 1 && dy == 0) dir = 1;
-        else if (dx == 0 && dy == -1) dir = 2; else if (dx == -1 && dy == 0) dir = 3;
-        else return fail(e, TS_E_INVALID, "explicit path is not a 4-adjacent chain");
+        dir = dir_of_step(x - px, y - py);
+        if (dir < 0) return fail(e, TS_E_INVALID, "explicit path is not a 4-adjacent chain");
         px = x; py = y;
       } else {
         dir = path_dirs[o + k];
         if (dir > 3) return fail(e, TS_E_INVALID, "direction code out of range");
-        px += (dir == 1) - (dir == 3); py += (dir == 0) - (dir == 2);
+        px += dir_dx(dir); py += dir_dy(dir);
       }
       if (px < 0 || px >= W || py < 0 || py >= H) return fail(e, TS_E_INVALID, "explicit path leaves the grid");
-      enc[wpos + (k >> 4)] |= (uint32_t)dir << ((k & 15) * 2);
+      path_put(enc.data() + wpos, k, dir);
     }
-    wpos += ((size_t)len + 15) / 16;
+    wpos += path_words((size_t)len);
   }
   return add_vehicles_core(e, n, start, goal, pop, plen, poff, enc);
 }

@@ -40,19 +40,13 @@ __device__ __forceinline__ int32_t* ax_buf(const AScratch& S, int k) { return k 
 // sequential reader over an aux path (staged cells or pool-resident directions)
 struct AxReader {
   const int32_t* cells;
-  const uint32_t* pool;
-  uint32_t off;
-  int cell, idx, W;
+  PathWalk walk;   // (walk.idx counts the staged cells too)
   __device__ void init(const Dev& d, const AScratch& S, const VW& v, int k) {
-    idx = 0; W = d.W; pool = d.pool;
+    walk.idx = 0; walk.W = d.W; walk.pool = d.pool;
     if (v.ax_staged[k]) { cells = ax_buf(S, k); }
-    else { cells = nullptr; off = d.ax_off[k][v.vid]; cell = d.ax_start[k][v.vid]; }
+    else { cells = nullptr; walk.off = d.ax_off[k][v.vid]; walk.cell = d.ax_start[k][v.vid]; }
   }
-  __device__ __forceinline__ int next() {
-    if (cells) return cells[idx++];
-    cell = step_cell(cell, path_dir(pool, off, idx++), W);
-    return cell;
-  }
+  __device__ __forceinline__ int next() { return cells ? cells[walk.idx++] : walk.next(); }
 };
 
 __device__ __forceinline__ int vw_path_cell(const Dev& d, const AScratch* S, const VW& v, int k, int& walk) {
@@ -75,15 +69,16 @@ __device__ void scan_ahead_dev(const Dev& d, const TsParams& P, const AScratch* 
     int cells[SCAN_MAX];
     uint32_t dyn[SCAN_MAX];   // the dword holding occ / stop / stuck / stat
     // the next 16 steps are at most 32 bits of the direction string: two pool words, decoded in registers
-    const uint32_t wi = (uint32_t)v.pcur >> 4, nwords = (uint32_t)path_words(v.pcur + v.plen);
+    // (path_window without its test of the first word: path_words.h)
+    const uint32_t wi = (uint32_t)v.pcur >> PATH_STEP_SHIFT, nwords = (uint32_t)path_words(v.pcur + v.plen);
     uint64_t bits = d.pool[v.off + wi];
     if (wi + 1 < nwords) bits |= (uint64_t)d.pool[v.off + wi + 1] << 32;
-    bits >>= (v.pcur & 15) * 2;
+    bits >>= (v.pcur & PATH_STEP_MASK) * PATH_DIR_BITS;
     {
       int c = v.pos;
 #pragma unroll
       for (int k = 0; k < SCAN_MAX; k++) {
-        if (k < look) c = step_cell(c, (int)((bits >> (2 * k)) & 3), d.W);
+        if (k < look) c = step_cell(c, (int)((bits >> (PATH_DIR_BITS * k)) & PATH_DIR_MASK), d.W);
         cells[k] = c;
       }
     }
@@ -327,13 +322,12 @@ __device__ void encode_cells(const Dev& d, uint32_t off, int start_cell, const i
   uint32_t word = 0;
   for (int k = 0; k < len; k++) {
     int c = cells[k];
-    int delta = c - prev;
-    int dir = delta == d.W ? 0 : delta == 1 ? 1 : delta == -d.W ? 2 : 3;
-    word |= (uint32_t)dir << ((k & 15) * 2);
-    if ((k & 15) == 15) { d.pool[off + (k >> 4)] = word; word = 0; }
+    int dir = dir_of_delta(c - prev, d.W);
+    word |= (uint32_t)dir << ((k & PATH_STEP_MASK) * PATH_DIR_BITS);   // (path_put's place, in a register: path_words.h)
+    if ((k & PATH_STEP_MASK) == PATH_STEP_MASK) { d.pool[off + (k >> PATH_STEP_SHIFT)] = word; word = 0; }
     prev = c;
   }
-  if (len & 15) d.pool[off + (len >> 4)] = word;
+  if (len & PATH_STEP_MASK) d.pool[off + (len >> PATH_STEP_SHIFT)] = word;
 }
 // A plan into the pool, in one allocation: the new path (S.P[0..v.plen), if `path`) and the staged aux paths, from v.pos on;
 // the vehicle's path and aux records then point at them.  Returns what was rewritten as Dev::chg counts it (bit 0 path,
@@ -558,22 +552,20 @@ TS_REPLAN_OCC __global__ void __launch_bounds__(64) k_spawn_plan(Dev d, TsParams
   if (one) *status = len;
 }
 
-// path-pool garbage collection: every live vehicle copies the words it still needs into a fresh pool
+// path-pool garbage collection: every live vehicle copies the words it still needs (path_words.h: path_live) into a fresh pool
 __global__ void k_pool_gc(Dev d, int n_active, uint32_t* new_pool, unsigned long long* new_used) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_active) return;
   int vid = d.active[i];
   if (vid < 0) return;
   {
-    int cur = d.path_cur[vid], len = d.path_len[vid];
-    int w0 = cur >> 4, words = path_words(len) - w0;
-    d.path_off[vid] = words > 0 ? (uint32_t)move_words(new_pool, new_used, d.pool + d.path_off[vid] + w0, words) : 0u;
-    d.path_cur[vid] = cur & 15; d.path_len[vid] = len - (w0 << 4);
+    const PathLive l = path_live(d.path_cur[vid], d.path_len[vid]);
+    d.path_off[vid] = l.words > 0 ? (uint32_t)move_words(new_pool, new_used, d.pool + d.path_off[vid] + l.w0, l.words) : 0u;
+    d.path_cur[vid] = l.cur; d.path_len[vid] = l.len;
   }
   for (int k = 0; k < 4; k++) {
-    int len = d.ax_len[k][vid];
-    if (len <= 0) continue;
-    d.ax_off[k][vid] = (uint32_t)move_words(new_pool, new_used, d.pool + d.ax_off[k][vid], path_words(len));
+    const int words = aux_words(d.ax_len[k][vid]);
+    if (words > 0) d.ax_off[k][vid] = (uint32_t)move_words(new_pool, new_used, d.pool + d.ax_off[k][vid], words);
   }
 }
 

@@ -22,8 +22,6 @@ struct DemandArgs {
   int spl;                   // path steps per lane and iteration (a team covers spl * T)
 };
 
-__device__ __forceinline__ int dm_delta(int dir, int W) { return dir == 0 ? W : dir == 1 ? 1 : dir == 2 ? -W : -1; }
-
 // A team of T lanes per vehicle, 64 / T vehicles per wavefront, taken in the active list's order.  Per iteration a team
 // covers spl * T steps of the path: lane l decodes steps [l * spl, (l + 1) * spl) into the displacement they add up to
 // (the packed words start at path_cur, mid-word as a rule), an exclusive prefix sum over the team turns the displacements
@@ -61,8 +59,8 @@ __global__ void __launch_bounds__(BLK) k_demand_walk(DemandArgs a) {
       int disp = 0;
       uint32_t w = 0;
       for (int j = 0, s = pcur + k0; j < nv; j++, s++) {
-        if (j == 0 || (s & 15) == 0) w = a.pool[off + ((uint32_t)s >> 4)];
-        disp += dm_delta((w >> ((s & 15) * 2)) & 3, a.W);
+        if (j == 0 || (s & PATH_STEP_MASK) == 0) w = a.pool[off + ((uint32_t)s >> PATH_STEP_SHIFT)];
+        disp += dir_delta((w >> ((s & PATH_STEP_MASK) * PATH_DIR_BITS)) & PATH_DIR_MASK, a.W);
       }
       int incl = disp;
       for (int o = 1; o < T; o <<= 1) {
@@ -75,9 +73,9 @@ __global__ void __launch_bounds__(BLK) k_demand_walk(DemandArgs a) {
       if (k0 < a.limit) { bin = k0 / a.bin_cells; rem = k0 - bin * a.bin_cells; }
       unsigned long long pk = 0;   // eight 8-bit counts, one per bin
       for (int j = 0, s = pcur + k0; j < nv; j++, s++) {
-        if (j == 0 || (s & 15) == 0) w = a.pool[off + ((uint32_t)s >> 4)];
-        const int dir = (w >> ((s & 15) * 2)) & 3;
-        c += dm_delta(dir, a.W);
+        if (j == 0 || (s & PATH_STEP_MASK) == 0) w = a.pool[off + ((uint32_t)s >> PATH_STEP_SHIFT)];
+        const int dir = (w >> ((s & PATH_STEP_MASK) * PATH_DIR_BITS)) & PATH_DIR_MASK;
+        c += dir_delta(dir, a.W);
         if ((unsigned)c < (unsigned)a.N) {
           atomicAdd(&a.planes[(size_t)(bin * 4 + dir) * (size_t)a.N + (size_t)c], 1u);
           pk += 1ull << (bin * 8);

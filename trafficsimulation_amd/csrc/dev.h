@@ -6,6 +6,7 @@
 #include "../../include/trafficsim_observe.h"
 #include "../../include/trafficsim_triplog.h"
 #include "astar_words.h"
+#include "path_words.h"
 
 #define BLK 256
 
@@ -170,14 +171,6 @@ struct Dev {
 };
 static_assert(sizeof(Dev) == 976, "Dev travels by value and lies in the A* kernels' scratch: new members go into its padding");
 
-__device__ __forceinline__ int path_dir(const uint32_t* pool, uint32_t off, int k) {
-  return (pool[off + ((uint32_t)k >> 4)] >> ((k & 15) * 2)) & 3;
-}
-// pool words of a direction string of `len` steps (sixteen 2-bit directions per word)
-__device__ __forceinline__ int path_words(int len) { return (len + 15) >> 4; }
-__device__ __forceinline__ int step_cell(int cell, int dir, int W) {
-  return dir == 0 ? cell + W : dir == 1 ? cell + 1 : dir == 2 ? cell - W : cell - 1;
-}
 __device__ __forceinline__ void set_occ(const Dev& d, int c, int8_t v) { d.cell[c].occ = v; d.occ[c] = v; }
 __device__ __forceinline__ void set_stop(const Dev& d, int c, int8_t v) { d.cell[c].stop = v; d.stop[c] = v; }
 // cell -> (x, y) without an integer division (falls back to one when the map is beyond the magic number's range)

@@ -138,11 +138,9 @@ __global__ void k_move_claim(Dev d, TsParams P, int n_sched, uint32_t prefix, co
     } else {
       const int m = d.max_steps[vid];
       claim(d, pos, 0, key);
-      const uint32_t off = d.path_off[vid];
-      const int pcur = d.path_cur[vid];
-      int c = pos;
+      PathWalk w{d.pool, d.path_off[vid], d.path_cur[vid], pos, d.W};
       for (int k = 0; k < m; k++) {
-        c = step_cell(c, path_dir(d.pool, off, pcur + k), d.W);
+        const int c = w.next();
         claim(d, c, 0, key);
         if (d.G > 0) claim(d, c, 3, key);
       }
@@ -281,7 +279,7 @@ __device__ __forceinline__ void vehicle_step_dev(const Dev& d, const TsParams& P
           else {
             set_occ(d, c, 0); set_occ(d, nc, 1);
             d.cell[c].stuck = 0; d.cell[nc].stuck = (k == 0 && was_stuck) ? 1 : 0;
-            lastdir = nc == c + d.W ? 0 : nc == c + 1 ? 1 : nc == c - d.W ? 2 : 3;
+            lastdir = nc == c + d.W ? 0 : nc == c + 1 ? 1 : nc == c - d.W ? 2 : 3;   // (dir_of_delta, on the cells: path_words.h)
             if (d.obs_enter) obs_enter_dev(d, lastdir, nc);
             c = nc; moved++;
           }
@@ -470,17 +468,17 @@ __global__ void k_move_resolve(Dev d, TsParams P, int n_sched, uint32_t prefix, 
       const int pcur = d.path_cur[vid];
       // the next 8 steps are at most 16 bits of the direction string: two pool words, decoded in registers
       uint64_t bits = 0;
-      if (m > 0) {
-        const uint32_t wi = (uint32_t)pcur >> 4, nwords = ((uint32_t)d.path_len[vid] + 15u) >> 4;
+      if (m > 0) {   // (path_window without its test of the first word: path_words.h)
+        const uint32_t wi = (uint32_t)pcur >> PATH_STEP_SHIFT, nwords = ((uint32_t)d.path_len[vid] + (uint32_t)PATH_STEP_MASK) >> PATH_STEP_SHIFT;
         bits = d.pool[off + wi];
         if (wi + 1 < nwords) bits |= (uint64_t)d.pool[off + wi + 1] << 32;
-        bits >>= (pcur & 15) * 2;
+        bits >>= (pcur & PATH_STEP_MASK) * PATH_DIR_BITS;
       }
       int c = pos;
       cells[0] = pos;
 #pragma unroll
       for (int k = 0; k < MOVE_MAX; k++) {
-        if (k < m) c = step_cell(c, (int)((bits >> (2 * k)) & 3), d.W);
+        if (k < m) c = step_cell(c, (int)((bits >> (PATH_DIR_BITS * k)) & PATH_DIR_MASK), d.W);
         cells[k + 1] = c;
       }
 #pragma unroll
@@ -509,9 +507,9 @@ __global__ void k_move_resolve(Dev d, TsParams P, int n_sched, uint32_t prefix, 
       if (claim_rank(d.cell[pos].claim[0], prefix) < r || claim_rank(d.cell[pos].claim[1], prefix) < r) safe = false;
       const uint32_t off = d.path_off[vid];
       const int pcur = d.path_cur[vid];
-      int c = pos;
+      PathWalk w{d.pool, off, pcur, pos, d.W};
       for (int k = 0; k < mm && safe; k++) {
-        c = step_cell(c, path_dir(d.pool, off, pcur + k), d.W);
+        const int c = w.next();
         if (claim_rank(d.cell[c].claim[0], prefix) < r || claim_rank(d.cell[c].claim[1], prefix) < r) safe = false;
         if (lights && claim_rank(d.cell[c].claim[2], prefix) < r) safe = false;
       }
@@ -708,10 +706,9 @@ __global__ void k_rows(Dev d, int n_active, const uint32_t* crc_table, int32_t* 
   uint32_t crc = 0;
   if (plen > 0) {
     crc = 0xFFFFFFFFu;
-    int c = pos;
-    uint32_t off = d.path_off[vid];
+    PathWalk w{d.pool, d.path_off[vid], pcur, pos, d.W};
     for (int k = 0; k < plen; k++) {
-      c = step_cell(c, path_dir(d.pool, off, pcur + k), d.W);
+      const int c = w.next();
       int32_t xy[2] = {c % d.W, c / d.W};
       const uint8_t* p = (const uint8_t*)xy;
       for (int b = 0; b < 8; b++) crc = crc_table[(crc ^ p[b]) & 0xff] ^ (crc >> 8);
@@ -735,10 +732,10 @@ __global__ void k_meta_rows(Dev d, int n_active, int32_t* rows) {
 
 __global__ void k_path_cells(Dev d, int vid, int32_t* xy) {
   if (threadIdx.x || blockIdx.x) return;
-  int pcur = d.path_cur[vid], plen = d.path_len[vid] - pcur, c = d.pos[vid];
-  uint32_t off = d.path_off[vid];
+  const int pcur = d.path_cur[vid], plen = d.path_len[vid] - pcur;
+  PathWalk w{d.pool, d.path_off[vid], pcur, d.pos[vid], d.W};
   for (int k = 0; k < plen; k++) {
-    c = step_cell(c, path_dir(d.pool, off, pcur + k), d.W);
+    const int c = w.next();
     xy[2 * k] = c % d.W; xy[2 * k + 1] = c / d.W;
   }
 }

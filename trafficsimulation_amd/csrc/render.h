@@ -86,8 +86,7 @@ __global__ void k_render_routes(RenderArgs a) {
     int dx = 0, dy = 0;
     if (k < plen) {
       const int dir = path_dir(a.pool, off, pcur + k);
-      dx = dir == 1 ? 1 : dir == 3 ? -1 : 0;
-      dy = dir == 0 ? 1 : dir == 2 ? -1 : 0;
+      dx = dir_dx(dir); dy = dir_dy(dir);
     }
     for (int o = 1; o < 64; o <<= 1) {   // inclusive prefix sums
       const int ux = __shfl_up(dx, o), uy = __shfl_up(dy, o);

@@ -284,8 +284,9 @@ __global__ void k_replan_export(Dev d, const int32_t* owned, int n, ReplanRec* r
   if (count_only) {
     if (vid < 0) return;
     const uint8_t chg = d.chg[vid];
-    unsigned long long nw = (chg & 1) ? (unsigned long long)path_words(d.path_len[vid]) : 0ull;
-    for (int k = 0; k < 4; k++) if ((chg >> (1 + k)) & 1) nw += (unsigned long long)path_words(d.ax_len[k][vid]);
+    // (the live words of what was rewritten, path_words.h: a path just committed has its cursor at 0)
+    unsigned long long nw = (chg & 1) ? (unsigned long long)path_live(0, d.path_len[vid]).words : 0ull;
+    for (int k = 0; k < 4; k++) if ((chg >> (1 + k)) & 1) nw += (unsigned long long)aux_words(d.ax_len[k][vid]);
     if (nw) atomicAdd(words_n, nw);
     return;
   }
@@ -299,10 +300,10 @@ __global__ void k_replan_export(Dev d, const int32_t* owned, int n, ReplanRec* r
   const uint8_t chg = d.chg[vid];
   d.chg[vid] = 0;
   r.path_len = d.path_len[vid]; r.path_woff = -1;
-  if (chg & 1) r.path_woff = (int32_t)move_words(words, words_n, d.pool + d.path_off[vid], path_words(r.path_len));
+  if (chg & 1) r.path_woff = (int32_t)move_words(words, words_n, d.pool + d.path_off[vid], path_live(0, r.path_len).words);
   for (int k = 0; k < 4; k++) {
     r.ax_len[k] = d.ax_len[k][vid]; r.ax_start[k] = d.ax_start[k][vid]; r.ax_woff[k] = -1;
-    if ((chg >> (1 + k)) & 1) r.ax_woff[k] = (int32_t)move_words(words, words_n, d.pool + d.ax_off[k][vid], path_words(r.ax_len[k]));
+    if ((chg >> (1 + k)) & 1) r.ax_woff[k] = (int32_t)move_words(words, words_n, d.pool + d.ax_off[k][vid], aux_words(r.ax_len[k]));
   }
   recs[t] = r;
 }
@@ -317,14 +318,14 @@ __global__ void k_replan_import(Dev d, const ReplanRec* __restrict__ recs, int n
   d.max_steps[vid] = (int8_t)r.max_steps; d.cooldown[vid] = r.cooldown; d.over_dur[vid] = r.over_dur; d.det_dur[vid] = r.det_dur;
   d.stranded_left[vid] = r.stranded_left; d.tier_hint[vid] = (uint8_t)r.hint;
   if (r.path_woff >= 0) {
-    d.path_off[vid] = (uint32_t)move_words(d.pool, &d.cnt->pool_used, words + r.path_woff, path_words(r.path_len));
+    d.path_off[vid] = (uint32_t)move_words(d.pool, &d.cnt->pool_used, words + r.path_woff, path_live(0, r.path_len).words);
     d.path_len[vid] = r.path_len; d.path_cur[vid] = 0;
   }
   for (int k = 0; k < 4; k++) {
     d.ax_len[k][vid] = r.ax_len[k];
     if (r.ax_woff[k] >= 0) {
       d.ax_start[k][vid] = r.ax_start[k];
-      d.ax_off[k][vid] = (uint32_t)move_words(d.pool, &d.cnt->pool_used, words + r.ax_woff[k], path_words(r.ax_len[k]));
+      d.ax_off[k][vid] = (uint32_t)move_words(d.pool, &d.cnt->pool_used, words + r.ax_woff[k], aux_words(r.ax_len[k]));
     }
   }
 }
