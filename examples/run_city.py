@@ -66,6 +66,8 @@ if __name__ == "__main__":
     ap.add_argument("--trips", metavar="OUT.npy", default=None, help="write one record per finished trip (capi.TRIP_DTYPE) to this file")
     ap.add_argument("--trip-capacity", type=int, default=1 << 20, help="records the trip log holds (later ones are dropped and counted)")
     ap.add_argument("--demand", metavar="OUT.npy", default=None, help="write the planned load at the end of the run (remaining routes per cell, (H, W) uint32) to this file")
+    ap.add_argument("--select-link", nargs=2, metavar=("X,Y", "OUT.npy"), default=None,
+                    help="write the select-link load of cell (X, Y) at the end of the run (the remaining routes of the vehicles that will enter it, per cell, (H, W) uint32) to OUT.npy")
     ap.add_argument("--isochrone", nargs=2, metavar=("X,Y", "OUT.npy"), default=None,
                     help="write the travel cost from every cell to cell (X, Y) at the end of the run ((H, W) uint32, 0xFFFFFFFF: unreachable) to OUT.npy")
     ap.add_argument("--evacuate", metavar="OUT.npy", default=None,
@@ -88,6 +90,16 @@ if __name__ == "__main__":
         np.save(a.demand, load["load"][0])
         y, x = divmod(int(load["load"][0].argmax()), m.width)
         print(f"planned load: {load['steps']} steps of {load['vehicles']} vehicles; busiest cell ({x}, {y}) with {int(load['load'][0, y, x])} planned entries")
+    if a.select_link:
+        import numpy as np
+        x, y = (int(v) for v in a.select_link[0].split(","))
+        # on the device (include/trafficsim_selectlink.h): whose routes cross the gate, then the demand walk over those vehicles alone
+        link = m.select_link([[(x, y)]])
+        load = m.select_link_load(any=1)
+        np.save(a.select_link[1], load["load"][0])
+        by_dir = ", ".join(f"{d} {int(n)}" for d, n in zip("NESW", link["cross"][0, 0]))
+        print(f"select link ({x}, {y}): {link['crossing']} of {link['vehicles']} vehicles cross it {link['crossings']} times ({by_dir}); "
+              f"their routes hold {load['steps']} steps")
     if a.isochrone:
         import numpy as np
         x, y = (int(v) for v in a.isochrone[0].split(","))

@@ -24,7 +24,9 @@ WANT = ["k_replan", "k_replan_quad", "quad_policy", "replan_turn", "k_astar_sing
         # routes along a cost field (cfroute.h; k_cfr_hops: the last instance of the template the compiler reports)
         "k_cfr_hops", "k_cfr_count", "k_cfr_write", "k_cfr_load", "k_cfr_cells",
         # the cold readers and movers of the path pool (path_words.h)
-        "k_pool_gc", "k_replan_export", "k_replan_import", "k_ckpt_count_paths", "k_ckpt_pack_paths", "k_ckpt_unpack_paths", "k_rows", "k_path_cells"]
+        "k_pool_gc", "k_replan_export", "k_replan_import", "k_ckpt_count_paths", "k_ckpt_pack_paths", "k_ckpt_unpack_paths", "k_rows", "k_path_cells",
+        # select-link analysis (selectlink.h; k_selectlink_walk: the last instance of the template the compiler reports)
+        "k_selectlink_walk", "k_selectlink_scatter", "k_selectlink_select", "k_selectlink_od"]
 r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-pthread", "--offload-arch=gfx950", "--cuda-device-only", "-c",
                     "-o", "/dev/null", "engine.hip", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:], cwd=CSRC, capture_output=True, text=True)
 cur, rows = None, {}

@@ -1186,6 +1186,13 @@ class CApi:
         from .costfield import CostField
         return CostField(self)
 
+    # ---- select-link analysis (include/trafficsim_selectlink.h): entries, structs and methods live in selectlink.py ----
+    @property
+    def selectlink(self):
+        """The select-link entries of this engine, as a selectlink.SelectLink (a view like costfield)."""
+        from .selectlink import SelectLink
+        return SelectLink(self)
+
     # ---- trip log (include/trafficsim_triplog.h) ----------------------------------------------------
     @property
     def has_triplog(self) -> bool:

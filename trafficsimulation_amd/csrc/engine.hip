@@ -47,6 +47,7 @@
 #include "astar_batch.h"
 #include "observe.h"
 #include "demand.h"
+#include "selectlink.h"
 #include "triplog.h"
 #include "kernels.h"
 #include "lights_ext.h"
@@ -73,3 +74,4 @@
 #include "demand_api.h"
 #include "costfield_api.h"
 #include "cfroute_api.h"
+#include "selectlink_api.h"

@@ -1050,9 +1050,9 @@ class CityModel:
         return out
 
     # ---- route demand (include/trafficsim_demand.h) ---------------------------------------------------
-    def _demand_compute(self, bins, bin_cells, open_tail, vehicles) -> dict:
+    def _demand_compute(self, bins, bin_cells, open_tail, vehicles, select=None) -> dict:
+        """`select`: a byte mask over the spawn indices handed out so far, in place of `vehicles` (select_link_load)."""
         self._flush_host_writes()
-        select = None
         if vehicles is not None:
             select = np.zeros(self.engine.num_spawned(), dtype=np.uint8)
             idx = np.asarray([v._spawn_idx if hasattr(v, "_spawn_idx") else int(v) for v in vehicles], dtype=np.int64)
@@ -1068,7 +1068,10 @@ class CityModel:
         (bins, ceil(H / pooled), ceil(W / pooled)), with `pooled`: sums over pooled x pooled blocks), "by_direction":
         (bins, 4, H, W) by the direction N E S W of the step into the cell} and the fields of `engine.demand_info()`.  A snapshot
         of the state between two steps: not updated by step() and not carried by save / load / deepcopy / pickle."""
-        info = self._demand_compute(bins, bin_cells, open_tail, vehicles)
+        return self._planned_planes(self._demand_compute(bins, bin_cells, open_tail, vehicles), pooled)
+
+    def _planned_planes(self, info, pooled) -> dict:
+        """planned_load()'s result from the info of the compute that just ran."""
         eng, nb = self.engine, info["n_bins"]
         if pooled is None:
             load = np.stack([eng.demand_plane(b) for b in range(nb)])
@@ -1093,6 +1096,64 @@ class CityModel:
                         "planned_throughput": [sum(by_dir[d][b] for d in "NESW") for b in range(info["n_bins"])],
                         "planned_throughput_by_direction": by_dir})
         return out
+
+    # ---- select-link analysis (include/trafficsim_selectlink.h) ------------------------------------------
+    def gate_of_group(self, group, which: str = "ns_in") -> list:
+        """A gate made of a light group's cells, from the CSR tables intersection_demand() reads: its N-S approach cells
+        (`"ns_in"`), its W-E approach cells (`"ew_in"`) or the intersection's own cells (`"cells"`), open to all directions.
+        `group`: an IntersectionLightGroup or its index."""
+        keys = {"ns_in": "g_ns_in", "ew_in": "g_ew_in", "cells": "g_icell"}
+        if which not in keys:
+            raise ValueError(f"gate_of_group: unknown part {which!r} (one of {sorted(keys)})")
+        g = int(getattr(group, "index", group))
+        off = np.asarray(self.tables[keys[which] + "_off"])
+        if not 0 <= g < len(off) - 1:
+            raise ValueError(f"gate_of_group: no light group {g}")
+        xy = np.asarray(self.tables[keys[which] + "_xy"]).reshape(-1, 2)[off[g]:off[g + 1]]
+        return [(int(x), int(y)) for x, y in xy]
+
+    def select_link(self, gates, bins: int = 1, bin_cells: int = 1, open_tail: bool = True) -> dict:
+        """Whose routes go through here: the remaining main path of every live vehicle walked over `gates` on the device.
+        `gates`: a list of gates, each a list of (x, y) cells - open to every direction - or (x, y, "NESW"-subset): the
+        directions of the step into the cell that count.  Bins as for planned_load().  Returns {"cross": (G, bins, 4) uint64
+        crossings by gate, bin and direction N E S W, "pair": (G, G) uint64 vehicles whose routes cross both gates (the
+        diagonal: the gate's vehicles)} and the fields of `engine.selectlink.info()` ("vehicles", "crossing", "crossings", ...).
+        The result stays in the engine for select_link_vehicles / _load / _od.  A snapshot of the state between two steps: not
+        updated by step() and not carried by save / load / deepcopy / pickle (the model those give has neither gates nor a
+        result)."""
+        self._flush_host_writes()
+        sl = self.engine.selectlink
+        sl.set_gates(gates)
+        info = sl.compute(bins, bin_cells, open_tail)
+        cross, pair = sl.tables()
+        return dict(info, cross=cross, pair=pair)
+
+    def select_link_vehicles(self, any: int = 0, all: int = 0, none: int = 0) -> list:
+        """The agents, of the vehicles the last select_link() walked, whose gate mask meets (any == 0 or mask & any) and
+        mask & all == all and mask & none == 0 (bit g: gate g), in spawn order; vehicles that have left since are left out."""
+        sel, _ = self.engine.selectlink.select(any, all, none)
+        live = {int(r[0]) for r in self._snapshot()["rows"]}
+        return [self._vehicle_view(int(i)) for i in np.nonzero(sel)[0] if int(i) in live]
+
+    def select_link_load(self, any: int = 0, all: int = 0, none: int = 0, bins: int = 1, bin_cells: int = 1, open_tail: bool = True,
+                         pooled=None) -> dict:
+        """planned_load() of the vehicles that selection picks, with its bins, bin_cells, open_tail and pooled: the mask goes
+        from the select-link result to the demand walk as it is, and the load is of the routes as they are now."""
+        sel, _ = self.engine.selectlink.select(any, all, none)
+        mask = np.zeros(self.engine.num_spawned(), dtype=np.uint8)     # (vehicles spawned since the compute are not selected)
+        mask[:len(sel)] = sel
+        return self._planned_planes(self._demand_compute(bins, bin_cells, open_tail, None, mask), pooled)
+
+    def select_link_od(self, any: int = 0, all: int = 0, none: int = 0) -> dict:
+        """Where the selected vehicles were and where they were going when select_link() ran, by the zones of od_matrix():
+        {"zones": names, "count": (Z, Z) int64 indexed [zone of the cell, zone of the goal], "unzoned"}."""
+        zone, names = self._block_zones()
+        sl = self.engine.selectlink
+        if len(names) > capi.TRIPLOG_MAX_ZONES:
+            raise ValueError(f"select_link_od: {len(names)} zones, the engine takes {capi.TRIPLOG_MAX_ZONES}")
+        sl.set_zones(zone, len(names))
+        count, unzoned = sl.od(any, all, none)
+        return {"zones": names, "count": count, "unzoned": unzoned}
 
     # ---- cost fields (include/trafficsim_costfield.h) --------------------------------------------------
     @staticmethod
