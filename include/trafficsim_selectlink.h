@@ -46,8 +46,8 @@
  * simulation state and not part of a checkpoint; ts_checkpoint_load leaves gates, result and zones of the target as they
  * are; a new handle has neither gates nor a result.
  *
- * Sharded mode (ts_set_replan_sharding): vehicle state and paths are replicated, so every rank would compute the same
- * result and nothing is exchanged.  Not tested.
+ * Sharded mode (ts_set_replan_sharding): vehicle state and paths are replicated, so every rank computes the same
+ * result and nothing is exchanged (tests/test_gpu_ext_paths.py runs it on two ranks).
  *
  * Calls
  *   - only between ts_step calls, from the handle's caller thread (trafficsim.h conventions).

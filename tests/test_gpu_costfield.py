@@ -11,6 +11,7 @@ import pytest
 from tests import costfield_expect as ce
 from tests import procs
 from tests.engine_util import assert_same_state, engine_for, full_state, refused
+from tests.ext_rules import rule_of
 from tests.kats_util import cost_kats
 from tests.trace_util import setup_from_trace, trace_path
 from trafficsimulation_amd import _capi as capi
@@ -29,12 +30,6 @@ def set_tile(monkeypatch, tile):
         monkeypatch.delenv("TS_DEBUG_COSTFIELD_TILE", raising=False)
     else:
         monkeypatch.setenv("TS_DEBUG_COSTFIELD_TILE", str(tile))
-
-
-def rule_of(api, params, tables):
-    """The step rule on the engine's maps as they are now (the density map is download_density's)."""
-    return ce.Rule.from_params(params, tables["allowed_dirs_map"], tables["is_road_map"], tables["road_type_map"],
-                               api.map(capi.MAP_OCCUPANCY), api.map(capi.MAP_STOP), api.density())
 
 
 def check_field(api, rule, seeds, seed_cost=None, ctx="", tiles=TILES, monkeypatch=None, **q):

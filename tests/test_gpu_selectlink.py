@@ -13,6 +13,7 @@ from tests import observe_util as ou
 from tests import procs
 from tests import selectlink_expect as se
 from tests.engine_util import assert_same_deep_state, deep_state, engine_for, refused
+from tests.ext_rules import check_result, read_result
 from tests.ext_sidecar import read_planes
 from tests.trace_util import setup_from_trace, trace_path
 from trafficsimulation_amd import _capi as capi
@@ -43,28 +44,6 @@ def fixture_want(name, t, which, query):
     tr = load_trace(trace_path(name))
     veh, spawn, n, A, B = fixture_case(name, t)
     return se.walk(int(tr["height"]), int(tr["width"]), veh, spawn, n, (A, B)[which], query[0], query[1], bool(query[2]))
-
-
-def read_result(s):
-    """Everything a result holds, as one dict of arrays and ints."""
-    v, (cross, pair), info = s.vehicles(), s.tables(), s.info()
-    return {"mask": v["mask"], "crossings": v["crossings"], "first_step": v["first_step"], "first_gate": v["first_gate"],
-            "cross": cross, "pair": pair, "t_vehicles": info["vehicles"], "t_crossing": info["crossing"], "t_crossings": info["crossings"]}
-
-
-def check_result(s, want, gates, query, tick, ctx):
-    """One compute of `query` over the gates held against the rule's result `want`."""
-    info = s.compute(*query[:2], bool(query[2]))
-    assert info == s.info(), ctx
-    assert (info["held"], info["n_bins"], info["bin_cells"], info["open_tail"]) == (True, query[0], query[1], bool(query[2])), ctx
-    assert (info["n_gates"], info["n_gate_cells"], info["tick"]) == (len(gates), sum(len(g) for g in gates), tick), ctx
-    assert (info["width"], info["height"], info["n_spawned"]) == (s.api.W, s.api.H, len(want["mask"])), ctx
-    got = read_result(s)
-    for k in ("mask", "crossings", "first_step", "first_gate", "cross", "pair"):
-        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), f"{ctx}: {k} differs at {np.argwhere(got[k] != want[k])[:4].tolist()}"
-    for k in ("t_vehicles", "t_crossing", "t_crossings"):
-        assert got[k] == want[k], f"{ctx}: {k}: {got[k]} != {want[k]}"
-    return got
 
 
 # ---- 1. the fixture expectation, at the default chunk, the smallest and one above the longest path --------------------------------
