@@ -68,6 +68,8 @@ if __name__ == "__main__":
     ap.add_argument("--demand", metavar="OUT.npy", default=None, help="write the planned load at the end of the run (remaining routes per cell, (H, W) uint32) to this file")
     ap.add_argument("--select-link", nargs=2, metavar=("X,Y", "OUT.npy"), default=None,
                     help="write the select-link load of cell (X, Y) at the end of the run (the remaining routes of the vehicles that will enter it, per cell, (H, W) uint32) to OUT.npy")
+    ap.add_argument("--jams", metavar="OUT.npy", default=None,
+                    help="write one record per jam at the end of the run (queues of standing vehicles, jams.JAM_DTYPE) to this file")
     ap.add_argument("--isochrone", nargs=2, metavar=("X,Y", "OUT.npy"), default=None,
                     help="write the travel cost from every cell to cell (X, Y) at the end of the run ((H, W) uint32, 0xFFFFFFFF: unreachable) to OUT.npy")
     ap.add_argument("--evacuate", metavar="OUT.npy", default=None,
@@ -100,6 +102,14 @@ if __name__ == "__main__":
         by_dir = ", ".join(f"{d} {int(n)}" for d, n in zip("NESW", link["cross"][0, 0]))
         print(f"select link ({x}, {y}): {link['crossing']} of {link['vehicles']} vehicles cross it {link['crossings']} times ({by_dir}); "
               f"their routes hold {load['steps']} steps")
+    if a.jams:
+        import numpy as np
+        # on the device (include/trafficsim_jams.h): the connected components of the cells on which a vehicle stands
+        found = m.jams()
+        np.save(a.jams, found["jams"])
+        big = found["jams"][0] if found["n"] else None
+        print(f"jams: {found['n']} with {found['standing_vehicles']} standing vehicles on {found['standing_cells']} cells"
+              + (f"; the largest has {int(big['cells'])} cells from ({int(big['x0'])}, {int(big['y0'])}) to ({int(big['x1'])}, {int(big['y1'])})" if big is not None else ""))
     if a.isochrone:
         import numpy as np
         x, y = (int(v) for v in a.isochrone[0].split(","))

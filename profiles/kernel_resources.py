@@ -26,7 +26,10 @@ WANT = ["k_replan", "k_replan_quad", "quad_policy", "replan_turn", "k_astar_sing
         # the cold readers and movers of the path pool (path_words.h)
         "k_pool_gc", "k_replan_export", "k_replan_import", "k_ckpt_count_paths", "k_ckpt_pack_paths", "k_ckpt_unpack_paths", "k_rows", "k_path_cells",
         # select-link analysis (selectlink.h; k_selectlink_walk: the last instance of the template the compiler reports)
-        "k_selectlink_walk", "k_selectlink_scatter", "k_selectlink_select", "k_selectlink_od"]
+        "k_selectlink_walk", "k_selectlink_scatter", "k_selectlink_select", "k_selectlink_od",
+        # jam detection (jams.h; k_jam_tile: the last instance of the template the compiler reports)
+        "k_jam_mark_vehicles", "k_jam_mark_mask", "k_jam_init", "k_jam_tile", "k_jam_merge", "k_jam_flatten", "k_jam_number",
+        "k_jam_record_cells", "k_jam_record_vehicles", "k_jam_finish", "k_jam_groups"]
 r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-pthread", "--offload-arch=gfx950", "--cuda-device-only", "-c",
                     "-o", "/dev/null", "engine.hip", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:], cwd=CSRC, capture_output=True, text=True)
 cur, rows = None, {}

@@ -1193,6 +1193,13 @@ class CApi:
         from .selectlink import SelectLink
         return SelectLink(self)
 
+    # ---- jam detection (include/trafficsim_jams.h): entries, structs and methods live in jams.py ----
+    @property
+    def jams(self):
+        """The jam-detection entries of this engine, as a jams.Jams (a view like costfield)."""
+        from .jams import Jams
+        return Jams(self)
+
     # ---- trip log (include/trafficsim_triplog.h) ----------------------------------------------------
     @property
     def has_triplog(self) -> bool:

@@ -46,6 +46,7 @@
 #include "astar_quad.h"
 #include "astar_batch.h"
 #include "observe.h"
+#include "jams.h"
 #include "demand.h"
 #include "selectlink.h"
 #include "triplog.h"
@@ -75,3 +76,4 @@
 #include "costfield_api.h"
 #include "cfroute_api.h"
 #include "selectlink_api.h"
+#include "jams_api.h"

@@ -1155,6 +1155,57 @@ class CityModel:
         count, unzoned = sl.od(any, all, none)
         return {"zones": names, "count": count, "unzoned": unzoned}
 
+    # ---- jam detection (include/trafficsim_jams.h) -------------------------------------------------------
+    def jams(self, min_ticks: int = 1, link: str = "flow", top: Optional[int] = None) -> dict:
+        """Where the jams are now: the connected components of the cells on which a vehicle has stood for at least `min_ticks`
+        ticks (parked ones aside), labelled on the device.  `link`: "flow" joins 4-neighbours one of which may drive to the
+        other, "grid" all 4-neighbours.  Returns {"jams": the jams.JAM_DTYPE records sorted by (cells descending, root
+        ascending) and cut to the `top` largest, "label": (H, W) int32, the jam number of every cell (the number a record had
+        before the sort: `"number"` holds it per sorted record), -1 where there is none, "n": the number of jams} and the
+        fields of `engine.jams.info()` ("standing_vehicles", "standing_cells", "largest_cells", "tick", ...).  The result stays
+        in the engine for queue_report / jam_vehicles / jam_load.  A snapshot of the state between two steps: not updated by
+        step() and not carried by save / load / deepcopy / pickle (the model those give has no result)."""
+        self._flush_host_writes()
+        jm = self.engine.jams
+        info = jm.compute(min_ticks, link)
+        rec = jm.records()
+        order = np.lexsort((np.arange(len(rec)), -rec["cells"].astype(np.int64)))
+        if top is not None:
+            order = order[:max(int(top), 0)]
+        return dict(info, jams=rec[order], number=order.astype(np.int32), label=jm.plane("label"), n=info["n_jams"])
+
+    def queue_report(self, min_ticks: int = 1, link: str = "flow") -> List[dict]:
+        """Per light group, keyed like intersection_report(): the queues that reach its N-S and W-E approach cells, each whole
+        - their cells, vehicles, largest extent, longest wait and number - and the standing cells inside its box."""
+        self._flush_host_writes()
+        jm = self.engine.jams
+        info = jm.compute(min_ticks, link)
+        from .jams import JG_FIELDS
+        f = JG_FIELDS.index
+        out = []
+        for g, r in enumerate(jm.groups()):
+            row = {"group": self.intersection_light_groups[g].id if g < len(self.intersection_light_groups) else g,
+                   "index": g, "tick": info["tick"], "box_cells": int(r[f("box_cells")])}
+            for ax in ("ns", "ew"):
+                row.update({f"queue_{ax}": int(r[f(ax + "_cells")]), f"queue_vehicles_{ax}": int(r[f(ax + "_vehicles")]),
+                            f"queue_extent_{ax}": int(r[f(ax + "_extent")]), f"longest_wait_{ax}": int(r[f(ax + "_stuck_max")]),
+                            f"jams_{ax}": int(r[f(ax + "_jams")])})
+            out.append(row)
+        return out
+
+    def jam_vehicles(self, jam: int) -> list:
+        """The agents standing in jam `jam` (its number in the label plane) of the last jams() / queue_report(), in spawn
+        order; vehicles that have left since are left out."""
+        per_vehicle = self.engine.jams.vehicles()
+        if int(jam) < 0:
+            raise ValueError(f"jam_vehicles: {jam} is no jam number")
+        live = {int(r[0]) for r in self._snapshot()["rows"]}
+        return [self._vehicle_view(int(i)) for i in np.nonzero(per_vehicle == int(jam))[0] if int(i) in live]
+
+    def jam_load(self, jam: int, **planned_load_arguments) -> dict:
+        """Where the vehicles of that jam are going: planned_load(vehicles=jam_vehicles(jam), ...)."""
+        return self.planned_load(vehicles=self.jam_vehicles(jam), **planned_load_arguments)
+
     # ---- cost fields (include/trafficsim_costfield.h) --------------------------------------------------
     @staticmethod
     def _seed_cells(seeds) -> np.ndarray:
